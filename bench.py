@@ -27,6 +27,10 @@ The JSON line also carries
                evaluated at the bench length (rank 0, N = 1; "kind": "port, extrapolated");
   config.vae   BASELINE config 4 (Wan2.1 VAE encode + decode at 81 x 512 x 896) run once after the timed region,
                with both roofline fractions (rank 0, N = 1 only).
+
+--dump-outputs DIR writes what the last timed step computed (the network output for the CFG batch, the updated latent) as
+DIR/<name>.npy in float32 (64 MB at most; a larger array is written as a fixed seeded sample); inputs and weights are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -459,6 +463,26 @@ def multichar_leg(net, p, thw, ctx, clip, dev, Lt, Lc, args):
             "path": "scail_dit_block per layer (C executor) + token assembly in the host", "n_gpus": 1}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32, DUMP_BYTES in all.  An array above its share of the budget is written as
+    a fixed sample of its flattened elements (positions drawn with seed 0, sorted: the same for the same shape in every run), so that
+    two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    res = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        res[name] = {"shape": list(a.shape), "file": name + ".npy", "sampled": a.nbytes > share}
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -475,6 +499,8 @@ def main():
     ap.add_argument("--no-cfg-pair", action="store_true", help="A/B: evaluate both CFG elements in layer 0 (no SCAIL_DIT_CFG_PAIR)")
     ap.add_argument("--no-extra-legs", action="store_true", help="skip config.sp_compute_side and config.multichar after the timed region")
     ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 --pmc passes behind roofline.traffic (the stamped profiles/traffic.json value is reported then)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (network output, updated latent) as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -556,6 +582,7 @@ def main():
         v = net.forward_f32(xin, t, ctx, None, concat_images=dummy, ref_concat=ref, concat_smpl_render=pose,
                             image_clip_features=clip, chunk_dim=chunk_dim, cfg_pair=not args.no_cfg_pair)
         ops.cfg_euler_(x, v, args.cfg_scale, float(sig[i + 1] - sig[i]))
+        return v
 
     def barrier():
         if world > 1:
@@ -572,8 +599,9 @@ def main():
     timer.enabled = True
     barrier()
     t0 = time.perf_counter()
+    v_last = None
     for i in range(args.steps):
-        step(args.warmup + i)
+        v_last = step(args.warmup + i)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     barrier()
@@ -584,6 +612,13 @@ def main():
     finite = bool(torch.isfinite(x).all().item())
     x_full = sp.gather_to_rank0(x, chunk_dim) if sp is not None else x       # after the timed region: result fingerprint
     x_abs_mean = float(x_full.abs().mean().item())
+    dumped = None
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step: the network output for the [uncond; cond] batch and the latent after
+        # the CFG + Euler update, gathered to rank 0 (before the legs below reuse the network)
+        v_full = sp.gather_to_rank0(v_last, chunk_dim) if sp is not None else v_last
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {"velocity": v_full, "latent": x_full})
 
     hp, wp = H // 2, W // 2
     Lnoise = T * hp * wp
@@ -788,6 +823,8 @@ def main():
                       + f"; fits: per-token part {cb['c']:.2f} + {cb['a']:.3e} L s, self-attention {cb['a2']:.3e} L + {cb['b']:.3e} L^2 s "
                       f"-> {cb['t_tok']:.1f} + {cb['t_att']:.1f} s per block at L = {L}, x {p['num_layers']} layers = {t_cpu:.0f} s per step "
                       f"(embeddings / final layer < 0.1 % not included)"}
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

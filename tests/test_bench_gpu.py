@@ -35,6 +35,22 @@ def test_bench_single_tiny():
     assert o["cpu_baseline"]["kind"] == "port, extrapolated" and o["cpu_baseline"]["cores"] >= 1 and o["cpu_baseline"]["threads"] >= 1
 
 
+def test_bench_dump_outputs_tiny(tmp_path):
+    """--dump-outputs DIR: after the --steps timed steps, the last step's network output and updated latent as float32 .npy files; the
+    latent is the one the line's fingerprint (config.x_abs_mean) was taken from."""
+    import numpy as np
+    o = _run([sys.executable, "bench.py", "--config", "tiny", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-vae",
+              "--dump-outputs", str(tmp_path / "out")])
+    assert o["steps"] == 3 and o["ms_per_step"] > 0
+    assert o["roofline"]["launches_timed"] == 2 * 3                      # 2 layers x 3 timed steps
+    lat, vel = np.load(tmp_path / "out" / "latent.npy"), np.load(tmp_path / "out" / "velocity.npy")
+    assert lat.dtype == vel.dtype == np.float32
+    assert list(lat.shape) == o["dumped_outputs"]["latent"]["shape"] and lat.shape[0] == 1
+    assert list(vel.shape) == o["dumped_outputs"]["velocity"]["shape"] and vel.shape == (2,) + lat.shape[1:]
+    assert np.isfinite(lat).all() and np.isfinite(vel).all() and float(np.abs(vel).mean()) > 0
+    assert abs(float(np.abs(lat).mean()) - o["config"]["x_abs_mean"]) <= 1e-5 * o["config"]["x_abs_mean"]
+
+
 @pytest.mark.parametrize("mode", ["allgather", "ulysses"])
 def test_bench_two_ranks_one_gpu(mode):
     one = _run([sys.executable, "bench.py", "--config", "tiny", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
@@ -54,9 +70,14 @@ def test_bench_two_ranks_one_gpu(mode):
 
 def test_bench_eight_process_ranks_full_width_two_layers():
     """The driver's 8-rank launch line, `python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8`, at FULL WIDTH AND LENGTH (14B
-    layer shapes, 512x896x81f: 8 ulysses ranks of 5 heads x 6 104 token rows) with 2 of the 40 layers, on the gloo vehicle (all ranks on GPU 0, the
-    exchange staged through the host): eight PROCESSES drive scail_dit_step_sp with SCAIL_DIT_CFG_PAIR, the last-layer pruning and the planned
-    attention launch shape through a real process group, and the gathered result must reproduce the single-rank run of the same 2 layers."""
+    layer shapes, 512x896x81f: 8 ulysses ranks of 5 heads x 6 104 token rows) with 2 of the 40 layers, on the gloo vehicle (the exchange staged
+    through the host): eight PROCESSES drive scail_dit_step_sp with SCAIL_DIT_CFG_PAIR, the last-layer pruning and the planned
+    attention launch shape through a real process group, and the gathered result must reproduce the single-rank run of the same 2 layers.
+    The ranks go one per GPU (bench.py maps a gloo rank to LOCAL_RANK % device count): eight processes on one device oversubscribe it,
+    so the test needs an 8-GPU box."""
+    import torch
+    if torch.cuda.device_count() < 8:
+        pytest.skip(f"needs 8 GPUs (one rank process per GPU), found {torch.cuda.device_count()}")
     common = ["--config", "14b", "--layers", "2", "--steps", "1", "--warmup", "1", "--no-vae", "--no-cpu-baseline", "--no-extra-legs"]
     one = _run([sys.executable, "bench.py"] + common, timeout=900)
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
@@ -65,7 +86,6 @@ def test_bench_eight_process_ranks_full_width_two_layers():
     eight = _run(cmd + common, {"SCAIL_DIST_BACKEND": "gloo"}, base_env=env, timeout=1500)
     cfg = eight["config"]
     assert eight["n_gpus"] == 8 and cfg["finite"] and cfg["parallelism"] == "sp8-ulysses" and cfg["path"].startswith("scail_dit_step_sp")
-    import torch
     from conftest import attention_plan_rows
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     assert cfg["sp_check"]["ranks"] == 8 and cfg["attn_query_tile_rows"] == attention_plan_rows(cus, 5, 48832)      # 448 on the 256-CU part

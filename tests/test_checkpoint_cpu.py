@@ -1,12 +1,15 @@
 """Checkpoint ingest: the tensor-parallel merge of scail_amd/checkpoint.py.
   * partition -> merge is the identity on a DiT state dict and save_checkpoint(model_parallel_size=n) / load_checkpoint
     round-trips through the reference's directory layout (sat/training/model_io.py:36-48);
-  * (build container) the partition rule equals the REAL reference's ColumnParallelLinear.partition /
-    RowParallelLinear.partition (sat/mpu/layers.py:286-340, 438-460) for the strides the DiT uses."""
+  * the partition rule equals the REAL reference's ColumnParallelLinear.partition / RowParallelLinear.partition
+    (sat/mpu/layers.py:286-340, 438-460) for the strides the DiT uses (tests/golden/partition_rules.npz,
+    generator oracle/gen_golden_partition.py)."""
+import os
+
+import numpy as np
 import pytest
 import torch
 
-from oracle import ref_shims
 from oracle import scail_oracle as O
 
 
@@ -47,42 +50,32 @@ def test_partition_merge_roundtrip_and_files(tmp_path):
         C.merge_model_parallel_state_dicts(parts)
 
 
-@pytest.mark.skipif(not ref_shims.available(), reason="needs the reference tree (build container only)")
+def _partition_golden(golden_dir):
+    """the reference's own ColumnParallelLinear / RowParallelLinear.partition on seeded weights (oracle/gen_golden_partition.py)"""
+    return {k: torch.from_numpy(np.asarray(v)) for k, v in np.load(os.path.join(golden_dir, "partition_rules.npz")).items()}
+
+
 @pytest.mark.parametrize("stride,name", [(3, "transformer.layers.0.attention.query_key_value"),
                                          (2, "transformer.layers.0.cross_attention.key_value"),
                                          (2, "mixins.adaln_layer.clip_feature_key_value_list.0"),
                                          (1, "transformer.layers.0.mlp.dense_h_to_4h")])
-def test_column_partition_rule_equals_reference(stride, name):
+def test_column_partition_rule_equals_reference(stride, name, golden_dir):
     from scail_amd import checkpoint as C
-    ref_shims.load_reference()
-    from sat import mpu
-    if not mpu.model_parallel_is_initialized():
-        mpu.initialize_model_parallel(1)
-    from sat.mpu.layers import ColumnParallelLinear
-    g = torch.Generator().manual_seed(1)
-    out_f, in_f = 24 * stride, 16
-    lin = ColumnParallelLinear(in_f, out_f, stride=stride, gather_output=False, bias=True)
-    w = torch.randn(out_f, in_f, generator=g)
+    g = _partition_golden(golden_dir)
+    w = g[f"col_s{stride}_w"]
+    assert w.shape == (24 * stride, 16)
     for n in (2, 4):
-        want = lin.partition(new_model_parallel_size=n, full_weight=w)
         got = C.partition_state_dict({name + ".weight": w}, n)
         for r in range(n):
-            assert torch.equal(got[r][name + ".weight"], want[r])
+            assert torch.equal(got[r][name + ".weight"], g[f"col_s{stride}_n{n}_r{r}"])
 
 
-@pytest.mark.skipif(not ref_shims.available(), reason="needs the reference tree (build container only)")
-def test_row_partition_rule_equals_reference():
+def test_row_partition_rule_equals_reference(golden_dir):
     from scail_amd import checkpoint as C
-    ref_shims.load_reference()
-    from sat import mpu
-    if not mpu.model_parallel_is_initialized():
-        mpu.initialize_model_parallel(1)
-    from sat.mpu.layers import RowParallelLinear
-    lin = RowParallelLinear(32, 8, input_is_parallel=True, bias=True)
-    w = torch.randn(8, 32, generator=torch.Generator().manual_seed(2))
-    want = lin.partition(new_model_parallel_size=4, full_weight=w)
+    g = _partition_golden(golden_dir)
+    w = g["row_w"]
     got = C.partition_state_dict({"transformer.layers.3.attention.dense.weight": w,
                                   "transformer.layers.3.attention.dense.bias": torch.ones(8)}, 4)
     for r in range(4):
-        assert torch.equal(got[r]["transformer.layers.3.attention.dense.weight"], want[r])
+        assert torch.equal(got[r]["transformer.layers.3.attention.dense.weight"], g[f"row_n4_r{r}"])
         assert torch.equal(got[r]["transformer.layers.3.attention.dense.bias"], torch.ones(8))

@@ -1,7 +1,6 @@
 """GPU side of the SAT seam (scail_amd/sat_mixins.py): the hook functions fed, through the real HipBackend (C ABI), the
-same tensors SAT hands them inside the reference network -- the argument contract tests/test_sat_mixins_cpu.py pins against
-the real reference's add_mixin / collect_hooks_ machinery in the build container (SAT itself is absent on the GPU box, so
-the hooks are called directly with the kwargs of sat/model/transformer.py:712-719 + dit_video_crossattn_sc_xc.py:1560-1586)."""
+same tensors SAT hands them inside the reference network (SAT itself is not a dependency of the project, so the hooks are
+called directly with the kwargs of sat/model/transformer.py:712-719 + dit_video_crossattn_sc_xc.py:1560-1586)."""
 import os
 
 import numpy as np
