@@ -44,7 +44,7 @@ import struct
 from dataclasses import dataclass
 from typing import List
 
-from . import isa, sched
+from . import codeobj, isa, sched
 from .isa import A, S, V, I32, F32, Neg, VCC, EXEC, M0, Instr
 
 KERNARG_SIZE = 168
@@ -1221,82 +1221,16 @@ class Gen:
 
 HEAD = """// GENERATED by scail_amd/asmgen/attn4.py -- do not edit; regenerate with `python -m scail_amd.asmgen.attn4`.
 // Hand-scheduled 4-wave flash attention for gfx950; see the generator's docstring for the register map and the pipeline.
-\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"
-\t.amdhsa_code_object_version 6
 """
 
 
-def kernel_text(c: Cfg) -> str:
-    body = isa.render(Gen(c).program())
-    return f"""// ---- kernel {c.name}: ring depth {c.rd}, <= {c.cap} fillers per MFMA gap, lookahead {c.lookahead} ----
-\t.text
-\t.protected\t{c.name}
-\t.globl\t{c.name}
-\t.p2align\t8
-\t.type\t{c.name},@function
-{body}.L{c.name}_end:
-\t.size\t{c.name}, .L{c.name}_end-{c.name}
-\t.section\t.rodata,"a",@progbits
-\t.p2align\t6, 0x0
-\t.amdhsa_kernel {c.name}
-\t\t.amdhsa_group_segment_fixed_size {c.lds_bytes}
-\t\t.amdhsa_private_segment_fixed_size 0
-\t\t.amdhsa_kernarg_size {X2_KERNARG_SIZE if c.x2 else KERNARG_SIZE}
-\t\t.amdhsa_user_sgpr_count 2
-\t\t.amdhsa_user_sgpr_kernarg_segment_ptr 1
-\t\t.amdhsa_system_sgpr_workgroup_id_x 1
-\t\t.amdhsa_system_sgpr_workgroup_id_y 1
-\t\t.amdhsa_system_sgpr_workgroup_id_z 1
-\t\t.amdhsa_system_vgpr_workitem_id 0
-\t\t.amdhsa_next_free_vgpr 512
-\t\t.amdhsa_next_free_sgpr 96
-\t\t.amdhsa_accum_offset 256
-\t\t.amdhsa_reserve_vcc 1
-\t\t.amdhsa_float_round_mode_32 0
-\t\t.amdhsa_float_round_mode_16_64 0
-\t\t.amdhsa_float_denorm_mode_32 3
-\t\t.amdhsa_float_denorm_mode_16_64 3
-\t\t.amdhsa_dx10_clamp 1
-\t\t.amdhsa_ieee_mode 1
-\t.end_amdhsa_kernel
-"""
-
-
-def metadata(cfgs) -> str:
-    ks = "".join(f"""  - .agpr_count:     256
-    .args:
-      - .offset:         0
-        .size:           {X2_KERNARG_SIZE if c.x2 else KERNARG_SIZE}
-        .value_kind:     by_value
-    .group_segment_fixed_size: {c.lds_bytes}
-    .kernarg_segment_align: 8
-    .kernarg_segment_size: {X2_KERNARG_SIZE if c.x2 else KERNARG_SIZE}
-    .max_flat_workgroup_size: 256
-    .name:           {c.name}
-    .private_segment_fixed_size: 0
-    .sgpr_count:     102
-    .sgpr_spill_count: 0
-    .symbol:         {c.name}.kd
-    .uniform_work_group_size: 1
-    .uses_dynamic_stack: false
-    .vgpr_count:     512
-    .vgpr_spill_count: 0
-    .wavefront_size: 64
-""" for c in cfgs)
-    return f"""\t.amdgpu_metadata
----
-amdhsa.kernels:
-{ks}amdhsa.target:   amdgcn-amd-amdhsa--gfx950
-amdhsa.version:
-  - 1
-  - 2
-...
-\t.end_amdgpu_metadata
-"""
+def kernel(c: Cfg) -> codeobj.Kernel:
+    return codeobj.Kernel(c.name, f"ring depth {c.rd}, <= {c.cap} fillers per MFMA gap, lookahead {c.lookahead}", isa.render(Gen(c).program()),
+                          lds_bytes=c.lds_bytes, kernarg_size=X2_KERNARG_SIZE if c.x2 else KERNARG_SIZE)
 
 
 def assembly(cfgs) -> str:
-    return HEAD + "".join(kernel_text(c) for c in cfgs) + metadata(cfgs)
+    return codeobj.assembly(HEAD, map(kernel, cfgs))
 
 
 DEFAULT = Cfg(rd=4, cap=5, name="scail_attn4")
@@ -1424,23 +1358,5 @@ def variant_cfgs():
     return out
 
 
-def main():
-    import os
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    out = os.path.join(os.path.dirname(here), "csrc", "attn4.s")
-    if "--variants" in sys.argv:
-        dst = sys.argv[sys.argv.index("--variants") + 1]
-        open(dst, "w").write(assembly(SHIPPED + variant_cfgs()))
-        print(dst)
-        return
-    text = assembly(SHIPPED)
-    if "--check" in sys.argv:
-        sys.exit(0 if open(out).read() == text else 1)
-    if not os.path.exists(out) or open(out).read() != text:
-        open(out, "w").write(text)
-    print(out, len(text.splitlines()), "lines")
-
-
 if __name__ == "__main__":
-    main()
+    codeobj.main("attn4")

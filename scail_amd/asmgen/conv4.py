@@ -43,7 +43,7 @@ import struct
 from dataclasses import dataclass
 from typing import List
 
-from . import isa, sched
+from . import codeobj, isa, sched
 from .isa import A, S, V, I32, F32, VCC, EXEC, M0, Instr
 
 KERNARG_SIZE = 152
@@ -887,82 +887,16 @@ class Gen:
 
 HEAD = """// GENERATED by scail_amd/asmgen/conv4.py -- do not edit; regenerate with `python -m scail_amd.asmgen.conv4`.
 // Hand-scheduled 3x3x3 causal convolution for gfx950 (2 frames x 16 x 16 voxels x 96 channels per workgroup); see the generator.
-\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"
-\t.amdhsa_code_object_version 6
 """
 
 
-def kernel_text(c: Cfg) -> str:
-    body = isa.render(Gen(c).program())
-    return f"""// ---- kernel {c.name}: epilogue {c.epi} ----
-\t.text
-\t.protected\t{c.name}
-\t.globl\t{c.name}
-\t.p2align\t8
-\t.type\t{c.name},@function
-{body}.L{c.name}_end:
-\t.size\t{c.name}, .L{c.name}_end-{c.name}
-\t.section\t.rodata,"a",@progbits
-\t.p2align\t6, 0x0
-\t.amdhsa_kernel {c.name}
-\t\t.amdhsa_group_segment_fixed_size {LDS_BYTES}
-\t\t.amdhsa_private_segment_fixed_size 0
-\t\t.amdhsa_kernarg_size {KERNARG_SIZE}
-\t\t.amdhsa_user_sgpr_count 2
-\t\t.amdhsa_user_sgpr_kernarg_segment_ptr 1
-\t\t.amdhsa_system_sgpr_workgroup_id_x 1
-\t\t.amdhsa_system_sgpr_workgroup_id_y 1
-\t\t.amdhsa_system_sgpr_workgroup_id_z 1
-\t\t.amdhsa_system_vgpr_workitem_id 0
-\t\t.amdhsa_next_free_vgpr 512
-\t\t.amdhsa_next_free_sgpr {N_SGPR}
-\t\t.amdhsa_accum_offset 256
-\t\t.amdhsa_reserve_vcc 1
-\t\t.amdhsa_float_round_mode_32 0
-\t\t.amdhsa_float_round_mode_16_64 0
-\t\t.amdhsa_float_denorm_mode_32 3
-\t\t.amdhsa_float_denorm_mode_16_64 3
-\t\t.amdhsa_dx10_clamp 1
-\t\t.amdhsa_ieee_mode 1
-\t.end_amdhsa_kernel
-"""
-
-
-def metadata(cfgs) -> str:
-    ks = "".join(f"""  - .agpr_count:     256
-    .args:
-      - .offset:         0
-        .size:           {KERNARG_SIZE}
-        .value_kind:     by_value
-    .group_segment_fixed_size: {LDS_BYTES}
-    .kernarg_segment_align: 8
-    .kernarg_segment_size: {KERNARG_SIZE}
-    .max_flat_workgroup_size: 256
-    .name:           {c.name}
-    .private_segment_fixed_size: 0
-    .sgpr_count:     102
-    .sgpr_spill_count: 0
-    .symbol:         {c.name}.kd
-    .uniform_work_group_size: 1
-    .uses_dynamic_stack: false
-    .vgpr_count:     512
-    .vgpr_spill_count: 0
-    .wavefront_size: 64
-""" for c in cfgs)
-    return f"""\t.amdgpu_metadata
----
-amdhsa.kernels:
-{ks}amdhsa.target:   amdgcn-amd-amdhsa--gfx950
-amdhsa.version:
-  - 1
-  - 2
-...
-\t.end_amdgpu_metadata
-"""
+def kernel(c: Cfg) -> codeobj.Kernel:
+    return codeobj.Kernel(c.name, f"epilogue {c.epi}", isa.render(Gen(c).program()), lds_bytes=LDS_BYTES, kernarg_size=KERNARG_SIZE,
+                          sgprs=N_SGPR)
 
 
 def assembly(cfgs) -> str:
-    return HEAD + "".join(kernel_text(c) for c in cfgs) + metadata(cfgs)
+    return codeobj.assembly(HEAD, map(kernel, cfgs))
 
 
 DEFAULTS = [Cfg(epi=0, name="scail_conv4_e0"), Cfg(epi=3, name="scail_conv4_e3")]
@@ -994,18 +928,5 @@ def variant_cfgs():
     return out
 
 
-def main():
-    import os
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    out = os.path.join(os.path.dirname(here), "csrc", "conv4.s")
-    text = assembly(DEFAULTS)
-    if "--check" in sys.argv:
-        sys.exit(0 if os.path.exists(out) and open(out).read() == text else 1)
-    if not os.path.exists(out) or open(out).read() != text:
-        open(out, "w").write(text)
-    print(out, len(text.splitlines()), "lines")
-
-
 if __name__ == "__main__":
-    main()
+    codeobj.main("conv4")

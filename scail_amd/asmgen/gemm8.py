@@ -17,7 +17,7 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import List
 
-from . import isa, sched
+from . import codeobj, isa, sched
 from .gemm4 import KERNARG_SIZE, pack_args, tile_table  # noqa: F401  (same argument block and tile-order table)
 from .gemm4 import (S_KARG, S_WG, S_X, S_W, S_BIAS, S_Y, S_RES, S_GATE, S_TAB, S_LDA, S_LDC, S_LDR, S_GS, S_M, S_N, S_K, S_RPB,
                     S_XRSRC, S_WRSRC, S_KOFF, S_KMAX, S_T, S_KT, S_WAVE, S_WM, S_WN, S_M0T, S_N0T, ST, S_SAVE)
@@ -292,82 +292,16 @@ class Gen:
 
 HEAD = """// GENERATED by scail_amd/asmgen/gemm8.py -- do not edit; regenerate with `python -m scail_amd.asmgen.gemm8`.
 // Hand-scheduled 8-wave bf16 GEMM for gfx950 (256 x 256 x 64 tile, two waves per SIMD, 128 accumulators per lane in a[0:127]).
-\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"
-\t.amdhsa_code_object_version 6
 """
 
 
-def kernel_text(c: Cfg) -> str:
-    body = isa.render(Gen(c).program())
-    return f"""// ---- kernel {c.name}: epilogue {c.epi} ----
-\t.text
-\t.protected\t{c.name}
-\t.globl\t{c.name}
-\t.p2align\t8
-\t.type\t{c.name},@function
-{body}.L{c.name}_end:
-\t.size\t{c.name}, .L{c.name}_end-{c.name}
-\t.section\t.rodata,"a",@progbits
-\t.p2align\t6, 0x0
-\t.amdhsa_kernel {c.name}
-\t\t.amdhsa_group_segment_fixed_size 131072
-\t\t.amdhsa_private_segment_fixed_size 0
-\t\t.amdhsa_kernarg_size {KERNARG_SIZE}
-\t\t.amdhsa_user_sgpr_count 2
-\t\t.amdhsa_user_sgpr_kernarg_segment_ptr 1
-\t\t.amdhsa_system_sgpr_workgroup_id_x 1
-\t\t.amdhsa_system_sgpr_workgroup_id_y 1
-\t\t.amdhsa_system_sgpr_workgroup_id_z 1
-\t\t.amdhsa_system_vgpr_workitem_id 0
-\t\t.amdhsa_next_free_vgpr 256
-\t\t.amdhsa_next_free_sgpr 96
-\t\t.amdhsa_accum_offset 128
-\t\t.amdhsa_reserve_vcc 1
-\t\t.amdhsa_float_round_mode_32 0
-\t\t.amdhsa_float_round_mode_16_64 0
-\t\t.amdhsa_float_denorm_mode_32 3
-\t\t.amdhsa_float_denorm_mode_16_64 3
-\t\t.amdhsa_dx10_clamp 1
-\t\t.amdhsa_ieee_mode 1
-\t.end_amdhsa_kernel
-"""
-
-
-def metadata(cfgs) -> str:
-    ks = "".join(f"""  - .agpr_count:     128
-    .args:
-      - .offset:         0
-        .size:           {KERNARG_SIZE}
-        .value_kind:     by_value
-    .group_segment_fixed_size: 131072
-    .kernarg_segment_align: 8
-    .kernarg_segment_size: {KERNARG_SIZE}
-    .max_flat_workgroup_size: 512
-    .name:           {c.name}
-    .private_segment_fixed_size: 0
-    .sgpr_count:     102
-    .sgpr_spill_count: 0
-    .symbol:         {c.name}.kd
-    .uniform_work_group_size: 1
-    .uses_dynamic_stack: false
-    .vgpr_count:     256
-    .vgpr_spill_count: 0
-    .wavefront_size: 64
-""" for c in cfgs)
-    return f"""\t.amdgpu_metadata
----
-amdhsa.kernels:
-{ks}amdhsa.target:   amdgcn-amd-amdhsa--gfx950
-amdhsa.version:
-  - 1
-  - 2
-...
-\t.end_amdgpu_metadata
-"""
+def kernel(c: Cfg) -> codeobj.Kernel:
+    return codeobj.Kernel(c.name, f"epilogue {c.epi}", isa.render(Gen(c).program()), lds_bytes=131072, kernarg_size=KERNARG_SIZE,
+                          vgprs=256, agprs=128, wg_size=512)
 
 
 def assembly(cfgs) -> str:
-    return HEAD + "".join(kernel_text(c) for c in cfgs) + metadata(cfgs)
+    return codeobj.assembly(HEAD, map(kernel, cfgs))
 
 
 DEFAULTS = [Cfg(epi=e, name=f"scail_gemm8_e{e}") for e in (0, 1, 3, 4)]
@@ -382,19 +316,5 @@ def variant_cfgs():
     return out
 
 
-def main():
-    import os
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    out = os.path.join(os.path.dirname(os.path.dirname(here)), "build_abl", "gemm8.s")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    text = assembly(DEFAULTS)
-    if "--check" in sys.argv:
-        sys.exit(0 if open(out).read() == text else 1)
-    if not os.path.exists(out) or open(out).read() != text:
-        open(out, "w").write(text)
-    print(out, len(text.splitlines()), "lines")
-
-
 if __name__ == "__main__":
-    main()
+    codeobj.main("gemm8")

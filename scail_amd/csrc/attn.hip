@@ -22,8 +22,6 @@
 // the end.  LDS rows are padded (K: 272 B, V^T: 144 B) so every ds_read_b128 service group touches
 // 16 distinct 16-byte slots.
 #include <atomic>
-#include <map>
-#include <mutex>
 #include "common.h"
 
 #define HD 128
@@ -828,57 +826,19 @@ struct Attn4Args {
     uint32_t* restarts;          // optional device counter: + 1 per workgroup that restarts after an overflow of the optimistic pass (NULL: none)
 };
 static_assert(sizeof(Attn4Args) == 168, "Attn4Args must match asmgen/attn4.py KERNARG_SIZE");
-// Code objects, kernel handles (and the GEMM's tile-order tables, gemm.hip) belong to ONE device: they are cached per HIP device
-// id, so a process that drives several GPUs (a DiT on cuda:0 and another engine on cuda:1, a threaded multi-GPU host) launches the
-// module loaded on the device that is current at the call.
-static std::map<int, hipModule_t> g_attn4_modules;                // device -> loaded code object
 static const char* const k_attn4_default = "scail_attn4_m16f";   // the shipped kernel
 static std::string g_attn4_name = k_attn4_default;               // A/B variants of the measurement build replace it ("attn4_kernel:<suffix>")
-static std::map<std::pair<int, std::string>, hipFunction_t> g_attn4_fns;
-static std::mutex g_attn4_mutex;
 static std::atomic<float> g_attn4_thr_log2{8.0f};   // lazy-rescale threshold: P <= 2^thr
 static std::atomic<int> g_attn4_xcd{1};      // XCD-aware workgroup-id decode (A/B knob "attn4_xcd")
 
-static int attn4_function(const std::string& name, hipFunction_t* fn) {
-    std::lock_guard<std::mutex> lk(g_attn4_mutex);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        scail_set_error("attn4: hipGetDevice failed");
-        return 2;
-    }
-    auto mit = g_attn4_modules.find(dev);
-    if (mit == g_attn4_modules.end()) {
-        hipModule_t mod = nullptr;
-        hipError_t e = hipModuleLoadData(&mod, k_attn4_hsaco);
-        if (e != hipSuccess) {
-            scail_set_error(std::string("attn4: hipModuleLoadData failed: ") + hipGetErrorString(e));
-            return 2;
-        }
-        mit = g_attn4_modules.emplace(dev, mod).first;
-    }
-    auto it = g_attn4_fns.find(std::make_pair(dev, name));
-    if (it == g_attn4_fns.end()) {
-        hipFunction_t f;
-        hipError_t e = hipModuleGetFunction(&f, mit->second, name.c_str());
-        if (e != hipSuccess) {
-            scail_set_error("attn4: kernel " + name + " is not in the embedded code object: " + hipGetErrorString(e));
-            return 2;
-        }
-        it = g_attn4_fns.emplace(std::make_pair(dev, name), f).first;
-    }
-    *fn = it->second;
-    return 0;
-}
-
 // load the embedded code object and resolve the shipped kernel now (scail_dit_create calls this: a first launch inside
 // hipStreamBeginCapture must not have to load a module)
-static int attn4_cu_count();
 int scail_attn4_preload() {
     hipFunction_t fn;
     // every shipped kernel the launch plan / the cross-attention dispatch can pick, and the per-device CU count the plan reads
     for (const char* name : {"scail_attn4_m16f", "scail_attn4_m16f_q3", "scail_attn4_x2"})
-        if (int rc = attn4_function(name, &fn)) return rc;
-    return attn4_cu_count() > 0 ? 0 : 2;
+        if (int rc = scail_module_function("attn4", k_attn4_hsaco, name, &fn)) return rc;
+    return scail_device_cus() > 0 ? 0 : 2;
 }
 
 static std::atomic<int> g_attn4_mode{1};     // 1 = use attn4 where eligible (default), 0 = never (8-wave kernels only)
@@ -916,23 +876,6 @@ struct Attn4Launch {
     int rows;                   // 256 | 192
     int64_t item0, n_items;     // items [item0, item0 + n_items) of the pair-major (pair, query tile) list of THIS tile height
 };
-// CUs of the current device (cached per device); 0 + scail_last_error when the runtime cannot say -- the plan does not guess
-static int attn4_cu_count() {
-    static std::map<int, int> cus;
-    std::lock_guard<std::mutex> lk(g_attn4_mutex);
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        scail_set_error("attn4: hipGetDevice failed");
-        return 0;
-    }
-    auto it = cus.find(dev);
-    if (it != cus.end()) return it->second;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) {
-        scail_set_error("attn4: the device's compute-unit count is not available (hipDeviceAttributeMultiprocessorCount)");
-        return 0;
-    }
-    return cus[dev] = n;
-}
 // Returns the number of launches (1 or 2), or 0 + scail_last_error when the device's CU count is unavailable.
 // Constants of the plan (measured, profiles/r05_attn_sp_shape_probe.log): k_attn4_q3_cost = 0.79 (a 192-row tile against a 256-row one),
 // a 1.5 % minimum gain before anything but the single 256-row launch is chosen, 0.02 round-equivalents for the gap between two launches.
@@ -944,7 +887,7 @@ static int attn4_plan(int64_t n_batch, int64_t heads, int64_t Lq, Attn4Launch ou
     const int forced = opt ? opt : g_attn4_rows_hint;
     if (forced == 192) { out[0] = {192, 0, W3}; return 1; }
     if (forced == 256) { out[0] = {256, 0, W4}; return 1; }
-    int64_t cus = attn4_cu_count();
+    int64_t cus = scail_device_cus();       // the plan does not guess
     if (cus <= 0) return 0;
     const int avail = g_attn4_cus.load(std::memory_order_relaxed);
     if (avail > 0 && avail < cus) cus = avail;
@@ -1079,7 +1022,7 @@ extern "C" int scail_tune_set(const char* knob, int value) {
         if (name == "scail_attn4_general") name = "scail_attn4";      // the 32x32x16 kernel (round 2's raw-scale path)
         g_attn4_name = name;
         hipFunction_t fn;
-        return attn4_function(name, &fn);
+        return scail_module_function("attn4", k_attn4_hsaco, name, &fn);
     }
     if (std::string(knob).rfind("gemm4", 0) == 0) return scail_gemm4_knob(knob, value);     // "gemm4" on / off, "gemm4_kernel:<suffix>"
     if (std::string(knob) == "gemm_tile") return scail_gemm_tune(value);
@@ -1157,7 +1100,7 @@ extern "C" int scail_flash_attn_bf16(const scail_bf16* q, int64_t q_bs, int64_t 
         const int64_t pairs = heads * n_batch;
         for (int li = 0; li < n_launch; ++li) {
             const Attn4Launch& pl = plan[li];
-            if (int rc = attn4_function(pl.rows == 192 ? g_attn4_name + "_q3" : g_attn4_name, &fn)) return rc;
+            if (int rc = scail_module_function("attn4", k_attn4_hsaco, pl.rows == 192 ? g_attn4_name + "_q3" : g_attn4_name, &fn)) return rc;
             Attn4Args a;
             a.q = q; a.k = k; a.vt = vt; a.o = o;
             a.q_bs = q_bs; a.q_rs = q_rs; a.k_ss = k_ss; a.k_bs = k_bs; a.k_rs = k_rs; a.vt_ss = vt_ss; a.vt_bs = vt_bs;
@@ -1177,14 +1120,7 @@ extern "C" int scail_flash_attn_bf16(const scail_bf16* q, int64_t q_bs, int64_t 
             // pair in step; 5 pairs: 4 % faster than a run per XCD); whole launches of 8 k pairs -> pairs dealt round-robin (mode 1);
             // anything else -> 8 equal runs of the item list (mode 2)
             a.xcd_mode = (!g_attn4_xcd || pairs < 8) ? 0 : ((pairs % 8 == 0 && n_launch == 1) ? 1 : 2);
-            size_t sz = sizeof(a);
-            void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-            hipError_t e = hipModuleLaunchKernel(fn, (unsigned)(a.xcd_mode == 2 ? 8 * a.items_per_xcd : a.n_items), 1, 1, 256, 1, 1, 0,
-                                                 (hipStream_t)stream, nullptr, extra);
-            if (e != hipSuccess) {
-                scail_set_error(std::string("attn4: launch failed: ") + hipGetErrorString(e));
-                return 2;
-            }
+            if (int rc = scail_module_launch("attn4", fn, (unsigned)(a.xcd_mode == 2 ? 8 * a.items_per_xcd : a.n_items), 256, a, stream)) return rc;
         }
         return 0;
     }
@@ -1296,7 +1232,9 @@ extern "C" int scail_cross_attn2_bf16(const scail_bf16* q, int64_t q_bs, int64_t
         // scail_attn4_x2 (csrc/attn4.s, asmgen/attn4.py Cfg.x2): the 4-wave pipeline of the self-attention kernel, persistent workgroups (one
         // per CU) walking over the (pair, 256-row query block) items, the key pipeline run once per key set and item
         hipFunction_t fn;
-        if (int rc = attn4_function("scail_attn4_x2", &fn)) return rc;
+        if (int rc = scail_module_function("attn4", k_attn4_hsaco, "scail_attn4_x2", &fn)) return rc;
+        const int cus = scail_device_cus();
+        if (cus <= 0) return 2;
         Attn4X2Args a;
         Attn4Args& b = a.base;
         const int64_t Lkp1 = (Lk1 + 63) / 64 * 64, Lkp2 = (Lk2 + 63) / 64 * 64;
@@ -1314,16 +1252,9 @@ extern "C" int scail_cross_attn2_bf16(const scail_bf16* q, int64_t q_bs, int64_t
         b.item0 = 0;
         b.restarts = nullptr;            // the cross attention is not counted (scail_flash_attn_count_restarts is about the self-attention)
         a.k2 = k2; a.vt2 = vt2; a.k2_bs = k2_bs; a.vt2_bs = vt2_bs; a.Lk2 = (int32_t)Lk2; a.Lkp2 = (int32_t)Lkp2;
-        a.n_wgs = (int32_t)std::min<int64_t>(b.n_items, attn4_cu_count());
+        a.n_wgs = (int32_t)std::min<int64_t>(b.n_items, cus);
         a.pad = 0;
-        size_t sz = sizeof(a);
-        void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-        hipError_t e = hipModuleLaunchKernel(fn, (unsigned)a.n_wgs, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, extra);
-        if (e != hipSuccess) {
-            scail_set_error(std::string("cross_attn2 (attn4_x2): launch failed: ") + hipGetErrorString(e));
-            return 2;
-        }
-        return 0;
+        return scail_module_launch("cross_attn2 (attn4_x2)", fn, (unsigned)a.n_wgs, 256, a, stream);
     }
     static ScailDeviceOnce attr_set;
     if (attr_set.need()) {

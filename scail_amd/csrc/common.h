@@ -29,6 +29,25 @@ int scail_check_launch(const char* what);
         }                                                                          \
     } while (0)
 
+// ---- embedded code objects (codeobj.hip) ------------------------------------------------------
+// The generated kernels (scail_amd/asmgen) travel as code-object images embedded by build.py.  scail_module_function resolves kernel
+// `name` of `image` on the CURRENT device (module and function cached per device); 0, or 2 + scail_last_error "<family>: ...".
+int scail_module_function(const char* family, const void* image, const std::string& name, hipFunction_t* fn);
+// compute units of the current device (cached per device); 0 + scail_last_error when the runtime cannot say: callers do not guess
+int scail_device_cus();
+// hipModuleLaunchKernel of a 1-D grid with the kernel argument block `args`; a launch failure -> 2 + "<what>: launch failed: ..."
+template <class Args>
+int scail_module_launch(const char* what, hipFunction_t fn, unsigned grid, unsigned block, Args& args, void* stream) {
+    size_t sz = sizeof(args);
+    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+    hipError_t e = hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, (hipStream_t)stream, nullptr, extra);
+    if (e != hipSuccess) {
+        scail_set_error(std::string(what) + ": launch failed: " + hipGetErrorString(e));
+        return 2;
+    }
+    return 0;
+}
+
 // One-time per-DEVICE setup at a call site (hipFuncSetAttribute opt-ins of dynamic LDS are per device: a process that drives several
 // GPUs must repeat them on each): `static ScailDeviceOnce once_;  if (once_.need()) { ...setup...; once_.done(); }`.  Lock-free; two
 // threads racing on the same device both run the (idempotent) setup.

@@ -13,8 +13,6 @@
 #include "common.h"
 #include <atomic>
 #include <algorithm>
-#include <map>
-#include <mutex>
 
 #define CBM 128
 #define CBK 64
@@ -1021,59 +1019,7 @@ struct Conv4Args {
     int64_t y2_delta;                // (scail_conv4c_e5) bytes from y (the raw sum) to the normalised copy: same row stride and frame mapping
 };
 static_assert(sizeof(Conv4Args) == 152, "Conv4Args must match asmgen/conv4.py KERNARG_SIZE");
-static std::map<std::pair<int, int>, hipModule_t> g_conv4_modules;          // (device, code object: 0 conv4.s, 1 conv4u.s) -> loaded module
-static std::map<std::pair<int, std::string>, hipFunction_t> g_conv4_fn;     // (device, kernel name)
-static std::mutex g_conv4_mutex;
 static std::string g_conv4_suffix;                                          // measurement build: "conv4_kernel:<suffix>"
-
-static int conv4_function(const std::string& name, hipFunction_t* fn) {
-    std::lock_guard<std::mutex> lk(g_conv4_mutex);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        scail_set_error("conv4: hipGetDevice failed");
-        return 2;
-    }
-    const int which = (name.rfind("scail_conv4u", 0) == 0 || name.rfind("scail_conv4n", 0) == 0 || name.rfind("scail_conv4f", 0) == 0 ||
-                       name.rfind("scail_conv4c", 0) == 0) ? 1 : 0;
-    auto mit = g_conv4_modules.find(std::make_pair(dev, which));
-    if (mit == g_conv4_modules.end()) {
-        hipModule_t mod = nullptr;
-        hipError_t e = hipModuleLoadData(&mod, which ? k_conv4u_hsaco : k_conv4_hsaco);
-        if (e != hipSuccess) {
-            scail_set_error(std::string("conv4: hipModuleLoadData failed: ") + hipGetErrorString(e));
-            return 2;
-        }
-        mit = g_conv4_modules.emplace(std::make_pair(dev, which), mod).first;
-    }
-    auto it = g_conv4_fn.find(std::make_pair(dev, name));
-    if (it == g_conv4_fn.end()) {
-        hipFunction_t f;
-        hipError_t e = hipModuleGetFunction(&f, mit->second, name.c_str());
-        if (e != hipSuccess) {
-            scail_set_error("conv4: kernel " + name + " is not in the embedded code object: " + hipGetErrorString(e));
-            return 2;
-        }
-        it = g_conv4_fn.emplace(std::make_pair(dev, name), f).first;
-    }
-    *fn = it->second;
-    return 0;
-}
-
-// compute units of the current device, cached per HIP device id (like gemm4_cu_count)
-static int conv4_cu_count() {
-    static std::map<int, int> cache;
-    static std::mutex mu;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = cache.find(dev);
-    if (it == cache.end()) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
-        it = cache.emplace(dev, n).first;
-    }
-    return it->second;
-}
 
 static std::atomic<int> g_conv4_cont{1};                                   // option "conv4_cont": the tile-continuation variants (scail_conv4c_e0 / e3 / e4) for the one-n-tile shapes
 int scail_conv4_cont_enable(int v) { g_conv4_cont = v != 0; return 0; }
@@ -1216,7 +1162,8 @@ static int conv3d_impl(const scail_bf16* x, const scail_bf16* w, const float* bi
         // wgs_per_xcd + b / 8.  One n tile: w takes the next tiles_per_wg (+ 1) tiles (the frame pairs of a spatial tile; consecutive pairs
         // share two input frames, the lane offsets stay).  Several n tiles (tiles_per_wg = 0): w takes tiles w, w + grid, ... so that an XCD
         // works on the n tiles of a few neighbouring frame pairs at a time and they share the patch through its L2.
-        const int cus = conv4_cu_count();
+        const int cus = scail_device_cus();
+        if (cus <= 0) return 2;
         a.wgs_per_xcd = (int32_t)std::min<int64_t>((tiles + 7) / 8, cus / 8);
         a.tiles_per_wg = a.tiles_n == 1 ? (int32_t)(tiles / (8 * a.wgs_per_xcd)) : 0;
         a.tiles = (int32_t)tiles;
@@ -1226,19 +1173,14 @@ static int conv3d_impl(const scail_bf16* x, const scail_bf16* w, const float* bi
         // (measurement build: the "_prof" variant is an e0 kernel that writes its phase timers through the residual pointer)
         const bool prof = g_conv4_suffix.find("prof") != std::string::npos;
         const bool cont = g_conv4_cont && !k1 && !nar && a.tiles_n == 1 && g_conv4_suffix.empty();      // one n tile: runs of frame pairs per workgroup (a measurement-build kernel variant takes precedence)
-        if (int rc = rn ? conv4_function(k1 ? "scail_conv4u_e7" : y != y_norm ? "scail_conv4c_e5" : "scail_conv4c_e6", &fn)
-                        : k1 ? conv4_function("scail_conv4u_e0", &fn) : nar ? conv4_function(g_conv4_cont && g_conv4_suffix.empty() ? "scail_conv4cn_e0" : "scail_conv4n_e0", &fn)
-                        : fnorm ? conv4_function(cont ? "scail_conv4c_e4" : "scail_conv4f_e4", &fn)
-                        : cont ? conv4_function(resid ? "scail_conv4c_e3" : "scail_conv4c_e0", &fn)
-                        : conv4_function(std::string(resid && !prof ? "scail_conv4_e3" : "scail_conv4_e0") + g_conv4_suffix, &fn)) return rc;
-        size_t sz = sizeof(a);
-        void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-        hipError_t e = hipModuleLaunchKernel(fn, (unsigned)a.wgs_per_xcd * 8u, 1, 1, 256, 1, 1, 0, (hipStream_t)stream, nullptr, extra);
-        if (e != hipSuccess) {
-            scail_set_error(std::string("conv4: launch failed: ") + hipGetErrorString(e));
-            return 2;
-        }
-        return 0;
+        const std::string name = rn ? (k1 ? "scail_conv4u_e7" : y != y_norm ? "scail_conv4c_e5" : "scail_conv4c_e6")
+                                 : k1 ? "scail_conv4u_e0" : nar ? (g_conv4_cont && g_conv4_suffix.empty() ? "scail_conv4cn_e0" : "scail_conv4n_e0")
+                                 : fnorm ? (cont ? "scail_conv4c_e4" : "scail_conv4f_e4")
+                                 : cont ? (resid ? "scail_conv4c_e3" : "scail_conv4c_e0")
+                                 : std::string(resid && !prof ? "scail_conv4_e3" : "scail_conv4_e0") + g_conv4_suffix;
+        // conv4.s holds scail_conv4_e0 / e3 and their measurement-build variants, conv4u.s every other generated convolution
+        if (int rc = scail_module_function("conv4", name.rfind("scail_conv4_", 0) == 0 ? k_conv4_hsaco : k_conv4u_hsaco, name, &fn)) return rc;
+        return scail_module_launch("conv4", fn, (unsigned)a.wgs_per_xcd * 8u, 256, a, stream);
     }
     if (!rn && (g_conv_halo || fuse) && p.kt == 3 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && !p.ups &&
         p.ph == 1 && p.pw == 1 && p.Ho == p.Hi && p.Wo == p.Wi &&
@@ -1337,7 +1279,9 @@ static int conv3d_impl(const scail_bf16* x, const scail_bf16* w, const float* bi
         const int lds = (nn * wld + 8 * 32 * CD_STRIP_LD) * 2 + 2 * nn * 4;        // W, the waves' strips, bias + gamma
         if (g_conv_direct && !p.ups && resid == nullptr && p.Cin % 8 == 0 && nn % 32 == 0 && shape && lds <= 150 * 1024 && ldc % 8 == 0 &&
             (reinterpret_cast<uintptr_t>(y) & 15) == 0 && p.M >= 4096 && p.M < (1ll << 40) && p.Ho * (int64_t)p.Wo < (1ll << 31) && p.Ho * (int64_t)p.Wo >= 32) {
-            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((p.M + 255) / 256, conv4_cu_count()));
+            const int cus = scail_device_cus();
+            if (cus <= 0) return 2;
+            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((p.M + 255) / 256, cus));
             if (rn) {       // raw output + the consumer's normalised input (scail_conv3d_cl_resid_norm checked conv_direct_dual_eligible)
                 SCAIL_REQUIRE(nb == 3 && nsplit == 1 && ksteps <= 14 && y != y_norm, "conv3d: dual-output direct kernel needs 96 channels, <= 14 k-steps");
                 ConvParams q = p;
@@ -1461,7 +1405,9 @@ extern "C" int scail_rms_silu(const scail_bf16* x, scail_bf16* y, const float* g
     constexpr int VPT = 2;
     const int64_t threads = ((nvox + VPT - 1) / VPT) << lg;
     // persistent blocks: 8 per CU (40 registers per lane), each walking over its share of the voxel groups
-    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((threads + 255) / 256, (int64_t)conv4_cu_count() * 8)));
+    const int cus = scail_device_cus();
+    if (cus <= 0) return 2;
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((threads + 255) / 256, (int64_t)cus * 8)));
     if (three)
         hipLaunchKernelGGL((rms_silu_kernel<3, VPT>), grid, dim3(256), 0, (hipStream_t)stream, x, y, gamma, nvox, (int)C, lg, silu);
     else

@@ -589,51 +589,12 @@ struct Gemm4Args {
     int32_t grid, entries;      // persistent kernels: workgroups launched (a multiple of 8) and entries of the order table
 };
 static_assert(sizeof(Gemm4Args) == 112, "Gemm4Args must match asmgen/gemm4.py KERNARG_SIZE");
-// per-device caches (a code object / a hipMalloc'd table belongs to the device that was current when it was created)
-static std::map<std::pair<int, int>, hipModule_t> g_gemm4_modules;          // (device, 4 | 8) -> loaded code object
-static std::map<std::pair<int, std::string>, hipFunction_t> g_gemm4_fn;     // (device, kernel name)
+// per-device cache (a hipMalloc'd table belongs to the device that was current when it was created)
 static std::map<std::tuple<int, int, int, int, int>, std::pair<uint32_t*, int>> g_gemm4_tables;   // (device, m tiles, n tiles, group height, table mode) -> device order table, entries
 static std::mutex g_gemm4_mutex;
 static std::atomic<int> g_gemm4_mode{4};               // generated kernels where eligible: 4 = gemm4 (default), 0 = never (csrc/gemm.hip only), 8 = gemm8 (measurement build)
 static std::string g_gemm4_suffix;         // A/B variants of the measurement build ("gemm4_kernel:<suffix>")
 static int g_gemm4_table_mode = 1;         // tile -> XCD assignment of the order table (0, 2: measurement build A/B, knob "gemm4_table")
-
-static int gemm4_function(const std::string& name, hipFunction_t* fn) {
-    std::lock_guard<std::mutex> lk(g_gemm4_mutex);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        scail_set_error("gemm4: hipGetDevice failed");
-        return 2;
-    }
-    const bool is8 = name.rfind("scail_gemm8", 0) == 0;
-    auto mit = g_gemm4_modules.find(std::make_pair(dev, is8 ? 8 : 4));
-    if (mit == g_gemm4_modules.end()) {
-#ifdef SCAIL_ABLATIONS
-        const void* image = is8 ? (const void*)k_gemm8_hsaco : (const void*)k_gemm4_hsaco;
-#else
-        const void* image = k_gemm4_hsaco;
-#endif
-        hipModule_t mod = nullptr;
-        hipError_t e = hipModuleLoadData(&mod, image);
-        if (e != hipSuccess) {
-            scail_set_error(std::string("gemm4: hipModuleLoadData failed: ") + hipGetErrorString(e));
-            return 2;
-        }
-        mit = g_gemm4_modules.emplace(std::make_pair(dev, is8 ? 8 : 4), mod).first;
-    }
-    auto it = g_gemm4_fn.find(std::make_pair(dev, name));
-    if (it == g_gemm4_fn.end()) {
-        hipFunction_t f;
-        hipError_t e = hipModuleGetFunction(&f, mit->second, name.c_str());
-        if (e != hipSuccess) {
-            scail_set_error("gemm4: kernel " + name + " is not in the embedded code object: " + hipGetErrorString(e));
-            return 2;
-        }
-        it = g_gemm4_fn.emplace(std::make_pair(dev, name), f).first;
-    }
-    *fn = it->second;
-    return 0;
-}
 
 // Tile order table: workgroup id b runs on XCD b % 8 and takes entry b >> 3 of that XCD's sequence; a sequence is made of whole tile
 // groups (group_m m-tiles x one n-tile at a time), so the 32 tiles in flight on an XCD share ~4 + 8 operand panels in its L2.
@@ -703,20 +664,6 @@ static int gemm4_table(int tm, int tn, int group_m, uint32_t** dev_table, int* e
     return 0;
 }
 
-static int gemm4_cu_count() {
-    static std::map<int, int> cache;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(g_gemm4_mutex);
-    auto it = cache.find(dev);
-    if (it == cache.end()) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        it = cache.emplace(dev, n).first;
-    }
-    return it->second;
-}
-
 // Frees the tile-order tables of EVERY device (scail_release_caches, include/scail_hip.h): call with no launch in flight.  A table's
 // device pointer is a kernel argument of every gemm4 launch, so it is baked into any hipGraph captured from such launches: graphs
 // captured before this call must be destroyed or re-captured, never replayed.
@@ -753,7 +700,7 @@ extern "C" int scail_gemm_kernel_for(int64_t lda, int64_t ldc, int64_t ldr, int6
 int scail_gemm4_preload() {
     hipFunction_t fn;
     for (int e : {0, 1, 3, 4})
-        if (int rc = gemm4_function("scail_gemm4_e" + std::to_string(e), &fn)) return rc;
+        if (int rc = scail_module_function("gemm4", k_gemm4_hsaco, "scail_gemm4_e" + std::to_string(e), &fn)) return rc;
     return 0;
 }
 
@@ -797,8 +744,13 @@ extern "C" int scail_gemm_bf16(const scail_bf16* x, int64_t lda, const scail_bf1
         const bool is8 = g_gemm4_mode == 8;
         std::string name = std::string(is8 ? "scail_gemm8_e" : "scail_gemm4_e") + std::to_string(epi4);
         if (epi4 == 0 || g_gemm4_suffix == "_pst" || g_gemm4_suffix == "_part" || g_gemm4_suffix == "_stgnt") name += g_gemm4_suffix;      // A/B variants: bias epilogue only, except the persistent set (ablation build)
+#ifdef SCAIL_ABLATIONS
+        const void* image = is8 ? k_gemm8_hsaco : k_gemm4_hsaco;
+#else
+        const void* image = k_gemm4_hsaco;
+#endif
         hipFunction_t fn;
-        if (int rc = gemm4_function(name, &fn)) return rc;
+        if (int rc = scail_module_function("gemm4", image, name, &fn)) return rc;
         uint32_t* table;
         int entries;
         if (int rc = gemm4_table((int)((M + 255) / 256), (int)(N / 256), g_group_m, &table, &entries)) return rc;
@@ -811,19 +763,13 @@ extern "C" int scail_gemm_bf16(const scail_bf16* x, int64_t lda, const scail_bf1
         unsigned grid = (unsigned)entries;
         const bool persistent = name.size() > 4 && name.compare(name.size() - 4, 4, "_pst") == 0;
         if (persistent) {
-            int cus = gemm4_cu_count();
+            int cus = scail_device_cus();
+            if (cus <= 0) return 2;
             if (cus < 8) cus = 8;
             grid = std::min<unsigned>((unsigned)entries, (unsigned)(cus / 8 * 8));
         }
         a.grid = (int32_t)grid; a.entries = (int32_t)entries;
-        size_t sz = sizeof(a);
-        void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-        hipError_t e = hipModuleLaunchKernel(fn, grid, 1, 1, is8 ? 512 : 256, 1, 1, 0, (hipStream_t)stream, nullptr, extra);
-        if (e != hipSuccess) {
-            scail_set_error(std::string("gemm4: launch failed: ") + hipGetErrorString(e));
-            return 2;
-        }
-        return 0;
+        return scail_module_launch("gemm4", fn, grid, is8 ? 512 : 256, a, stream);
     }
     GemmParams p;
     p.x = x; p.lda = lda; p.w = w; p.bias = bias; p.y = y; p.ldc = ldc;

@@ -495,16 +495,6 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 // 0 = the block-per-row kernels for every D (same-process A/B; the results agree up to the order of the fp32 sums)
 static std::atomic<int> g_row_wave{1};   // option state: atomic (set by one thread, read by every launching thread)
 int scail_row_wave_enable(int on) { g_row_wave = on != 0; return 0; }
-static int row_cu_count() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cus[dev] == 0) {
-        int n = 0;
-        cus[dev] = (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return cus[dev];
-}
 
 // returns -1 when the wave kernels do not cover this D (the caller launches the block kernel), else the launch status
 template <int MODE>
@@ -528,7 +518,9 @@ static int ln_wave_launch(const scail_bf16* x, int64_t ldx, scail_bf16* y, int64
     }
     // persistent workgroups: about three per compute unit (157 VGPRs, 40 KB of LDS), dealt evenly to the batch elements
     const int64_t n_batch = rows / rows_out;
-    const int64_t wpb = std::max<int64_t>(1, std::min<int64_t>((rows_out + 3) / 4, (3 * row_cu_count() + n_batch - 1) / n_batch));
+    const int cus = scail_device_cus();
+    if (cus <= 0) return 2;
+    const int64_t wpb = std::max<int64_t>(1, std::min<int64_t>((rows_out + 3) / 4, (3 * cus + n_batch - 1) / n_batch));
     switch (D / 512) {
         LN_WAVE(3) LN_WAVE(4) LN_WAVE(8) LN_WAVE(10) LN_WAVE(12)
         default: return -1;
@@ -589,7 +581,9 @@ static int rmsnorm_rope_launch(const scail_bf16* x, int64_t ldx, scail_bf16* y, 
     // with RoPE the wave form wins (0.455 -> 0.41 ms at config 2: the (cos, sin) pairs once per row instead of per chunk); without, the block
     // kernel is already at the pass's plateau (0.367 against 0.383 ms; profiles/r04_row_pass_probe.log)
     if (g_row_wave && w != nullptr && cos_tab != nullptr && D % 512 == 0) {
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 3 * (int64_t)row_cu_count()));
+        const int cus = scail_device_cus();
+        if (cus <= 0) return 2;
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 3 * (int64_t)cus));
 #define RR_WAVE(CPL_)                                                                                                                \
     case CPL_: {                                                                                                                     \
         constexpr int lds_ = 512 * CPL_ * 4;                                                                                         \
