@@ -5,8 +5,8 @@ One "step" = one full sampler step of the reference (sampling.py:960-963): a bat
 DiT forward over the L = 48 832 token sequence [ref | noise | pose] + CFG combine + Euler update on
 the fp32 state.  value = 37 632 noise tokens / t_step, whole job.
 
-  python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, or -- when WORLD_SIZE is not
-                                                        set -- this script re-executes itself under it with N local ranks)
+  python bench.py --gpus N --steps K --warmup W [--full]   (N > 1: launched by torch.distributed.run, or -- when WORLD_SIZE is not
+                                                           set -- this script re-executes itself under it with N local ranks)
 
 Inputs are synthetic and already resident in HBM when the timed region starts; weights
 are random-init bf16 of the 14B architecture (no checkpoint offline).  Nothing is skipped inside the
@@ -20,13 +20,20 @@ The JSON line also carries
   roofline     MFMA roofline of the dominant kernel (self-attention flash kernel): algorithmic
                4*Lq*Lk*128*heads*B FLOP per launch / mean launch time measured with HIP events on the
                launch stream inside the timed region; peak 2.5 PFLOP/s dense bf16 (MI355X_MICROARCH.md);
-  roofline_gemm  the same for the six per-token GEMMs of a block taken together (36 % of the step's FLOPs);
+               traffic from the committed profiles/traffic.json while it matches the kernel source;
+  roofline_gemm  the same for the six per-token GEMMs of a block taken together (36 % of the step's FLOPs).
+
+A plain run stops there: it sets up, warms up, times the steps, writes --dump-outputs and prints the line.  --full also runs what
+takes runs of its own after the timed region (rank 0, N = 1 only; each part can be left out with the option in brackets):
+  config.sp_compute_side, config.multichar  rank 0's launches of a 2 / 4 / 8-rank step on this GPU, and BASELINE config 5
+               (--no-extra-legs);
+  roofline.traffic_in_run  rocprofv3 --pmc passes around child processes that launch the attention and GEMM shapes; they replace
+               the stamped traffic figures when they succeed (--no-pmc);
+  config.vae   BASELINE config 4 (Wan2.1 VAE encode + decode at 81 x 512 x 896) run once, with both roofline fractions (--no-vae);
   cpu_baseline the CPU oracle (fp32 port of the reference block) timed on this box's host cores after a warm-up: the per-token
                part at three sequence lengths, the self-attention (the L^2 term) separately on 4 of the 80 (batch, head)
                pairs up to L = 36 624 (0.75 x the bench length); fitted (with a standard error) and
-               evaluated at the bench length (rank 0, N = 1; "kind": "port, extrapolated");
-  config.vae   BASELINE config 4 (Wan2.1 VAE encode + decode at 81 x 512 x 896) run once after the timed region,
-               with both roofline fractions (rank 0, N = 1 only).
+               evaluated at the bench length ("kind": "port, extrapolated"; --no-cpu-baseline).
 
 --dump-outputs DIR writes what the last timed step computed (the network output for the CFG batch, the updated latent) as
 DIR/<name>.npy in float32 (64 MB at most; a larger array is written as a fixed seeded sample); inputs and weights are seeded, so
@@ -493,12 +500,15 @@ def main():
     ap.add_argument("--layers", type=int, default=None, help="DEBUG ONLY: fewer layers (result flagged invalid)")
     ap.add_argument("--latent-hw", type=int, nargs=2, default=None, metavar=("H", "W"),
                     help="OTHER RESOLUTION (result flagged invalid for the headline metric): latent height / width, e.g. 60 104 = 480x832")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-vae", action="store_true", help="skip the config-4 VAE leg after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run config.sp_compute_side, config.multichar, the in-run PMC traffic passes, config.vae and "
+                         "cpu_baseline (a plain run prints the headline line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-vae", action="store_true", help="with --full: skip the config-4 VAE leg after the timed region")
     ap.add_argument("--cfg-scale", type=float, default=4.0)
     ap.add_argument("--no-cfg-pair", action="store_true", help="A/B: evaluate both CFG elements in layer 0 (no SCAIL_DIT_CFG_PAIR)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip config.sp_compute_side and config.multichar after the timed region")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 --pmc passes behind roofline.traffic (the stamped profiles/traffic.json value is reported then)")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip config.sp_compute_side and config.multichar after the timed region")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the in-run rocprofv3 --pmc passes behind roofline.traffic (the stamped profiles/traffic.json value is reported then)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed (network output, updated latent) as DIR/<name>.npy (float32)")
     args = ap.parse_args()
@@ -771,10 +781,12 @@ def main():
                 pass
             return {"error": f"{type(e).__name__}: {e}"[:500]}
 
-    if rank == 0 and world == 1 and use_c and args.config == "14b" and args.latent_hw is None and not args.no_extra_legs:
+    # --full: what takes runs of its own, after the timed region, on rank 0 of a one-rank run
+    full = args.full and rank == 0 and world == 1
+    if full and use_c and args.config == "14b" and args.latent_hw is None and not args.no_extra_legs:
         out["config"]["sp_compute_side"] = leg(sp_compute_side_leg, net, p, (T, H, W), ctx, clip, dev, t_step, args)
         out["config"]["multichar"] = leg(multichar_leg, net, p, (T, H, W), ctx, clip, dev, Lt, Lc, args)
-    if rank == 0 and world == 1 and use_c and args.config == "14b" and args.latent_hw is None and args.layers is None and n_char == 1 and not args.no_pmc:
+    if full and use_c and args.config == "14b" and args.latent_hw is None and args.layers is None and n_char == 1 and not args.no_pmc:
         # fabric traffic of the two big kernels from PMC counters collected in THIS run (the stamped file stays the fallback and the cross-check)
         pm = leg(pmc_traffic_leg, traffic, out.get("roofline_gemm", {}).get("traffic"))
         out["roofline"]["traffic_in_run"] = pm
@@ -790,9 +802,9 @@ def main():
                 out["roofline_gemm"]["traffic_source"] = "PMC counters of this run (roofline.traffic_in_run.gemm)"
             else:
                 out["roofline_gemm"]["traffic_source"] = stamped
-    if rank == 0 and world == 1 and not args.no_vae:
+    if full and not args.no_vae:
         out["config"]["vae"] = leg(vae_leg, dev, (not args.no_pmc) and args.config == "14b" and args.layers is None)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         cb = cpu_baseline(p, L)
         t_cpu = p["num_layers"] * cb["t_block"]
         out["cpu_baseline"] = {

@@ -23,8 +23,9 @@ def _run(cmd, env_extra=None, timeout=600, base_env=None):
     return json.loads(lines[0])
 
 
-def test_bench_single_tiny():
-    o = _run([sys.executable, "bench.py", "--config", "tiny", "--steps", "2", "--warmup", "1"])
+def test_bench_full_tiny():
+    """--full: the headline line plus what takes runs of its own after the timed region (here cpu_baseline)."""
+    o = _run([sys.executable, "bench.py", "--config", "tiny", "--steps", "2", "--warmup", "1", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in o, k
@@ -33,6 +34,17 @@ def test_bench_single_tiny():
     assert o["config"]["path"].startswith("scail_dit_step") and o["roofline"]["timed_by"].startswith("scail_dit_profile")
     assert o["roofline"]["launches_timed"] == 2 * 2                      # 2 layers x 2 timed steps, from the executor's own event pairs
     assert o["cpu_baseline"]["kind"] == "port, extrapolated" and o["cpu_baseline"]["cores"] >= 1 and o["cpu_baseline"]["threads"] >= 1
+
+
+def test_bench_plain_run_prints_the_headline_only():
+    """Without --full the run ends after the timed steps: the headline line and the timed region's own kernel times, nothing that takes
+    runs of its own after it."""
+    o = _run([sys.executable, "bench.py", "--config", "tiny", "--steps", "2", "--warmup", "1"])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "roofline"):
+        assert k in o, k
+    assert o["config"]["finite"] and o["value"] > 0 and o["roofline"]["launches_timed"] == 2 * 2
+    assert "cpu_baseline" not in o and "traffic_in_run" not in o["roofline"]
+    assert not {"vae", "sp_compute_side", "multichar"} & set(o["config"])
 
 
 def test_bench_dump_outputs_tiny(tmp_path):

@@ -7,7 +7,7 @@
 #   tests            pytest -m gpu (product build)                      tests-x        same, stop at the first failure
 #   variants         pytest -m "gpu and variant" on the measurement build (SCAIL_ABLATIONS=1)
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (driver style, default K / W)      bench-quick    --steps 3 --warmup 1 --no-cpu-baseline
+#   bench            python bench.py --full (default K / W)             bench-quick    --full --steps 3 --warmup 1 --no-cpu-baseline
 #   bench-prof       rocprofv3 --kernel-trace --stats of bench-quick -> bench_kernel_stats.md
 #   bench-2char      config 5 extension line                            bench-480      480x832x81f line
 #   vae-prof         kernel stats of the VAE leg (tools/vae_leg_probe.py)
@@ -45,8 +45,8 @@ for LEG in "$@"; do
     tests-x)     timeout 1800 python -m pytest tests -m gpu -x -q --durations=8 > "$O/gpu_tests.log" 2>&1; tail -30 "$O/gpu_tests.log" ;;
     variants)    SCAIL_ABLATIONS=1 timeout 900 python -m pytest tests -m "gpu and variant" -q > "$O/gpu_tests_variants.log" 2>&1; tail -3 "$O/gpu_tests_variants.log" ;;
     smoke)       timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > "$O/smoke.log" 2>&1; tail -2 "$O/smoke.log" ;;
-    bench)       timeout 1200 python bench.py > "$O/bench.log" 2>&1; tail -c 7000 "$O/bench.log" | cut -c1-5000 ;;
-    bench-quick) timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline > "$O/bench_quick.log" 2>&1; tail -c 5000 "$O/bench_quick.log" | cut -c1-4000 ;;
+    bench)       timeout 1200 python bench.py --full > "$O/bench.log" 2>&1; tail -c 7000 "$O/bench.log" | cut -c1-5000 ;;
+    bench-quick) timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > "$O/bench_quick.log" 2>&1; tail -c 5000 "$O/bench_quick.log" | cut -c1-4000 ;;
     bench-prof)  kstats bench python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-vae --no-extra-legs --no-pmc ;;     # (the legs after the timed region launch the same kernels at other shapes)
     bench-2char) timeout 600 python bench.py --config 14b-2char --steps 2 --warmup 1 --no-vae --no-cpu-baseline > "$O/bench_2char.log" 2>&1; grep -o '"ms_per_step": [0-9.]*\|"achieved": [0-9.]*' "$O/bench_2char.log" ;;
     bench-480)   timeout 600 python bench.py --latent-hw 60 104 --steps 2 --warmup 1 --no-vae --no-cpu-baseline > "$O/bench_480x832.log" 2>&1; grep -o '"ms_per_step": [0-9.]*\|"achieved": [0-9.]*' "$O/bench_480x832.log" ;;
