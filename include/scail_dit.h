@@ -198,6 +198,28 @@ int scail_dit_profile(scail_dit* h, int enable);
 int scail_dit_profile_read(scail_dit* h, int category, double* ms_total, int64_t* launches);
 
 /*
+ * fp8 per-token GEMMs (opt-in; the default is bf16).  The selected GEMMs of every block run as scail_quant_fp8_rows on their input rows +
+ * scail_gemm_fp8 (include/scail_hip.h: OCP e4m3, one fp32 scale per token and per output channel, so every output row still depends on its
+ * own input row alone and SCAIL_DIT_CFG_PAIR / the last-layer row pruning stay exact) under scail_dit_step, scail_dit_block and
+ * scail_dit_sample.  The patch embedding, the final layer, the time / AdaLN / conditioning projections and both attentions stay bf16.
+ * scail_dit_enable_fp8 quantizes the selected per-layer matrices from the handle's bf16 weights into the caller's device buffer
+ * buf (>= scail_dit_fp8_weight_bytes(h, which) bytes, 256-byte aligned; it must outlive the fp8 use), enqueued on `stream`; call it
+ * outside stream capture.  A selected shape outside scail_gemm_fp8's limits (N, K multiples of 128) fails it up front, naming the shape.
+ * which == 0 or buf == NULL: back to bf16.  While fp8 is enabled the workspace queries (scail_dit_workspace_bytes, _block_, _sample_)
+ * include the e4m3 copy of a GEMM input, and scail_dit_step_sp / scail_dit_block_sp return an error (sequence-parallel ranks: bf16 only).
+ * scail_dit_fp8_weight_bytes: -1 for a null handle or an unknown bit.
+ */
+#define SCAIL_DIT_FP8_QKV 1u    /* self-attention q | k | v projection */
+#define SCAIL_DIT_FP8_O 2u      /* self-attention out-projection (gated residual) */
+#define SCAIL_DIT_FP8_CQ 4u     /* cross-attention query projection */
+#define SCAIL_DIT_FP8_CO 8u     /* cross-attention out-projection (residual) */
+#define SCAIL_DIT_FP8_W1 16u    /* MLP up (GELU-tanh) */
+#define SCAIL_DIT_FP8_W2 32u    /* MLP down (gated residual) */
+#define SCAIL_DIT_FP8_ALL 63u
+int64_t scail_dit_fp8_weight_bytes(const scail_dit* h, uint32_t which);
+int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int64_t bytes, void* stream);
+
+/*
  * The whole Euler sampling loop of RFSampler (sampling.py:920-982) with VanillaCFG (guiders.py:41-57) for one request:
  *   for i < n_steps:  v = DiT([x; x], timesteps[i], cond [uncond | cond], ref, pose);  x += dsigma[i] (v_u + cfg (v_c - v_u))
  * x fp32 [1,T,16,H,W] in / out (device); timesteps DEVICE fp32 [n_steps][2] (= 1000 sigma_i, twice); dsigma HOST fp32

@@ -21,6 +21,7 @@ argument, and random-init weights unless checkpoints are given."""
 from __future__ import annotations
 
 import argparse
+import copy
 import os
 import time
 
@@ -225,8 +226,14 @@ def main():
     ap.add_argument("--request", action="append", default=[], help="'<prompt>@@<example_dir>' (the reference's cli input line); repeatable")
     ap.add_argument("--input-file", default=None, help="text file of request lines (the reference's --input-type txt)")
     ap.add_argument("--output-dir", default="outputs", help="results of --request / --input-file go to <output-dir>/<example>/")
+    ap.add_argument("--gemm-precision", choices=("bf16", "fp8"), default=None,
+                    help="precision of the six per-token GEMMs of every block (default: the config's, bf16); fp8 = e4m3 with per-token / "
+                         "per-channel scales, single GPU")
     a = ap.parse_args()
     cfg = TINY if a.tiny or not a.base else load_yaml_configs(*a.base)
+    if a.gemm_precision is not None:
+        cfg = copy.deepcopy(cfg)
+        cfg["model"]["network_config"].setdefault("params", {})["gemm_precision"] = a.gemm_precision
     lines = [(r, i) for i, r in enumerate(a.request)] + (list(read_from_file(a.input_file)) if a.input_file else [])
     if lines:
         import os

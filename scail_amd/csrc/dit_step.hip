@@ -4,6 +4,8 @@
 // sat/model/transformer.py:572-746), for one rank or for a sequence-parallel rank (the collectives of the per-layer exchange go to
 // the host through a callback).  Host code only: every line below enqueues kernels on the caller's stream; nothing synchronises, so
 // a single-rank step is hipGraph-capturable.
+#include <algorithm>
+#include <array>
 #include <vector>
 
 #include "common.h"
@@ -28,6 +30,11 @@ struct scail_dit {
     ProfPool pool[PROF_CATS];
     hipEvent_t sp_ev[3] = {nullptr, nullptr, nullptr};   // fork / join events of the sequence-parallel block's side streams (created on first use)
     uint32_t* restart_ctr = nullptr;                     // device counter of restarted self-attention workgroups (allocated by the first scail_dit_profile(h, 1))
+    // fp8 GEMMs (scail_dit_enable_fp8): the SCAIL_DIT_FP8_* mask in force and, per layer and GEMM (bit index), the e4m3 weight codes and
+    // per-channel scales in the caller's buffer
+    uint32_t fp8 = 0;
+    struct Fp8W { const uint8_t* q; const float* s; };
+    std::vector<std::array<Fp8W, 6>> fp8w;
 };
 
 namespace {
@@ -38,7 +45,7 @@ inline int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
 
 // workspace layout (bytes, 256-aligned blocks)
 struct Ws {
-    int64_t tok, h, xn, qkv, att, ff, vt, xf, tokout, temb, e1, emb, adaln, mod, emb2, fin, total;
+    int64_t tok, h, xn, qkv, att, ff, vt, xf, tokout, temb, e1, emb, adaln, mod, emb2, fin, xq, sx, total;
 };
 
 // elements of the V^T staging buffer of a (B, Ltok) block: one rank (sp_mode < 0): all heads x the local keys; ulysses: heads / ranks
@@ -50,7 +57,8 @@ int64_t vt_elems(const scail_dit_config& c, int64_t B, int64_t Ltok, int sp_mode
     return B * (sp_mode == SCAIL_SP_ULYSSES ? nh / ranks : nh) * 128 * Lfp;
 }
 
-Ws layout(const scail_dit_config& c, int64_t B, int64_t T, int64_t H, int64_t W, int sp_mode = -1, int64_t ranks = 1) {
+// f8_k: the widest K of the GEMMs that run in fp8 (0: none) -- the e4m3 copy of a GEMM's input rows and their scales (xq, sx)
+Ws layout(const scail_dit_config& c, int64_t B, int64_t T, int64_t H, int64_t W, int sp_mode = -1, int64_t ranks = 1, int64_t f8_k = 0) {
     const int64_t D = c.hidden_size, FF = c.inner_hidden_size;
     const int64_t hp = H / 2, wp = W / 2;
     const int64_t Lnoise = T * hp * wp, Ltok = hp * wp + Lnoise + T * (H / 4) * (W / 4);
@@ -73,6 +81,8 @@ Ws layout(const scail_dit_config& c, int64_t B, int64_t T, int64_t H, int64_t W,
     s.mod = take((int64_t)c.num_layers * B * 6 * D * 4);
     s.emb2 = take(B * 2 * D * 4);
     s.fin = take(B * 2 * D * 4);
+    s.xq = f8_k ? take(B * Ltok * f8_k) : 0;
+    s.sx = f8_k ? take(B * Ltok * 4) : 0;
     s.total = off;
     return s;
 }
@@ -139,7 +149,45 @@ struct RestartCount {
 
 struct BlockBufs {
     scail_bf16 *xn, *qkv, *att, *ff, *vt;
+    uint8_t* xq = nullptr;   // fp8 GEMMs only: e4m3 rows of the GEMM input and their scales (rows x the widest fp8 K)
+    float* sx = nullptr;
 };
+
+// The per-token GEMMs of a block, by SCAIL_DIT_FP8_* bit index: (N, K) and the bf16 weight
+enum { G_QKV = 0, G_O, G_CQ, G_CO, G_W1, G_W2, G_COUNT };
+static const char* const k_gemm_names[G_COUNT] = {"qkv", "o", "cq", "co", "w1", "w2"};
+static void gemm_shape(const scail_dit_config& c, int g, int64_t* N, int64_t* K) {
+    const int64_t D = c.hidden_size, FF = c.inner_hidden_size;
+    *N = g == G_QKV ? 3 * D : g == G_W1 ? FF : D;
+    *K = g == G_W2 ? FF : D;
+}
+static const scail_bf16* gemm_weight(const scail_dit_layer& lw, int g) {
+    const scail_bf16* const w[G_COUNT] = {lw.qkv_w, lw.o_w, lw.cq_w, lw.co_w, lw.w1, lw.w2};
+    return w[g];
+}
+static int64_t fp8_k(const scail_dit* h) {
+    int64_t kmax = 0;
+    for (int g = 0; g < G_COUNT; ++g)
+        if (h->fp8 & (1u << g)) {
+            int64_t N, K;
+            gemm_shape(h->cfg, g, &N, &K);
+            kmax = std::max(kmax, K);
+        }
+    return kmax;
+}
+
+// GEMM g of layer i: scail_gemm_bf16, or (SCAIL_DIT_FP8_* bit g enabled) the rows of x quantized to e4m3 into the block's scratch and
+// scail_gemm_fp8 on the layer's e4m3 weight; the same epilogue either way
+static int dit_gemm(scail_dit* h, int64_t i, int g, const BlockBufs& bf, const scail_bf16* x, int64_t lda, const float* bias, scail_bf16* y,
+                    int64_t ldc, int64_t M, int64_t N, int64_t K, int epi, const scail_bf16* resid, int64_t ldr, const float* gate, int64_t gs,
+                    int64_t rpb, void* stream) {
+    if (h->fp8 & (1u << g)) {
+        const scail_dit::Fp8W& f = h->fp8w[i][g];
+        DIT_TRY(scail_quant_fp8_rows(x, lda, bf.xq, K, bf.sx, M, K, stream));
+        return scail_gemm_fp8(bf.xq, K, bf.sx, f.q, f.s, bias, y, ldc, M, N, K, epi, resid, ldr, gate, gs, rpb, stream);
+    }
+    return scail_gemm_bf16(x, lda, gemm_weight(h->layers[i], g), bias, y, ldc, M, N, K, epi, resid, ldr, gate, gs, rpb, stream);
+}
 
 constexpr float ATTN_SCALE = 0.08838834764831845f;              // 1 / sqrt(128)
 constexpr float ATTN_LOG2_SCALE = ATTN_SCALE * 1.4426950408889634f;   // queries in log2 units (scail_flash_attn_bf16 SCAIL_ATTN_Q_PRESCALED)
@@ -150,14 +198,16 @@ constexpr float ATTN_LOG2_SCALE = ATTN_SCALE * 1.4426950408889634f;   // queries
 // sat/transformer_defaults.py:163-176).  m = the (6D) modulation row of element b0 (rows of later elements 6D apart).
 // block_attn_out: the out-projection + gated residual alone; block_cross_mlp: the rest (the first point of a block at which the two CFG
 // elements of a step differ: scail_dit_step's SCAIL_DIT_CFG_PAIR).
-static int block_attn_out(scail_dit* h, int64_t i, scail_bf16* hid, scail_bf16* att, const float* m, int64_t nb, int64_t rpb, void* stream) {
+static int block_attn_out(scail_dit* h, int64_t i, scail_bf16* hid, scail_bf16* att, const float* m, int64_t nb, int64_t rpb, const BlockBufs& bf,
+                          void* stream) {
     const int64_t D = h->cfg.hidden_size;
     const scail_dit_layer& lw = h->layers[i];
-    DIT_PROF(SCAIL_DIT_PROF_GEMM, scail_gemm_bf16(att, D, lw.o_w, lw.o_b, hid, D, nb * rpb, D, D, SCAIL_EPI_RESID, hid, D, m + 2 * D, 6 * D, rpb, stream));
+    DIT_PROF(SCAIL_DIT_PROF_GEMM, dit_gemm(h, i, G_O, bf, att, D, lw.o_b, hid, D, nb * rpb, D, D, SCAIL_EPI_RESID, hid, D, m + 2 * D, 6 * D, rpb, stream));
     return 0;
 }
 static int block_cross_mlp(scail_dit* h, int64_t i, scail_bf16* hid, scail_bf16* att, scail_bf16* q3, scail_bf16* xn, scail_bf16* ff,
-                           const float* m, const scail_dit_cond* cond, int64_t Btot, int64_t b0, int64_t nb, int64_t rpb, void* stream) {
+                           const float* m, const scail_dit_cond* cond, int64_t Btot, int64_t b0, int64_t nb, int64_t rpb, const BlockBufs& bf,
+                           void* stream) {
     const scail_dit_config& c = h->cfg;
     const int64_t D = c.hidden_size, FF = c.inner_hidden_size, nh = c.num_heads;
     const float eps = c.layernorm_epsilon;
@@ -166,7 +216,7 @@ static int block_cross_mlp(scail_dit* h, int64_t i, scail_bf16* hid, scail_bf16*
     const scail_dit_layer& lw = h->layers[i];
     // -- cross attention: text + CLIP, ungated residual (dit...:1039-1042, :1107-1203) --
     DIT_TRY(scail_layernorm_affine(hid, D, xn, D, lw.ln_w, lw.ln_b, M, D, eps, stream));
-    DIT_PROF(SCAIL_DIT_PROF_GEMM, scail_gemm_bf16(xn, D, lw.cq_w, lw.cq_b, q3, 3 * D, M, D, D, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
+    DIT_PROF(SCAIL_DIT_PROF_GEMM, dit_gemm(h, i, G_CQ, bf, xn, D, lw.cq_b, q3, 3 * D, M, D, D, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
     // (the queries go to the attention in log2 units, like the self-attention's: no scale / shift per score in the kernel)
     DIT_TRY(scail_rmsnorm_rope_scaled(q3, 3 * D, q3, 3 * D, lw.cqn, nullptr, nullptr, M, M, D, 128, eps, ATTN_LOG2_SCALE, stream));
     const bool shared_clip = cond->Bc == 1;
@@ -177,34 +227,35 @@ static int block_cross_mlp(scail_dit* h, int64_t i, scail_bf16* hid, scail_bf16*
     DIT_PROF(SCAIL_DIT_PROF_CROSS_ATTN, scail_cross_attn2_bf16(q3, rpb * 3 * D, 3 * D, kt, cond->Lt * D, D, vtt, nh * 128 * Ltp, cond->Lt,
                                                                kc, shared_clip ? 0 : cond->Lc * D, D, vtc, shared_clip ? 0 : nh * 128 * Lcp, cond->Lc,
                                                                att, rpb * D, D, nb, nh, rpb, SCAIL_ATTN_Q_PRESCALED, stream));
-    DIT_PROF(SCAIL_DIT_PROF_GEMM, scail_gemm_bf16(att, D, lw.co_w, lw.co_b, hid, D, M, D, D, SCAIL_EPI_RESID, hid, D, nullptr, 0, 0, stream));
+    DIT_PROF(SCAIL_DIT_PROF_GEMM, dit_gemm(h, i, G_CO, bf, att, D, lw.co_b, hid, D, M, D, D, SCAIL_EPI_RESID, hid, D, nullptr, 0, 0, stream));
     // -- MLP (dit...:1045-1050; sat/transformer_defaults.py:163-176) --
     DIT_TRY(scail_ln_modulate(hid, D, xn, D, m + 3 * D, m + 4 * D, 6 * D, nb, rpb, rpb, 0, D, eps, stream));
-    DIT_PROF(SCAIL_DIT_PROF_GEMM, scail_gemm_bf16(xn, D, lw.w1, lw.b1, ff, FF, M, FF, D, SCAIL_EPI_GELU_TANH, nullptr, 0, nullptr, 0, 0, stream));
-    DIT_PROF(SCAIL_DIT_PROF_GEMM, scail_gemm_bf16(ff, FF, lw.w2, lw.b2, hid, D, M, D, FF, SCAIL_EPI_RESID, hid, D, m + 5 * D, 6 * D, rpb, stream));
+    DIT_PROF(SCAIL_DIT_PROF_GEMM, dit_gemm(h, i, G_W1, bf, xn, D, lw.b1, ff, FF, M, FF, D, SCAIL_EPI_GELU_TANH, nullptr, 0, nullptr, 0, 0, stream));
+    DIT_PROF(SCAIL_DIT_PROF_GEMM, dit_gemm(h, i, G_W2, bf, ff, FF, lw.b2, hid, D, M, D, FF, SCAIL_EPI_RESID, hid, D, m + 5 * D, 6 * D, rpb, stream));
     return 0;
 }
 // Everything after the self-attention of the rows [row0, row0 + rows) of every element (rows == Ltok: the whole block in one set of
 // launches; fewer: per element, the wanted rows only).  pair: hid / att / m of element 1 do not exist yet -- the out-projection runs
 // for element 0 and its result (the hidden states after the self-attention residual) is copied to element 1 before the elements part.
 static int block_tail(scail_dit* h, int64_t i, scail_bf16* hid, const float* m, const scail_dit_cond* cond, int64_t B, int64_t Ltok,
-                      scail_bf16* att, scail_bf16* q, scail_bf16* xn, scail_bf16* ff, int64_t row0, int64_t rows, bool pair, void* stream) {
+                      const BlockBufs& bf, int64_t row0, int64_t rows, bool pair, void* stream) {
     const int64_t D = h->cfg.hidden_size;
+    scail_bf16 *att = bf.att, *q = bf.qkv, *xn = bf.xn, *ff = bf.ff;
     if (pair) {
-        DIT_TRY(block_attn_out(h, i, hid + row0 * D, att + row0 * D, m, 1, rows, stream));
+        DIT_TRY(block_attn_out(h, i, hid + row0 * D, att + row0 * D, m, 1, rows, bf, stream));
         if (hipMemcpyAsync(hid + Ltok * D, hid, (size_t)Ltok * D * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
             scail_set_error("scail_dit (cfg pair): hipMemcpyAsync failed");
             return 2;
         }
     }
     if (rows == Ltok) {
-        if (!pair) DIT_TRY(block_attn_out(h, i, hid, att, m, B, Ltok, stream));
-        return block_cross_mlp(h, i, hid, att, q, xn, ff, m, cond, B, 0, B, Ltok, stream);
+        if (!pair) DIT_TRY(block_attn_out(h, i, hid, att, m, B, Ltok, bf, stream));
+        return block_cross_mlp(h, i, hid, att, q, xn, ff, m, cond, B, 0, B, Ltok, bf, stream);
     }
     for (int64_t b = 0; b < B; ++b) {
         const int64_t r = b * Ltok + row0;
-        if (!pair) DIT_TRY(block_attn_out(h, i, hid + r * D, att + r * D, m + b * 6 * D, 1, rows, stream));
-        DIT_TRY(block_cross_mlp(h, i, hid + r * D, att + r * D, q + r * 3 * D, xn, ff, m + b * 6 * D, cond, B, b, 1, rows, stream));
+        if (!pair) DIT_TRY(block_attn_out(h, i, hid + r * D, att + r * D, m + b * 6 * D, 1, rows, bf, stream));
+        DIT_TRY(block_cross_mlp(h, i, hid + r * D, att + r * D, q + r * 3 * D, xn, ff, m + b * 6 * D, cond, B, b, 1, rows, bf, stream));
     }
     return 0;
 }
@@ -230,14 +281,14 @@ static int dit_block(scail_dit* h, int64_t i, scail_bf16* hid, const float* m, c
     const scail_dit_layer& lw = h->layers[i];
     // -- self attention (dit...:1031-1036, :1058-1105) --
     DIT_TRY(scail_ln_modulate(hid, D, bf.xn, D, m, m + D, 6 * D, Bs, Ltok, Ltok, 0, D, eps, stream));
-    DIT_PROF(SCAIL_DIT_PROF_GEMM, scail_gemm_bf16(bf.xn, D, lw.qkv_w, lw.qkv_b, qkv, 3 * D, M, 3 * D, D, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
+    DIT_PROF(SCAIL_DIT_PROF_GEMM, dit_gemm(h, i, G_QKV, bf, bf.xn, D, lw.qkv_b, qkv, 3 * D, M, 3 * D, D, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
     DIT_TRY(scail_rmsnorm_rope(k, 3 * D, k, 3 * D, lw.kn, rope_cos, rope_sin, M, Ltok, D, 128, eps, stream));
     DIT_TRY(scail_transpose_v(v, 3 * D, Ltok * 3 * D, bf.vt, Bs, nh, 128, Ltok, stream));
     // the queries go to the attention in log2 units (q * scale * log2 e, one rounding): its exp2 then needs no scale / shift per score
     DIT_TRY(scail_rmsnorm_rope_scaled(q, 3 * D, q, 3 * D, lw.qn, rope_cos, rope_sin, M, Ltok, D, 128, eps, ATTN_LOG2_SCALE, stream));
     DIT_PROF(SCAIL_DIT_PROF_SELF_ATTN, scail_flash_attn_bf16(q + row0 * 3 * D, Ltok * 3 * D, 3 * D, k, 0, Ltok * 3 * D, 3 * D, bf.vt, 0, nh * 128 * Lp,
                                                              bf.att + row0 * D, Ltok * D, D, Bs, nh, rows, Ltok, 1, SCAIL_ATTN_Q_PRESCALED, 0, stream));
-    return block_tail(h, i, hid, m, cond, B, Ltok, bf.att, q, bf.xn, bf.ff, row0, rows, pair, stream);
+    return block_tail(h, i, hid, m, cond, B, Ltok, bf, row0, rows, pair, stream);
 }
 
 // ---- the sequence-parallel block (include/scail_dit.h "sequence-parallel execution") ----
@@ -252,6 +303,7 @@ static int sp_exchange(const scail_dit_sp* sp, int op, int64_t layer, int64_t b,
 }
 
 static int sp_check(const scail_dit* h, const scail_dit_sp* sp) {
+    SCAIL_REQUIRE(h->fp8 == 0, "fp8 GEMMs are enabled on this handle; sequence-parallel ranks run bf16 only (scail_dit_enable_fp8(h, 0, ...) first)");
     SCAIL_REQUIRE(sp != nullptr && sp->exchange != nullptr, "null sequence-parallel descriptor / exchange callback");
     SCAIL_REQUIRE(sp->ranks >= 2 && sp->ranks <= 64, "ranks must be 2..64");
     SCAIL_REQUIRE(sp->mode == SCAIL_SP_ALLGATHER || sp->mode == SCAIL_SP_ULYSSES, "unknown exchange mode");
@@ -392,26 +444,28 @@ static int dit_block_sp(scail_dit* h, int64_t i, scail_bf16* hid, const float* m
                                                                      1, nh, rows, Lf, 1, SCAIL_ATTN_Q_PRESCALED, 0, stream));
         }
     }
-    return block_tail(h, i, hid, m, cond, Btot, Ltok, bf.att, q, bf.xn, bf.ff, row0, rows, pair, stream);
+    return block_tail(h, i, hid, m, cond, Btot, Ltok, bf, row0, rows, pair, stream);
 }
 
 // Seam B2 (SAT hook layer_forward): one block on caller-owned hidden states.  Workspace: scail_dit_block_workspace_bytes.
-static int64_t block_ws(const scail_dit_config& c, int64_t B, int64_t Ltok, int sp_mode, int64_t ranks, int64_t* off) {
+// off[0..4]: xn, qkv, att, ff, vt; off[5..6]: the fp8 scratch (xq, sx; empty unless f8_k > 0)
+static int64_t block_ws(const scail_dit_config& c, int64_t B, int64_t Ltok, int sp_mode, int64_t ranks, int64_t* off, int64_t f8_k = 0) {
     const int64_t D = c.hidden_size, FF = c.inner_hidden_size;
     int64_t o = 0;
-    const int64_t sizes[5] = {B * Ltok * D * 2, B * Ltok * 3 * D * 2, B * Ltok * D * 2, B * Ltok * FF * 2, vt_elems(c, B, Ltok, sp_mode, ranks) * 2};
-    for (int j = 0; j < 5; ++j) { off[j] = o; o += align256(sizes[j]); }
+    const int64_t sizes[7] = {B * Ltok * D * 2, B * Ltok * 3 * D * 2, B * Ltok * D * 2, B * Ltok * FF * 2, vt_elems(c, B, Ltok, sp_mode, ranks) * 2,
+                              B * Ltok * f8_k, f8_k ? B * Ltok * 4 : 0};
+    for (int j = 0; j < 7; ++j) { off[j] = o; o += align256(sizes[j]); }
     return o;
 }
 extern "C" int64_t scail_dit_block_workspace_bytes(const scail_dit* h, int64_t B, int64_t Ltok) {
     if (h == nullptr || B <= 0 || Ltok <= 0) return -1;
-    int64_t off[5];
-    return block_ws(h->cfg, B, Ltok, -1, 1, off);
+    int64_t off[7];
+    return block_ws(h->cfg, B, Ltok, -1, 1, off, fp8_k(h));
 }
 extern "C" int64_t scail_dit_block_sp_workspace_bytes(const scail_dit* h, int32_t mode, int32_t ranks, int64_t B, int64_t Ltok) {
     if (h == nullptr || B <= 0 || Ltok <= 0 || ranks < 2 || (mode != SCAIL_SP_ALLGATHER && mode != SCAIL_SP_ULYSSES)) return -1;
     if (mode == SCAIL_SP_ULYSSES && h->cfg.num_heads % ranks != 0) return -1;
-    int64_t off[5];
+    int64_t off[7];
     return block_ws(h->cfg, B, Ltok, mode, ranks, off);
 }
 extern "C" int scail_dit_block_sp(scail_dit* h, int64_t layer, scail_bf16* hidden, const float* mod, const scail_dit_cond* cond,
@@ -420,7 +474,7 @@ extern "C" int scail_dit_block_sp(scail_dit* h, int64_t layer, scail_bf16* hidde
     SCAIL_REQUIRE(h != nullptr && hidden != nullptr && mod != nullptr && cond != nullptr, "null argument");
     SCAIL_REQUIRE(layer >= 0 && layer < h->cfg.num_layers && B > 0 && Ltok > 0, "bad layer / shape");
     DIT_TRY(sp_check(h, sp));
-    int64_t off[5];
+    int64_t off[7];
     const int64_t need = block_ws(h->cfg, B, Ltok, sp->mode, sp->ranks, off);
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                   "workspace too small or not 256-byte aligned (scail_dit_block_sp_workspace_bytes)");
@@ -434,13 +488,17 @@ extern "C" int scail_dit_block(scail_dit* h, int64_t layer, scail_bf16* hidden, 
                                void* workspace, int64_t workspace_bytes, void* stream) {
     SCAIL_REQUIRE(h != nullptr && hidden != nullptr && mod != nullptr && cond != nullptr, "null argument");
     SCAIL_REQUIRE(layer >= 0 && layer < h->cfg.num_layers && B > 0 && Ltok > 0, "bad layer / shape");
-    int64_t off[5];
-    const int64_t need = block_ws(h->cfg, B, Ltok, -1, 1, off);
+    int64_t off[7];
+    const int64_t need = block_ws(h->cfg, B, Ltok, -1, 1, off, fp8_k(h));
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                   "workspace too small or not 256-byte aligned (scail_dit_block_workspace_bytes)");
     char* base = static_cast<char*>(workspace);
     auto P = [&](int j) { return reinterpret_cast<scail_bf16*>(base + off[j]); };
-    const BlockBufs bf{P(0), P(1), P(2), P(3), P(4)};
+    BlockBufs bf{P(0), P(1), P(2), P(3), P(4)};
+    if (h->fp8) {
+        bf.xq = reinterpret_cast<uint8_t*>(base + off[5]);
+        bf.sx = reinterpret_cast<float*>(base + off[6]);
+    }
     return dit_block(h, layer, hidden, mod, cond, rope_cos, rope_sin, B, Ltok, bf, 0, Ltok, false, stream);
 }
 
@@ -473,6 +531,64 @@ extern "C" void scail_dit_destroy(scail_dit* h) {
         if (h->restart_ctr != nullptr) (void)hipFree(h->restart_ctr);
     }
     delete h;
+}
+
+// ---- fp8 per-token GEMMs (include/scail_dit.h scail_dit_enable_fp8) ----
+// caller buffer layout: for every layer, for every selected GEMM in bit order, the e4m3 codes [N, K] then the fp32 scales [N], each
+// block 256-byte aligned
+static int64_t fp8_weight_bytes(const scail_dit_config& c, uint32_t which) {
+    int64_t per_layer = 0;
+    for (int g = 0; g < G_COUNT; ++g)
+        if (which & (1u << g)) {
+            int64_t N, K;
+            gemm_shape(c, g, &N, &K);
+            per_layer += align256(N * K) + align256(N * 4);
+        }
+    return per_layer * c.num_layers;
+}
+extern "C" int64_t scail_dit_fp8_weight_bytes(const scail_dit* h, uint32_t which) {
+    if (h == nullptr || (which & ~(uint32_t)SCAIL_DIT_FP8_ALL) != 0) return -1;
+    return fp8_weight_bytes(h->cfg, which);
+}
+extern "C" int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int64_t bytes, void* stream) {
+    SCAIL_REQUIRE(h != nullptr, "null handle");
+    SCAIL_REQUIRE((which & ~(uint32_t)SCAIL_DIT_FP8_ALL) == 0, "unknown SCAIL_DIT_FP8_* bit");
+    if (which == 0 || buf == nullptr) {     // back to bf16
+        h->fp8 = 0;
+        h->fp8w.clear();
+        return 0;
+    }
+    for (int g = 0; g < G_COUNT; ++g)
+        if (which & (1u << g)) {
+            int64_t N, K;
+            gemm_shape(h->cfg, g, &N, &K);
+            if (N % 128 != 0 || K % 128 != 0) {
+                scail_set_error("scail_dit_enable_fp8: the " + std::string(k_gemm_names[g]) + " GEMM (N x K = " + std::to_string(N) + " x " +
+                                std::to_string(K) + ") is outside scail_gemm_fp8's limits (N % 128 == 0, K % 128 == 0)");
+                return 1;
+            }
+        }
+    SCAIL_REQUIRE(bytes >= fp8_weight_bytes(h->cfg, which), "buffer too small (scail_dit_fp8_weight_bytes)");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "buffer must be 256-byte aligned");
+    h->fp8 = 0;                             // bf16 until every selected matrix is quantized
+    h->fp8w.assign(h->cfg.num_layers, {});
+    char* p = static_cast<char*>(buf);
+    for (int64_t i = 0; i < h->cfg.num_layers; ++i)
+        for (int g = 0; g < G_COUNT; ++g) {
+            if (!(which & (1u << g))) continue;
+            int64_t N, K;
+            gemm_shape(h->cfg, g, &N, &K);
+            uint8_t* q = reinterpret_cast<uint8_t*>(p);
+            float* sc = reinterpret_cast<float*>(p + align256(N * K));
+            p += align256(N * K) + align256(N * 4);
+            if (int rc = scail_quant_fp8_rows(gemm_weight(h->layers[i], g), K, q, K, sc, N, K, stream)) {
+                h->fp8w.clear();
+                return rc;
+            }
+            h->fp8w[i][g] = {q, sc};
+        }
+    h->fp8 = which;
+    return 0;
 }
 
 extern "C" int scail_dit_profile(scail_dit* h, int enable) {
@@ -534,7 +650,7 @@ extern "C" int scail_dit_profile_read(scail_dit* h, int category, double* ms_tot
 
 extern "C" int64_t scail_dit_workspace_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W) {
     if (h == nullptr || B <= 0 || T <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0) return -1;
-    return layout(h->cfg, B, T, H, W).total;
+    return layout(h->cfg, B, T, H, W, -1, 1, fp8_k(h)).total;
 }
 extern "C" int64_t scail_dit_sp_workspace_bytes(const scail_dit* h, int32_t mode, int32_t ranks, int64_t B, int64_t T, int64_t H, int64_t W) {
     if (h == nullptr || B <= 0 || T <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0 || ranks < 2) return -1;
@@ -581,7 +697,7 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
     SCAIL_REQUIRE((n_ref == 1 || n_ref == B) && (n_pose == 1 || n_pose == B), "ref / pose batch must be 1 or B");
     SCAIL_REQUIRE(cond->Bc == 1 || cond->Bc == B, "clip batch must be 1 or B");
     const scail_dit_config& c = h->cfg;
-    const Ws s = sp ? layout(c, B, T, H, W, sp->mode, sp->ranks) : layout(c, B, T, H, W);
+    const Ws s = sp ? layout(c, B, T, H, W, sp->mode, sp->ranks) : layout(c, B, T, H, W, -1, 1, fp8_k(h));
     SCAIL_REQUIRE(c.time_embed_dim == c.hidden_size, "final-layer table add needs time_embed_dim == hidden_size");
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= s.total, "workspace too small (scail_dit_workspace_bytes)");
     SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
@@ -626,7 +742,11 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
                                 KPAD, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
     }
 
-    const BlockBufs bf{xn, qkv, att, ff, vt};
+    BlockBufs bf{xn, qkv, att, ff, vt};
+    if (h->fp8) {
+        bf.xq = reinterpret_cast<uint8_t*>(base + s.xq);
+        bf.sx = F32(s.sx);
+    }
     for (int64_t i = 0; i < nl; ++i) {
         // the last layer's output is only read at the noise tokens (final layer below): queries / out-projection / cross attention /
         // MLP of its ref and pose rows are skipped (23 % of that layer's post-K/V work; same result)

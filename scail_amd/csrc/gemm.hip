@@ -15,6 +15,7 @@
 // of tiles so neighbours share operand panels in that XCD's L2), then grouped ordering (g_group_m = 4 m-tiles
 // per group, m fastest) so the co-resident tiles of an XCD share a few operand panels.
 #include "common.h"
+#include "gemm_epi.h"
 #include <atomic>
 #include <algorithm>
 #include <map>
@@ -26,86 +27,10 @@
 #define LDT 72  // padded LDS row, elements (144 B)
 #define GROUP_M 8
 
-struct GemmParams {
-    const u16* x; int64_t lda;
-    const u16* w;
-    const float* bias;
-    u16* y; int64_t ldc;
-    int M, N, K;
-    const u16* resid; int64_t ldr;
-    const float* gate; int64_t gate_stride; int64_t rows_per_batch;
-    int group_m;   // m-tiles per tile group of the block -> tile map (q8 kernel; others use GROUP_M)
-};
-
 // Two instantiations share this body:
 //   128 x 128 tile, 4 waves (2 x 2), wave tile 64 x 64,  74 KB LDS, 2 workgroups per CU  (small / ragged N)
 //   256 x 256 tile, 8 waves (2 x 4), wave tile 128 x 64, 147 KB LDS, 1 workgroup per CU  (the big per-token
 //   GEMMs: half the L2->LDS bytes per FLOP, 6 LDS fragment reads per 8 MFMAs instead of 4 per 4)
-// Fused epilogue shared by the kernels below.  A lane holds output column m (= row of x) and, per 32x32
-// accumulator fragment, rows n = nbase + 8 rr + 4 g + e.  All loads of one pass (bias once; residual and
-// gate per output row) are issued before their first use: one memory round trip per pass.
-template <int EPI, int MI, int NI, int WTM, int WTN>
-__device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[NI][MI], const GemmParams& p, int m0, int n0, int wm, int wn,
-                                              int l31, int g) {
-    float4 bb[NI][4];
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int n = n0 + wn * WTN + ni * 32 + 8 * rr + 4 * g;
-            bb[ni][rr] = (p.bias != nullptr && n < p.N) ? *reinterpret_cast<const float4*>(p.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-        const int m = m0 + wm * WTM + mi * 32 + l31;
-        if (m >= p.M) continue;
-        uint2 rv[NI][4];
-        float4 gt[NI][4];
-        if (EPI == SCAIL_EPI_RESID) {
-            const int64_t bidx = (p.gate != nullptr) ? (int64_t)m / p.rows_per_batch : 0;
-#pragma unroll
-            for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-                for (int rr = 0; rr < 4; ++rr) {
-                    const int n = n0 + wn * WTN + ni * 32 + 8 * rr + 4 * g;
-                    const bool ok = n < p.N;
-                    rv[ni][rr] = ok ? *reinterpret_cast<const uint2*>(p.resid + (int64_t)m * p.ldr + n) : make_uint2(0, 0);
-                    gt[ni][rr] = (ok && p.gate != nullptr) ? *reinterpret_cast<const float4*>(p.gate + bidx * p.gate_stride + n)
-                                                           : make_float4(1.f, 1.f, 1.f, 1.f);
-                }
-        }
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) {
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const int n = n0 + wn * WTN + ni * 32 + 8 * rr + 4 * g;
-                if (n >= p.N) continue;
-                float v[4];
-                v[0] = acc[ni][mi][4 * rr + 0] + bb[ni][rr].x;
-                v[1] = acc[ni][mi][4 * rr + 1] + bb[ni][rr].y;
-                v[2] = acc[ni][mi][4 * rr + 2] + bb[ni][rr].z;
-                v[3] = acc[ni][mi][4 * rr + 3] + bb[ni][rr].w;
-                if (EPI == SCAIL_EPI_GELU_TANH) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = gelu_tanh_f(v[e]);
-                } else if (EPI == SCAIL_EPI_GELU_ERF) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = gelu_erf_f(v[e]);
-                } else if (EPI == SCAIL_EPI_RESID) {
-                    v[0] = bf_lo(rv[ni][rr].x) + gt[ni][rr].x * v[0];
-                    v[1] = bf_hi(rv[ni][rr].x) + gt[ni][rr].y * v[1];
-                    v[2] = bf_lo(rv[ni][rr].y) + gt[ni][rr].z * v[2];
-                    v[3] = bf_hi(rv[ni][rr].y) + gt[ni][rr].w * v[3];
-                }
-                uint2 o;
-                o.x = pack_bf16x2(v[0], v[1]);
-                o.y = pack_bf16x2(v[2], v[3]);
-                *reinterpret_cast<uint2*>(p.y + (int64_t)m * p.ldc + n) = o;
-            }
-        }
-    }
-}
-
 // DMA: operand tiles arrive by LDS-DMA (global_load_lds_dwordx4, 1 KiB = 8 rows x 128 B per wave-instruction,
 // lane-linear -> unpadded 128-B rows); bank conflicts are removed by XOR-ing the 16-byte chunk index with
 // (row >> 1) & 7 on the per-lane SOURCE address and on the fragment reads.  No staging VGPRs, no ds_write.

@@ -1,0 +1,265 @@
+// FP8 (OCP e4m3fn) path of the per-token GEMMs (include/scail_hip.h "fp8 per-token GEMMs"):
+//   scail_quant_fp8_rows  bf16 [R, C] -> e4m3 [R, C] + one fp32 scale per row (activations per token, weights per output channel)
+//   scail_gemm_fp8        y = epi(acc[m, n] * sx[m] * sw[n] + bias[n]), acc = the e4m3 product on the block-scaled MFMA
+//                         v_mfma_scale_f32_32x32x64_f8f6f4 (twice the bf16 matrix rate per clock), bf16 out.
+// The E8M0 block scales of the MFMA are held at the unit value (127): the per-row fp32 scales are applied in the epilogue, so every
+// output row still depends on its own input row alone (what keeps the executor's CFG-pair and last-layer prunings exact).
+#include "common.h"
+#include "gemm_epi.h"
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+typedef uint8_t u8;
+
+// ---- quantization ------------------------------------------------------------------------------------------------------------
+// One 256-thread block per row, 16-byte loads (8 bf16) per lane: pass 1 takes amax = max |x| over the row, pass 2 re-reads the row
+// (an L2 hit: a row is at most a few tens of KB) and writes 8 codes per lane.  Numerics (bit-exact, tests/test_fp8_gpu.py):
+//   amax == 0: s = 1, q = 0;  else s = amax / 448, r = 448 / amax, q = e4m3_rne(clamp(x r, -448, 448)) (clamped first: e4m3fn has no
+//   infinity, v_cvt_pk_fp8_f32 would turn an overflow into NaN).
+#define QF8_THREADS 256
+__global__ __launch_bounds__(QF8_THREADS) void scail_quant_fp8_rows_kernel(const u16* __restrict__ x, int64_t ldx, u8* __restrict__ q,
+                                                                           int64_t ldq, float* __restrict__ s, int cols) {
+    __shared__ float red[QF8_THREADS / 64];
+    const int64_t r = blockIdx.x;
+    const u16* xr = x + r * ldx;
+    u8* qr = q + r * ldq;
+    float amax = 0.f;
+    for (int c = threadIdx.x * 8; c < cols; c += QF8_THREADS * 8) {
+        float f[8];
+        unpack8(*reinterpret_cast<const uint4*>(xr + c), f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(f[e]));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
+    __syncthreads();
+    amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const bool zero = amax == 0.f;
+    const float rs = zero ? 0.f : 448.0f / amax;
+    if (threadIdx.x == 0) s[r] = zero ? 1.0f : amax / 448.0f;
+    for (int c = threadIdx.x * 8; c < cols; c += QF8_THREADS * 8) {
+        float f[8];
+        unpack8(*reinterpret_cast<const uint4*>(xr + c), f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = fminf(fmaxf(f[e] * rs, -448.0f), 448.0f);
+        int lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+        lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+        int hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
+        hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+        *reinterpret_cast<uint2*>(qr + c) = zero ? make_uint2(0u, 0u) : make_uint2((uint32_t)lo, (uint32_t)hi);
+    }
+}
+
+extern "C" int scail_quant_fp8_rows(const scail_bf16* x, int64_t ldx, uint8_t* q, int64_t ldq, float* s, int64_t rows, int64_t cols,
+                                    void* stream) {
+    SCAIL_REQUIRE(x != nullptr && q != nullptr && s != nullptr, "null pointer");
+    SCAIL_REQUIRE(rows >= 0 && cols > 0 && cols % 8 == 0 && cols < (1ll << 30), "cols must be a positive multiple of 8");
+    SCAIL_REQUIRE(ldx >= cols && ldq >= cols && ldx % 8 == 0 && ldq % 8 == 0, "ldx / ldq must be >= cols and multiples of 8");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(q) & 7) == 0 &&
+                      (reinterpret_cast<uintptr_t>(s) & 3) == 0,
+                  "pointer alignment (x 16 B, q 8 B, s 4 B)");
+    SCAIL_REQUIRE(rows < (1ll << 31), "too many rows");
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(scail_quant_fp8_rows_kernel, dim3((unsigned)rows), dim3(QF8_THREADS), 0, (hipStream_t)stream,
+                       reinterpret_cast<const u16*>(x), ldx, q, ldq, s, (int)cols);
+    return scail_check_launch("scail_quant_fp8_rows");
+}
+
+// ---- GEMM --------------------------------------------------------------------------------------------------------------------
+// 256 x 256 tile, k-tile 128 (= 128 bytes of a row, as the bf16 kernels' 64), 8 waves (2 x 4), wave tile 128(m) x 64(n) as
+// 4 x 2 fragments of v_mfma_scale_f32_32x32x64_f8f6f4.  Both operands arrive by LDS-DMA (global_load_lds_dwordx4, 8 rows x 128 B per
+// wave-instruction, lane-linear unpadded 128-B rows) two k-tiles deep, all LDS in ONE dynamic __shared__ array; bank conflicts are
+// removed by XOR-ing the 16-byte chunk index with (row >> 1) & 7 on the per-lane SOURCE address and on the fragment reads (the layout
+// of gemm.hip's LDS-DMA kernel).  One barrier per k-tile: the DMA of tile t + 1 is issued before the MFMAs of tile t and retired
+// (vmcnt(0) + barrier) after them.
+// Fragments: the MFMA is issued "transposed" (A = W rows, B = x rows) so that a lane's accumulators run along n (gemm_epi.h).  Lane
+// (r = l & 31, g = l >> 5) of a 32x32x64 step feeds the 32 bytes k = 32 g .. 32 g + 31 of row r of each operand.  A and B take the same
+// k subset per lane, so the dot product is right whatever order the hardware gives those 32 k inside the step (the block scales are
+// all 1); the exact-integer test with an asymmetric W proves the row / column map.
+#define F8_BK 128
+#define F8_GROUP_M 4
+
+struct GemmFp8Params {
+    GemmParams e;                  // epilogue part (x / w unused)
+    const u8* x; const u8* w;      // e4m3 [M, lda], [N, K]
+    const float* sx; const float* sw;
+};
+
+template <int EPI>
+__global__ __launch_bounds__(512) void scail_gemm_fp8_kernel(GemmFp8Params P) {
+    constexpr int BM = 256, BN = 256, WN = 4, NT = 512;
+    constexpr int WTM = 128, WTN = 64, MI = WTM / 32, NI = WTN / 32;
+    extern __shared__ __attribute__((aligned(16))) u8 smem8[];
+    u8* Xs = smem8;                   // [2][BM][F8_BK]
+    u8* Ws = smem8 + 2 * BM * F8_BK;  // [2][BN][F8_BK]
+    const GemmParams& p = P.e;
+
+    // ---- tile mapping: XCD-aware bijective remap, then groups of F8_GROUP_M m-tiles sweeping n ----
+    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    const int nb = tiles_m * tiles_n;
+    int wg;
+    {
+        const int id = blockIdx.x;
+        const int q = nb >> 3, r = nb & 7, xcd = id & 7, loc = id >> 3;
+        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    }
+    const int in_group = F8_GROUP_M * tiles_n;
+    const int gid = wg / in_group;
+    const int first_m = gid * F8_GROUP_M;
+    const int gsz = min(tiles_m - first_m, F8_GROUP_M);
+    const int pid_m = first_m + (wg % in_group) % gsz;
+    const int pid_n = (wg % in_group) / gsz;
+    const int m0 = pid_m * BM, n0 = pid_n * BN;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    const int l31 = lane & 31, g = lane >> 5;
+
+    // LDS-DMA pieces: piece j of an operand = tile rows 8j .. 8j + 7; lane -> row 8j + (l >> 3), chunk l & 7.  Rows past M / N read
+    // the last row (their outputs are not stored).
+    constexpr int PA = BM / 8 / (NT / 64), PB = BN / 8 / (NT / 64);
+    const int d_row = lane >> 3, d_c = lane & 7;
+    const u8* srcx[PA];
+    const u8* srcw[PB];
+#pragma unroll
+    for (int i = 0; i < PA; ++i) {
+        const int r = 8 * (wave * PA + i) + d_row;
+        srcx[i] = P.x + (int64_t)min(m0 + r, p.M - 1) * p.lda + ((d_c ^ ((r >> 1) & 7)) << 4);
+    }
+#pragma unroll
+    for (int i = 0; i < PB; ++i) {
+        const int r = 8 * (wave * PB + i) + d_row;
+        srcw[i] = P.w + (int64_t)min(n0 + r, p.N - 1) * p.K + ((d_c ^ ((r >> 1) & 7)) << 4);
+    }
+#define F8_DMA(k0_, buf_)                                                                                                 \
+    {                                                                                                                     \
+        _Pragma("unroll") for (int i_ = 0; i_ < PA; ++i_)                                                                 \
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcx[i_] + (k0_)),          \
+                (__attribute__((address_space(3))) void*)(Xs + ((buf_) * BM + 8 * (wave * PA + i_)) * F8_BK), 16, 0, 0);  \
+        _Pragma("unroll") for (int i_ = 0; i_ < PB; ++i_)                                                                 \
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcw[i_] + (k0_)),          \
+                (__attribute__((address_space(3))) void*)(Ws + ((buf_) * BN + 8 * (wave * PB + i_)) * F8_BK), 16, 0, 0);  \
+    }
+    // fragment-read byte offsets in this lane's row: k-step ks, 16-byte half hf -> chunk 4 ks + 2 g + hf, swizzled
+    int foff[2][2];
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) foff[ks][hf] = ((4 * ks + 2 * g + hf) ^ ((l31 >> 1) & 7)) << 4;
+
+    f32x16 acc[NI][MI];
+#pragma unroll
+    for (int a = 0; a < NI; ++a)
+#pragma unroll
+        for (int b = 0; b < MI; ++b)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+
+    const int nk = p.K / F8_BK;
+    F8_DMA(0, 0)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int t = 0; t < nk; ++t) {
+        const int cur = t & 1;
+        if (t + 1 < nk) F8_DMA((t + 1) * F8_BK, cur ^ 1)
+        const u8* xs = Xs + (cur * BM + wm * WTM + l31) * F8_BK;
+        const u8* ws = Ws + (cur * BN + wn * WTN + l31) * F8_BK;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            i32x8 wf[NI], xf[MI];
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                const uint4 lo = *reinterpret_cast<const uint4*>(ws + i * 32 * F8_BK + foff[ks][0]);
+                const uint4 hi = *reinterpret_cast<const uint4*>(ws + i * 32 * F8_BK + foff[ks][1]);
+                wf[i] = i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+            }
+#pragma unroll
+            for (int i = 0; i < MI; ++i) {
+                const uint4 lo = *reinterpret_cast<const uint4*>(xs + i * 32 * F8_BK + foff[ks][0]);
+                const uint4 hi = *reinterpret_cast<const uint4*>(xs + i * 32 * F8_BK + foff[ks][1]);
+                xf[i] = i32x8{(int)lo.x, (int)lo.y, (int)lo.z, (int)lo.w, (int)hi.x, (int)hi.y, (int)hi.z, (int)hi.w};
+            }
+#pragma unroll
+            for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi)
+                    acc[ni][mi] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[ni], xf[mi], acc[ni][mi], 0, 0, 0, 127, 0, 127);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+#undef F8_DMA
+
+    // per-token x per-channel scales: acc[ni][mi][4 rr + e] is (m = .. + l31, n = .. + 8 rr + 4 g + e); v = (acc * sx[m]) * sw[n]
+#pragma unroll
+    for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+            const int n = n0 + wn * WTN + ni * 32 + 8 * rr + 4 * g;
+            const float4 swn = n < p.N ? *reinterpret_cast<const float4*>(P.sw + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi) {
+                const float sxm = P.sx[min(m0 + wm * WTM + mi * 32 + l31, p.M - 1)];
+                acc[ni][mi][4 * rr + 0] = acc[ni][mi][4 * rr + 0] * sxm * swn.x;
+                acc[ni][mi][4 * rr + 1] = acc[ni][mi][4 * rr + 1] * sxm * swn.y;
+                acc[ni][mi][4 * rr + 2] = acc[ni][mi][4 * rr + 2] * sxm * swn.z;
+                acc[ni][mi][4 * rr + 3] = acc[ni][mi][4 * rr + 3] * sxm * swn.w;
+            }
+        }
+    gemm_epilogue<EPI, MI, NI, WTM, WTN>(acc, p, m0, n0, wm, wn, l31, g);
+}
+
+template <int EPI>
+static int launch_gemm_fp8(const GemmFp8Params& P, hipStream_t stream) {
+    constexpr int lds = 2 * (256 + 256) * F8_BK;   // 128 KB
+    static ScailDeviceOnce attr_set;
+    if (attr_set.need()) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scail_gemm_fp8_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        if (e != hipSuccess) {
+            scail_set_error(std::string("scail_gemm_fp8: hipFuncSetAttribute: ") + hipGetErrorString(e));
+            return 2;
+        }
+        attr_set.done();
+    }
+    const int tiles = ((P.e.M + 255) / 256) * ((P.e.N + 255) / 256);
+    hipLaunchKernelGGL((scail_gemm_fp8_kernel<EPI>), dim3((unsigned)tiles), dim3(512), lds, stream, P);
+    return scail_check_launch("scail_gemm_fp8");
+}
+
+extern "C" int scail_gemm_fp8(const uint8_t* x, int64_t lda, const float* sx, const uint8_t* w, const float* sw, const float* bias,
+                              scail_bf16* y, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
+                              const scail_bf16* resid, int64_t ldr, const float* gate, int64_t gate_stride,
+                              int64_t rows_per_batch, void* stream) {
+    SCAIL_REQUIRE(x != nullptr && sx != nullptr && w != nullptr && sw != nullptr && y != nullptr, "null pointer");
+    SCAIL_REQUIRE(M >= 1 && M < (1ll << 31), "M must be >= 1");
+    SCAIL_REQUIRE(N > 0 && N % 128 == 0 && N < (1ll << 31), "N must be a positive multiple of 128");
+    SCAIL_REQUIRE(K > 0 && K % 128 == 0 && K < (1ll << 31), "K must be a positive multiple of 128");
+    SCAIL_REQUIRE(lda >= K && lda % 16 == 0 && ldc >= N && ldc % 4 == 0, "lda must be >= K and a multiple of 16, ldc >= N and a multiple of 4");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0 &&
+                      (reinterpret_cast<uintptr_t>(sw) & 15) == 0 && (reinterpret_cast<uintptr_t>(sx) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(y) & 7) == 0 && (reinterpret_cast<uintptr_t>(bias) & 15) == 0,
+                  "pointer alignment (x, w, sw, bias 16 B; y 8 B; sx 4 B)");
+    if (epilogue == SCAIL_EPI_RESID) {
+        SCAIL_REQUIRE(resid != nullptr && ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(resid) & 7) == 0, "RESID epilogue needs resid with ldr % 4 == 0");
+        SCAIL_REQUIRE(gate == nullptr || (rows_per_batch > 0 && gate_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(gate) & 15) == 0),
+                      "gate needs rows_per_batch > 0, gate_stride % 4 == 0");
+    }
+    GemmFp8Params P;
+    GemmParams& p = P.e;
+    p.x = nullptr; p.lda = lda; p.w = nullptr; p.bias = bias;
+    p.y = reinterpret_cast<u16*>(y); p.ldc = ldc;
+    p.M = (int)M; p.N = (int)N; p.K = (int)K;
+    p.resid = reinterpret_cast<const u16*>(resid); p.ldr = ldr; p.gate = gate; p.gate_stride = gate_stride; p.rows_per_batch = rows_per_batch;
+    p.group_m = F8_GROUP_M;
+    P.x = x; P.w = w; P.sx = sx; P.sw = sw;
+    hipStream_t s = (hipStream_t)stream;
+    switch (epilogue) {
+        case SCAIL_EPI_BIAS: return launch_gemm_fp8<SCAIL_EPI_BIAS>(P, s);
+        case SCAIL_EPI_GELU_TANH: return launch_gemm_fp8<SCAIL_EPI_GELU_TANH>(P, s);
+        case SCAIL_EPI_RESID: return launch_gemm_fp8<SCAIL_EPI_RESID>(P, s);
+        default:
+            scail_set_error("scail_gemm_fp8: epilogue must be SCAIL_EPI_BIAS, SCAIL_EPI_GELU_TANH or SCAIL_EPI_RESID");
+            return 1;
+    }
+}

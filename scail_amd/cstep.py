@@ -78,6 +78,24 @@ class CStep:
         L.call("scail_dit_create", C.byref(cfg), C.byref(w), C.byref(h))
         self._h = h
         self._ws = None
+        self._fp8_buf = None
+        if getattr(net, "fp8_mask", 0):
+            self.enable_fp8(net.fp8_mask, W["patch_w"].device)
+
+    def enable_fp8(self, which: int, device) -> None:
+        """scail_dit_enable_fp8: quantize the selected per-token GEMM weights (lib.FP8_GEMMS bits) into a buffer this object owns;
+        which = 0 returns to bf16."""
+        lib = L.load()
+        if not which:
+            L.call("scail_dit_enable_fp8", self._h, 0, None, 0, torch.cuda.current_stream(device).cuda_stream)
+            self._fp8_buf = None
+            return
+        need = lib.scail_dit_fp8_weight_bytes(self._h, which)
+        if need < 0:
+            raise L.ScailHipError(f"scail_dit_fp8_weight_bytes: bad mask {which}")
+        buf = torch.empty(need, device=device, dtype=torch.uint8)
+        L.call("scail_dit_enable_fp8", self._h, which, buf.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream)
+        self._fp8_buf = buf
 
     def close(self):
         if self._h is not None:

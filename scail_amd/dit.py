@@ -57,6 +57,31 @@ def _register(root: nn.Module, path: str, p: nn.Parameter):
     mod.register_parameter(parts[-1], p)
 
 
+def _fp8_options(gemm_precision, fp8_gemms):
+    """("bf16" | "fp8", SCAIL_DIT_FP8_* mask) from the constructor options: fp8_gemms = None (all six per-token GEMMs), an iterable of
+    names from lib.FP8_GEMMS, or the mask itself."""
+    if gemm_precision not in ("bf16", "fp8"):
+        raise ValueError(f"gemm_precision must be 'bf16' or 'fp8', got {gemm_precision!r}")
+    if gemm_precision == "bf16":
+        if fp8_gemms is not None:
+            raise ValueError("fp8_gemms needs gemm_precision='fp8'")
+        return "bf16", 0
+    if fp8_gemms is None:
+        return "fp8", L.FP8_ALL
+    if isinstance(fp8_gemms, int) and not isinstance(fp8_gemms, bool):
+        mask = fp8_gemms
+    else:
+        if isinstance(fp8_gemms, str):
+            fp8_gemms = [g for g in fp8_gemms.replace(",", " ").split() if g]
+        unknown = [g for g in fp8_gemms if g not in L.FP8_GEMMS]
+        if unknown:
+            raise ValueError(f"fp8_gemms: unknown GEMM(s) {unknown}; choose from {sorted(L.FP8_GEMMS)}")
+        mask = sum(L.FP8_GEMMS[g] for g in set(fp8_gemms))
+    if not 0 < mask <= L.FP8_ALL:
+        raise ValueError(f"fp8_gemms must select at least one of {sorted(L.FP8_GEMMS)} (mask 1..{L.FP8_ALL}), got {fp8_gemms!r}")
+    return "fp8", mask
+
+
 class DiffusionTransformer(nn.Module):
     """Reference-compatible network object; see module docstring."""
 
@@ -68,7 +93,7 @@ class DiffusionTransformer(nn.Module):
                  parallel_output=True, height_interpolation=1.0, width_interpolation=1.0, time_interpolation=1.0,
                  use_SwiGLU=False, use_RMSNorm=False, cfg_embed_dim=None, ofs_embed_dim=None,
                  layernorm_epsilon=1e-6, inner_hidden_size=None, use_i2v_clip=False, dtype="bf16",
-                 device=None, init_seed=1234, **kwargs):
+                 device=None, init_seed=1234, gemm_precision="bf16", fp8_gemms=None, **kwargs):
         super().__init__()
         # ---- options of the reference class this engine does not implement: fail loudly ----
         unsupported = []
@@ -119,6 +144,13 @@ class DiffusionTransformer(nn.Module):
         for nm, mult in (("hidden_size", 64), ("inner_hidden_size", 64), ("text_dim", 64)):
             if getattr(self, nm) % mult:
                 raise NotImplementedError(f"{nm} must be a multiple of {mult}")
+        # opt-in fp8 (e4m3) per-token GEMMs (include/scail_dit.h scail_dit_enable_fp8); a yaml sets them through network_config.params
+        self.gemm_precision, self.fp8_mask = _fp8_options(gemm_precision, fp8_gemms)
+        if self.fp8_mask:
+            D, FF = self.hidden_size, self.inner_hidden_size
+            for name, (n, k) in (("qkv", (3 * D, D)), ("o", (D, D)), ("cq", (D, D)), ("co", (D, D)), ("w1", (FF, D)), ("w2", (D, FF))):
+                if self.fp8_mask & L.FP8_GEMMS[name] and (n % 128 or k % 128):
+                    raise NotImplementedError(f"fp8 GEMM {name} ({n} x {k}): the fp8 kernel needs N and K multiples of 128")
         self._build_params(device, init_seed)
         self._prepared: Optional[Dict] = None
         self._cond_cache = None
@@ -131,6 +163,7 @@ class DiffusionTransformer(nn.Module):
         # one C call per network evaluation (include/scail_dit.h) instead of ~25 ctypes calls per layer; env override
         self.use_c_step = os.environ.get("SCAIL_C_STEP", "1") != "0"
         self._cstep = None
+        self._c_blocks = False             # test hook: drive the executor block by block (scail_dit_block) as the multi-character path does
 
     # ------------------------------------------------------------------------------------------
     # parameters (reference names / shapes)
@@ -473,11 +506,14 @@ class DiffusionTransformer(nn.Module):
         cos, sin = self._rope(T, hp, wp, H_shift, W_shift, dev, n_char)
         sp = self.sp if (self.sp is not None and self.sp.size > 1) else None
         use_c = self.use_c_step and self._tap is None and self.kernel_timer is None
+        if self.fp8_mask and (sp is not None or not use_c):
+            raise NotImplementedError("gemm_precision='fp8' runs in the C executor on a single rank only: not on sequence-parallel ranks, "
+                                      "not on the per-op path (SCAIL_C_STEP=0, _tap, kernel_timer)")
         if use_c and self._cstep is None:
             from .cstep import CStep
             self._cstep = CStep(self, W)
         xch = sp.c_exchange(nh, D, B, Ltok, dev) if (use_c and sp is not None) else None
-        if use_c and n_char == 1:
+        if use_c and n_char == 1 and not self._c_blocks:
             # the whole evaluation as ONE call into the library (include/scail_dit.h); same kernels, same order.  A sequence-parallel
             # rank runs the same executor: only the collectives of the per-layer exchange come back to the host (xch)
             if sp is None:

@@ -57,6 +57,8 @@ SIGNATURES = {
     "scail_release_caches": [],
     "scail_f32_to_bf16": [_p, _p, _i64, _p],
     "scail_bf16_to_f32": [_p, _p, _i64, _p],
+    "scail_quant_fp8_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _p],
+    "scail_gemm_fp8": [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _i64, _p, _i64, _i64, _p],
     # include/scail_dit.h (structs are passed by pointer; scail_amd/cstep.py builds them)
     "scail_dit_create": [_p, _p, _p],
     "scail_dit_destroy": [_p],
@@ -72,6 +74,8 @@ SIGNATURES = {
     "scail_dit_block_sp": [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _p],
     "scail_dit_sample_workspace_bytes": [_p, _i64, _i64, _i64],
     "scail_dit_sample": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _i64, _p],
+    "scail_dit_fp8_weight_bytes": [_p, C.c_uint32],
+    "scail_dit_enable_fp8": [_p, C.c_uint32, _p, _i64, _p],
     # include/scail_vae.h (scail_amd/cvae.py builds the structs)
     "scail_vae_create": [_p, _p],
     "scail_vae_destroy": [_p],
@@ -82,7 +86,8 @@ SIGNATURES = {
 }
 # return types other than the int status
 RESTYPES = {"scail_dit_destroy": None, "scail_vae_destroy": None, "scail_vae_workspace_bytes": _i64, "scail_dit_workspace_bytes": _i64, "scail_dit_sample_workspace_bytes": _i64,
-            "scail_dit_block_workspace_bytes": _i64, "scail_dit_sp_workspace_bytes": _i64, "scail_dit_block_sp_workspace_bytes": _i64}
+            "scail_dit_block_workspace_bytes": _i64, "scail_dit_sp_workspace_bytes": _i64, "scail_dit_block_sp_workspace_bytes": _i64,
+            "scail_dit_fp8_weight_bytes": _i64}
 
 # include/scail_hip_ablation.h: only libscail_hip_abl.so (SCAIL_ABLATIONS=1) exports these
 ABLATION_SIGNATURES = {
@@ -93,7 +98,11 @@ ABLATIONS = LIB_PATH.endswith("_abl.so")
 
 EPI_BIAS, EPI_GELU_TANH, EPI_GELU_ERF, EPI_RESID = 0, 1, 2, 3
 ACT_NONE, ACT_SILU, ACT_GELU_TANH = 0, 1, 2
-ABI_VERSION = 5          # 5 = scail_rmsnorm_rope_slabs takes a slab row stride; the sequence-parallel exchange is ONE collective per direction
+# include/scail_dit.h SCAIL_DIT_FP8_*: the per-token GEMMs of a block that scail_dit_enable_fp8 switches to fp8
+FP8_GEMMS = {"qkv": 1, "o": 2, "cq": 4, "co": 8, "w1": 16, "w2": 32}
+FP8_ALL = 63
+ABI_VERSION = 6          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);
+                         # 5 = scail_rmsnorm_rope_slabs takes a slab row stride; the sequence-parallel exchange is ONE collective per direction
                          # (send / recv layouts of scail_dit.h), exchange-wait / restart categories of scail_dit_profile_read;
                          # 4 = `flags` argument of scail_dit_step / scail_dit_step_sp (SCAIL_DIT_CFG_PAIR), options "attn4_rows" / "attn4_xcd";
                          # include/scail_hip.h scail_abi_version: 2 = negative SCAIL_ATTN_Q_PRESCALED sentinel + the SP executor entry points;

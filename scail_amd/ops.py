@@ -81,6 +81,54 @@ def gemm(x, w, bias=None, out=None, epilogue=L.EPI_BIAS, resid=None, gate=None, 
     return out
 
 
+def quant_fp8_rows(x, out=None, scale=None):
+    """Per-row e4m3 quantization (include/scail_hip.h scail_quant_fp8_rows): x (..., C) bf16 -> (codes uint8 (rows, C), scales fp32
+    (rows,)); x = codes.view(torch.float8_e4m3fn) * scales[:, None] up to the e4m3 rounding."""
+    _chk(x, bf16, "quant_fp8_rows.x")
+    R, C, ldx = _rowmajor2d(x, "quant_fp8_rows.x")
+    if out is None:
+        out = torch.empty(R, C, device=x.device, dtype=torch.uint8)
+    if scale is None:
+        scale = torch.empty(R, device=x.device, dtype=f32)
+    _chk(out, torch.uint8, "quant_fp8_rows.out"); _chk(scale, f32, "quant_fp8_rows.scale")
+    Ro, Co, ldq = _rowmajor2d(out, "quant_fp8_rows.out")
+    assert Ro == R and Co == C and scale.numel() == R and scale.is_contiguous()
+    L.call("scail_quant_fp8_rows", x.data_ptr(), ldx, out.data_ptr(), ldq, scale.data_ptr(), R, C, _stream())
+    return out, scale
+
+
+def gemm_fp8(xq, sx, wq, sw, bias=None, out=None, epilogue=L.EPI_BIAS, resid=None, gate=None, rows_per_batch=0):
+    """y = epilogue((xq @ wq.T) * sx[:, None] * sw[None, :] + bias) (include/scail_hip.h scail_gemm_fp8).  xq (M, K) / wq (N, K) e4m3 codes
+    (uint8, from quant_fp8_rows), sx (M,) / sw (N,) fp32; bias, out, resid, gate as for gemm()."""
+    _chk(xq, torch.uint8, "gemm_fp8.xq"); _chk(wq, torch.uint8, "gemm_fp8.wq")
+    _chk(sx, f32, "gemm_fp8.sx"); _chk(sw, f32, "gemm_fp8.sw")
+    M, K, lda = _rowmajor2d(xq, "gemm_fp8.xq")
+    N = wq.shape[0]
+    if wq.shape[1] != K or not wq.is_contiguous():
+        raise L.ScailHipError("gemm_fp8: wq must be contiguous (N, K)")
+    assert sx.numel() == M and sw.numel() == N and sx.is_contiguous() and sw.is_contiguous()
+    if out is None:
+        out = torch.empty(M, N, device=xq.device, dtype=bf16)
+    _chk(out, bf16, "gemm_fp8.out")
+    Mo, No, ldc = _rowmajor2d(out, "gemm_fp8.out")
+    assert Mo == M and No == N, (Mo, M, No, N)
+    ldr = 0
+    if resid is not None:
+        _chk(resid, bf16, "gemm_fp8.resid")
+        Mr, Nr, ldr = _rowmajor2d(resid, "gemm_fp8.resid")
+        assert Mr == M and Nr == N
+    gs = 0
+    if gate is not None:
+        _chk(gate, f32, "gemm_fp8.gate")
+        assert gate.dim() == 2 and gate.shape[1] == N and gate.stride(1) == 1
+        gs = gate.stride(0)
+    if bias is not None:
+        _chk(bias, f32, "gemm_fp8.bias")
+    L.call("scail_gemm_fp8", xq.data_ptr(), lda, sx.data_ptr(), wq.data_ptr(), sw.data_ptr(), _ptr(bias), out.data_ptr(), ldc, M, N, K,
+           epilogue, _ptr(resid), ldr, _ptr(gate), gs, rows_per_batch, _stream())
+    return out
+
+
 def ln_modulate(x, shift, scale, out=None, eps=1e-6, rows_out=None, src_rows_per_batch=None, src_row_offset=0):
     """x (B, Ls, D) bf16; shift/scale fp32 (B, D) views (same row stride).  Output (B, rows_out, D)."""
     _chk(x, bf16, "ln_modulate.x"); _chk(shift, f32, "shift"); _chk(scale, f32, "scale")

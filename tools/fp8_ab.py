@@ -1,0 +1,157 @@
+"""A/B of the fp8 (e4m3) per-token GEMM path against bf16, in one process, alternating the two arms with device events after warm-up
+(include/scail_hip.h scail_gemm_fp8 / scail_quant_fp8_rows, include/scail_dit.h scail_dit_enable_fp8):
+  * the four distinct 14B GEMM shapes at M = 97 664 (N x K = 15360 x 5120, 5120 x 5120, 13824 x 5120, 5120 x 13824): TFLOP/s of
+    scail_gemm_bf16 (gemm4) and scail_gemm_fp8, the fraction of the 5 PF dense MX-fp8 peak, the ratio fp8 / gemm4;
+  * the quantization pass in GB/s (bf16 read + e4m3 write + scales);
+  * the config-2 step (14B, 512x896x81f, B = 2, CFG pair, scail_dit_step): bf16 against fp8 with every per-token GEMM in fp8, or the
+    --mask of SCAIL_DIT_FP8_* bits.
+Usage: python tools/fp8_ab.py [--reps 10] [--layers 40] [--no-step] [--no-gemm] [--mask 63]
+Prints one line per measurement and a JSON summary line last."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from scail_amd import lib as L, ops  # noqa: E402
+
+M14B = 97664
+SHAPES = [(15360, 5120), (5120, 5120), (13824, 5120), (5120, 13824)]
+PEAK_FP8_TF = 5000.0
+P14B = dict(hidden_size=5120, num_attention_heads=40, inner_hidden_size=13824, text_dim=4096, time_freq_dim=256, time_embed_dim=5120)
+
+
+def _time(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def _summ(ts):
+    return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
+
+
+def ab(arms, reps, warmup=2):
+    """arms: {name: fn}; runs warmup rounds, then `reps` rounds alternating the arms; returns {name: [ms]}"""
+    for _ in range(warmup):
+        for fn in arms.values():
+            fn()
+    torch.cuda.synchronize()
+    out = {k: [] for k in arms}
+    for _ in range(reps):
+        for k, fn in arms.items():
+            out[k].append(_time(fn))
+    return out
+
+
+def gemm_leg(reps, dev):
+    res = []
+    g = torch.Generator(device=dev).manual_seed(0)
+    for N, K in SHAPES:
+        x = torch.randn(M14B, K, device=dev, generator=g).to(torch.bfloat16)
+        w = (torch.randn(N, K, device=dev, generator=g) * 0.02).to(torch.bfloat16)
+        b = torch.randn(N, device=dev, generator=g)
+        y = torch.empty(M14B, N, device=dev, dtype=torch.bfloat16)
+        xq, sx = ops.quant_fp8_rows(x)
+        wq, sw = ops.quant_fp8_rows(w)
+        ts = ab({"bf16": lambda: ops.gemm(x, w, b, out=y), "fp8": lambda: ops.gemm_fp8(xq, sx, wq, sw, b, out=y),
+                 "quant": lambda: ops.quant_fp8_rows(x, out=xq, scale=sx)}, reps)
+        flop = 2.0 * M14B * N * K
+        r = {"N": N, "K": K, "M": M14B, "kernel_bf16": L.load().scail_gemm_kernel_for(K, N, 0, M14B, N, K, 0)}
+        for k in ("bf16", "fp8"):
+            s = _summ(ts[k])
+            r[k] = dict(s, tflops=flop / s["median_ms"] / 1e9, tflops_range=[flop / s["max_ms"] / 1e9, flop / s["min_ms"] / 1e9])
+        r["fp8"]["frac_mxfp8_peak"] = r["fp8"]["tflops"] / PEAK_FP8_TF
+        r["fp8_over_gemm4"] = r["bf16"]["median_ms"] / r["fp8"]["median_ms"]
+        qs = _summ(ts["quant"])
+        r["quant"] = dict(qs, gbps=(M14B * K * 3 + M14B * 4) / qs["median_ms"] / 1e6)
+        print(f"GEMM {N:5d} x {K:5d} (M {M14B}): bf16 {r['bf16']['tflops']:7.1f} TF ({r['bf16']['median_ms']:.3f} ms), "
+              f"fp8 {r['fp8']['tflops']:7.1f} TF ({r['fp8']['median_ms']:.3f} ms, {100 * r['fp8']['frac_mxfp8_peak']:.1f} % of 5 PF), "
+              f"fp8 / gemm4 {r['fp8_over_gemm4']:.3f}x;  quant of x {r['quant']['gbps']:.0f} GB/s ({qs['median_ms']:.3f} ms)", flush=True)
+        res.append(r)
+        del x, w, y, xq, wq
+        torch.cuda.empty_cache()
+    return res
+
+
+def step_leg(reps, layers, mask, dev):
+    from scail_amd.cstep import CStep
+    from scail_amd.dit import DiffusionTransformer
+    from scail_amd.sampler import make_flow_timesteps
+    T, H, W, Lt, Lc = 21, 64, 112, 512, 257
+    net = DiffusionTransformer(transformer_args=dict(model_parallel_size=1), num_frames=81, latent_width=300, latent_height=300,
+                               share_adaln=True, use_i2v_clip=True, device=dev, init_seed=1234, num_layers=layers, **P14B)
+    g = torch.Generator().manual_seed(1234)
+    x = torch.randn(1, T, 16, H, W, generator=g).to(dev)
+    ref = torch.randn(1, 1, 16, H, W, generator=g).to(dev).to(torch.bfloat16)
+    pose = torch.randn(1, T, 16, H // 2, W // 2, generator=g).to(dev).to(torch.bfloat16)
+    ctx = torch.randn(2, Lt, P14B["text_dim"], generator=g).to(dev).to(torch.bfloat16)
+    clip = torch.randn(1, Lc, 1280, generator=g).to(dev).to(torch.bfloat16)
+    sig = make_flow_timesteps(0, 50, shift_scale=5, mode="normal")
+    t = (sig[10] * 1000.0).repeat(2).to(dev)
+    xin = torch.cat([x, x], 0)
+    dummy = torch.zeros(1, device=dev)
+    net._cstep = CStep(net, net.prepare())
+    state = {}
+
+    def run(mode):
+        if state.get("mode") != mode:
+            net._cstep.enable_fp8(mask if mode == "fp8" else 0, dev)
+            torch.cuda.synchronize()
+            state["mode"] = mode
+        return net.forward_f32(xin, t, ctx, None, concat_images=dummy, ref_concat=ref, concat_smpl_render=pose, image_clip_features=clip,
+                               cfg_pair=True)
+
+    outs = {m: run(m).float() for m in ("bf16", "fp8")}
+    cos = float(torch.nn.functional.cosine_similarity(outs["bf16"].flatten().double(), outs["fp8"].flatten().double(), dim=0))
+    ts = ab({"bf16": lambda: run("bf16"), "fp8": lambda: run("fp8")}, reps, warmup=1)
+    r = {"layers": layers, "mask": mask, "L": (1 + T) * (H // 2) * (W // 2) + T * (H // 4) * (W // 4), "cosine_fp8_vs_bf16": cos}
+    for k in ("bf16", "fp8"):
+        r[k] = _summ(ts[k])
+    r["speedup"] = r["bf16"]["median_ms"] / r["fp8"]["median_ms"]
+    # per-category kernel time of one step of each arm (the executor's own event pairs)
+    for mode in ("bf16", "fp8"):
+        run(mode)
+        torch.cuda.synchronize()
+        net._cstep.profile(True)
+        run(mode)
+        torch.cuda.synchronize()
+        r[mode]["gemm_ms"] = net._cstep.profile_read(CStep.PROF_GEMM)[0]
+        net._cstep.profile(False)
+    print(f"config-2 step ({layers} layers, mask {mask}): bf16 {r['bf16']['median_ms']:.1f} ms [{r['bf16']['min_ms']:.1f}, {r['bf16']['max_ms']:.1f}]"
+          f" (GEMMs {r['bf16']['gemm_ms']:.1f}), fp8 {r['fp8']['median_ms']:.1f} ms [{r['fp8']['min_ms']:.1f}, {r['fp8']['max_ms']:.1f}] "
+          f"(GEMMs + quant {r['fp8']['gemm_ms']:.1f}); speedup {r['speedup']:.3f}x; output cosine fp8 vs bf16 {cos:.6f}", flush=True)
+    net._cstep.close()
+    return r
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--step-reps", type=int, default=4)
+    ap.add_argument("--layers", type=int, default=40)
+    ap.add_argument("--mask", type=int, default=L.FP8_ALL)
+    ap.add_argument("--no-gemm", action="store_true")
+    ap.add_argument("--no-step", action="store_true")
+    a = ap.parse_args()
+    dev = "cuda"
+    L.load()
+    out = {"device": torch.cuda.get_device_name(0)}
+    if not a.no_gemm:
+        out["gemm"] = gemm_leg(a.reps, dev)
+    if not a.no_step:
+        out["step"] = step_leg(a.step_reps, a.layers, a.mask, dev)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
