@@ -73,7 +73,7 @@ typedef struct scail_dit scail_dit;
 int scail_dit_create(const scail_dit_config* cfg, const scail_dit_weights* w, scail_dit** out);
 void scail_dit_destroy(scail_dit* h);
 
-/* Bytes of caller-provided device workspace one step needs for a (B, T, H, W) latent batch. */
+/* Bytes of caller-provided device workspace one step needs for a (B, T, H, W) latent batch (-1: bad handle / shape). */
 int64_t scail_dit_workspace_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W);
 
 /*
@@ -94,6 +94,38 @@ int scail_dit_step(scail_dit* h, const float* x, const float* timesteps, const s
                    const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose,
                    const float* rope_cos, const float* rope_sin, float* out,
                    int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes, void* stream);
+
+/*
+ * ---- more than one character (an EXTENSION, BASELINE config 5: the reference has one reference frame and one pose stream, dit...:1559) ----
+ * Naming scheme: every network-level entry point NAME has a form NAME_chars (scail_dit_X_workspace_bytes -> scail_dit_X_chars_workspace_bytes)
+ * that takes the character count n_char = C in 1..64 -- and, where a pose tensor is passed, its frame count pose_frames -- right after the
+ * pose arguments (the workspace queries: last).  The entry points without the suffix ARE the n_char == 1 forms: they forward with
+ * n_char = 1, pose_frames = T and keep their single-character kernel (scail_patchify), results and signatures.
+ *   ref  bf16 [n_ref, C, 16, H, W];  pose bf16 [n_pose, pose_frames = C*T, 16, H/2, W/2] (character k = frames kT .. (k+1)T - 1)
+ *   tokens  [ref_0 .. ref_{C-1} | noise | pose_0 .. pose_{C-1}]:  Lref = C (H/2)(W/2), Lnoise = T (H/2)(W/2), Lpose = C T (H/4)(W/4),
+ *           Ltok = Lref + Lnoise + Lpose; the noise rows are [Lref, Lref + Lnoise).  Assembled by ONE scail_patchify_chars launch.
+ *   rope_cos / rope_sin fp32 [Ltok, 64] from the host in that token order (scail_amd/rope.py build_tables(n_char = C): character k takes RoPE
+ *           windows the reference leaves unused).
+ * Everything that is a row window follows these lengths: patch_w embeds the ref + noise rows and pose_w the pose rows, the last layer runs
+ * past its K / V on the noise rows only, the final layer reads the noise rows.  SCAIL_DIT_CFG_PAIR has the same precondition as for C == 1
+ * (B == 2, n_ref == n_pose == 1, equal latents and timesteps).  The fp8 GEMMs work on the single-rank calls; the sequence-parallel calls
+ * refuse them as before.  A sequence-parallel rank's slab holds its H- or W-window of EVERY character's reference frame and pose stream (ref
+ * and pose sliced like the latent), so its token rows are the layout above for the slab: the exchange layouts do not change.
+ * Checked before anything is enqueued, with an error that names the value: n_char outside 1..64, pose_frames != n_char * T, and
+ * ranks * Ltok >= 2^31 - 64 (the attention launch takes ceil64(keys) < 2^31).
+ * Kernel choice of the self-attention at large Ltok: the 4-wave kernel scail_attn4_m16f addresses each operand with 32-bit byte offsets,
+ * rows * row stride < 2^30 elements; beyond that the launch runs the about 2x slower 8-wave kernel, with the same result.  With D = 5120:
+ *   one rank   (q, k rows of the fused [Ltok, 3D] projection)  Ltok < 69 906: config 5 (C = 2, L = 60 032) fits; C = 3 at the same latent
+ *              (L = 71 232) runs the 8-wave kernel
+ *   all-gather (keys: the gathered [ranks * Ltok, 2D] rows)    ranks * Ltok = full L < 104 858, and Ltok < 69 906 per rank
+ *   ulysses    (q, k rows of [ranks * Ltok, 3D / ranks])       Ltok < 69 906 per rank, i.e. full L < ranks * 69 906
+ * (scail_flash_attn_kernel_for answers for a given launch.)
+ */
+int64_t scail_dit_chars_workspace_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W, int64_t n_char);
+int scail_dit_step_chars(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
+                         const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
+                         const float* rope_cos, const float* rope_sin, float* out,
+                         int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes, void* stream);
 
 /*
  * Seam B2 (the SAT hook `layer_forward`, dit...:1009-1051): ONE transformer block, in place on caller-owned hidden states
@@ -167,6 +199,15 @@ int scail_dit_step_sp(scail_dit* h, const float* x, const float* timesteps, cons
                       int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace, int64_t workspace_bytes,
                       void* stream);
 
+/* scail_dit_step_sp for n_char characters ("more than one character" above). */
+int64_t scail_dit_sp_chars_workspace_bytes(const scail_dit* h, int32_t mode, int32_t ranks, int64_t B, int64_t T, int64_t H, int64_t W,
+                                           int64_t n_char);
+int scail_dit_step_sp_chars(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
+                            const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
+                            const float* rope_cos, const float* rope_sin, float* out,
+                            int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace,
+                            int64_t workspace_bytes, void* stream);
+
 /* Seam B2 for a sequence-parallel rank: ONE transformer block in place on this rank's hidden [B, Ltok, D] (scail_dit_block + the exchange). */
 int64_t scail_dit_block_sp_workspace_bytes(const scail_dit* h, int32_t mode, int32_t ranks, int64_t B, int64_t Ltok);
 int scail_dit_block_sp(scail_dit* h, int64_t layer, scail_bf16* hidden, const float* mod, const scail_dit_cond* cond,
@@ -231,6 +272,12 @@ int scail_dit_sample(scail_dit* h, float* x, const float* timesteps, const float
                      const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose,
                      const float* rope_cos, const float* rope_sin, int64_t T, int64_t H, int64_t W,
                      void* workspace, int64_t workspace_bytes, void* stream);
+/* The same loop for n_char characters: ref [1, n_char, 16, H, W], pose [1, pose_frames = n_char * T, 16, H/2, W/2]. */
+int64_t scail_dit_sample_chars_workspace_bytes(const scail_dit* h, int64_t T, int64_t H, int64_t W, int64_t n_char);
+int scail_dit_sample_chars(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                           const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose, int64_t n_char, int64_t pose_frames,
+                           const float* rope_cos, const float* rope_sin, int64_t T, int64_t H, int64_t W,
+                           void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

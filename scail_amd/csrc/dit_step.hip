@@ -58,10 +58,45 @@ int64_t vt_elems(const scail_dit_config& c, int64_t B, int64_t Ltok, int sp_mode
 }
 
 // f8_k: the widest K of the GEMMs that run in fp8 (0: none) -- the e4m3 copy of a GEMM's input rows and their scales (xq, sx)
-Ws layout(const scail_dit_config& c, int64_t B, int64_t T, int64_t H, int64_t W, int sp_mode = -1, int64_t ranks = 1, int64_t f8_k = 0) {
-    const int64_t D = c.hidden_size, FF = c.inner_hidden_size;
+// Token counts of a (T, H, W) latent (or latent slab) with C characters: [ref_0..ref_{C-1} | noise | pose_0..pose_{C-1}]
+struct TokLens {
+    int64_t Lref, Lnoise, Lpose, Ltok;
+};
+TokLens tok_lens(int64_t C, int64_t T, int64_t H, int64_t W) {
     const int64_t hp = H / 2, wp = W / 2;
-    const int64_t Lnoise = T * hp * wp, Ltok = hp * wp + Lnoise + T * (H / 4) * (W / 4);
+    TokLens l;
+    l.Lref = C * hp * wp;
+    l.Lnoise = T * hp * wp;
+    l.Lpose = C * T * (H / 4) * (W / 4);
+    l.Ltok = l.Lref + l.Lnoise + l.Lpose;
+    return l;
+}
+// the self-attention launch takes ceil64(keys) < 2^31 (scail_flash_attn_bf16); a sequence-parallel rank attends to all ranks' keys
+constexpr int64_t MAX_KEYS = (1ll << 31) - 64;
+bool shape_ok(int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, int64_t ranks) {
+    if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0 || C < 1 || C > 64 || ranks < 1) return false;
+    if (T >= (1 << 15) || H >= (1 << 15) || W >= (1 << 15)) return false;      // (keeps the products below in 64 bits)
+    return ranks * tok_lens(C, T, H, W).Ltok < MAX_KEYS;
+}
+
+// the character arguments of the *_chars entry points, checked first (host only; the message names the value)
+int chars_check(const char* who, int64_t n_char, int64_t pose_frames, int64_t T) {
+    if (n_char < 1 || n_char > 64) {
+        scail_set_error(std::string(who) + ": n_char must be 1..64, got " + std::to_string(n_char));
+        return 1;
+    }
+    if (pose_frames != n_char * T) {
+        scail_set_error(std::string(who) + ": pose must hold n_char * T = " + std::to_string(n_char) + " * " + std::to_string(T) + " frames, got " +
+                        std::to_string(pose_frames));
+        return 1;
+    }
+    return 0;
+}
+
+Ws layout(const scail_dit_config& c, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, int sp_mode = -1, int64_t ranks = 1, int64_t f8_k = 0) {
+    const int64_t D = c.hidden_size, FF = c.inner_hidden_size;
+    const TokLens tl = tok_lens(C, T, H, W);
+    const int64_t Lnoise = tl.Lnoise, Ltok = tl.Ltok;
     Ws s;
     int64_t off = 0;
     auto take = [&](int64_t bytes) { const int64_t o = off; off += align256(bytes); return o; };
@@ -648,65 +683,100 @@ extern "C" int scail_dit_profile_read(scail_dit* h, int category, double* ms_tot
     return 0;
 }
 
-extern "C" int64_t scail_dit_workspace_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W) {
-    if (h == nullptr || B <= 0 || T <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0) return -1;
-    return layout(h->cfg, B, T, H, W, -1, 1, fp8_k(h)).total;
+// The *_chars entry points take the character count; the entry points without it are their n_char == 1 form.
+extern "C" int64_t scail_dit_chars_workspace_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W, int64_t n_char) {
+    if (h == nullptr || !shape_ok(B, T, H, W, n_char, 1)) return -1;
+    return layout(h->cfg, B, T, H, W, n_char, -1, 1, fp8_k(h)).total;
 }
-extern "C" int64_t scail_dit_sp_workspace_bytes(const scail_dit* h, int32_t mode, int32_t ranks, int64_t B, int64_t T, int64_t H, int64_t W) {
-    if (h == nullptr || B <= 0 || T <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0 || ranks < 2) return -1;
+extern "C" int64_t scail_dit_workspace_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W) {
+    return scail_dit_chars_workspace_bytes(h, B, T, H, W, 1);
+}
+extern "C" int64_t scail_dit_sp_chars_workspace_bytes(const scail_dit* h, int32_t mode, int32_t ranks, int64_t B, int64_t T, int64_t H, int64_t W,
+                                                      int64_t n_char) {
+    if (h == nullptr || ranks < 2 || !shape_ok(B, T, H, W, n_char, ranks)) return -1;
     if (mode != SCAIL_SP_ALLGATHER && mode != SCAIL_SP_ULYSSES) return -1;
     if (mode == SCAIL_SP_ULYSSES && h->cfg.num_heads % ranks != 0) return -1;
-    return layout(h->cfg, B, T, H, W, mode, ranks).total;
+    return layout(h->cfg, B, T, H, W, n_char, mode, ranks).total;
+}
+extern "C" int64_t scail_dit_sp_workspace_bytes(const scail_dit* h, int32_t mode, int32_t ranks, int64_t B, int64_t T, int64_t H, int64_t W) {
+    return scail_dit_sp_chars_workspace_bytes(h, mode, ranks, B, T, H, W, 1);
 }
 
 static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
-                         const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose,
+                         const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
                          const float* rope_cos, const float* rope_sin, float* out,
                          int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+extern "C" int scail_dit_step_chars(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
+                                    const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
+                                    const float* rope_cos, const float* rope_sin, float* out,
+                                    int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes,
+                                    void* stream) {
+    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, n_char, pose_frames, rope_cos, rope_sin, out, B, T, H, W, nullptr, flags,
+                         workspace, workspace_bytes, stream);
+}
 extern "C" int scail_dit_step(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
                               const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose,
                               const float* rope_cos, const float* rope_sin, float* out,
                               int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes,
                               void* stream) {
-    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, rope_cos, rope_sin, out, B, T, H, W, nullptr, flags, workspace, workspace_bytes, stream);
+    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, 1, T, rope_cos, rope_sin, out, B, T, H, W, nullptr, flags, workspace,
+                         workspace_bytes, stream);
 }
 
+extern "C" int scail_dit_step_sp_chars(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
+                                       const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char,
+                                       int64_t pose_frames, const float* rope_cos, const float* rope_sin, float* out,
+                                       int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+    SCAIL_REQUIRE(h != nullptr, "null handle");
+    DIT_TRY(sp_check(h, sp));
+    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, n_char, pose_frames, rope_cos, rope_sin, out, B, T, H, W, sp, flags,
+                         workspace, workspace_bytes, stream);
+}
 extern "C" int scail_dit_step_sp(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
                                  const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose,
                                  const float* rope_cos, const float* rope_sin, float* out,
                                  int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace,
                                  int64_t workspace_bytes, void* stream) {
-    SCAIL_REQUIRE(h != nullptr, "null handle");
-    DIT_TRY(sp_check(h, sp));
-    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, rope_cos, rope_sin, out, B, T, H, W, sp, flags, workspace, workspace_bytes, stream);
+    return scail_dit_step_sp_chars(h, x, timesteps, cond, ref, n_ref, pose, n_pose, 1, T, rope_cos, rope_sin, out, B, T, H, W, sp, flags, workspace,
+                                   workspace_bytes, stream);
 }
 
-// x (B, T, 16, H, W): the whole latent (sp == nullptr) or this rank's H- or W-slab of it (rope tables rank-shifted by the host)
+// x (B, T, 16, H, W): the whole latent (sp == nullptr) or this rank's H- or W-slab of it (rope tables rank-shifted by the host).
+// n_char characters: ref (n_ref, n_char, 16, H, W), pose (n_pose, pose_frames = n_char * T, 16, H/2, W/2); a rank's slab holds its H- or
+// W-window of EVERY character's reference frame and pose stream, so its token rows are [ref_0..ref_{C-1} | noise | pose_0..pose_{C-1}] of
+// the slab, as on one rank (scail_amd/parallel.py chunks ref and pose like the latent).
 static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
-                         const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose,
+                         const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
                          const float* rope_cos, const float* rope_sin, float* out,
                          int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace, int64_t workspace_bytes,
                          void* stream) {
+    DIT_TRY(chars_check("scail_dit_step", n_char, pose_frames, T));
     SCAIL_REQUIRE(h != nullptr && cond != nullptr, "null handle / conditioning");
     SCAIL_REQUIRE((flags & ~(uint32_t)SCAIL_DIT_CFG_PAIR) == 0, "unknown step flag");
     SCAIL_REQUIRE(!(flags & SCAIL_DIT_CFG_PAIR) || (B == 2 && n_ref == 1 && n_pose == 1),
                   "SCAIL_DIT_CFG_PAIR needs B == 2 with one shared ref / pose (element 1 = element 0 except for the conditioning)");
     SCAIL_REQUIRE(B > 0 && B <= 8 && T > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, "latent batch must be 1..8, H and W multiples of 4");
+    const int64_t ranks = sp ? sp->ranks : 1;
+    if (!shape_ok(B, T, H, W, n_char, ranks)) {
+        scail_set_error("scail_dit_step: the self-attention takes fewer than 2^31 - 64 keys, got Ltok = " + std::to_string(tok_lens(n_char, T, H, W).Ltok) +
+                        " tokens x " + std::to_string(ranks) + " rank(s) (T, H, W must be below 32768)");
+        return 1;
+    }
     SCAIL_REQUIRE((n_ref == 1 || n_ref == B) && (n_pose == 1 || n_pose == B), "ref / pose batch must be 1 or B");
     SCAIL_REQUIRE(cond->Bc == 1 || cond->Bc == B, "clip batch must be 1 or B");
     const scail_dit_config& c = h->cfg;
-    const Ws s = sp ? layout(c, B, T, H, W, sp->mode, sp->ranks) : layout(c, B, T, H, W, -1, 1, fp8_k(h));
+    const Ws s = sp ? layout(c, B, T, H, W, n_char, sp->mode, sp->ranks) : layout(c, B, T, H, W, n_char, -1, 1, fp8_k(h));
     SCAIL_REQUIRE(c.time_embed_dim == c.hidden_size, "final-layer table add needs time_embed_dim == hidden_size");
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= s.total, "workspace too small (scail_dit_workspace_bytes)");
     SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
 
     const int64_t D = c.hidden_size, nl = c.num_layers;
     const float eps = c.layernorm_epsilon;
-    const int64_t hp = H / 2, wp = W / 2;
-    const int64_t Lref = hp * wp, Lnoise = T * hp * wp, Lpose = T * (H / 4) * (W / 4);
-    const int64_t Ltok = Lref + Lnoise + Lpose, Lrn = Lref + Lnoise;
+    const TokLens tl = tok_lens(n_char, T, H, W);
+    const int64_t Lref = tl.Lref, Lnoise = tl.Lnoise, Lpose = tl.Lpose, Ltok = tl.Ltok, Lrn = Lref + Lnoise;   // noise rows: [Lref, Lrn)
     char* base = static_cast<char*>(workspace);
     auto B16 = [&](int64_t off) { return reinterpret_cast<scail_bf16*>(base + off); };
     auto F32 = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
@@ -729,12 +799,16 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
     }
     DIT_TRY(scail_adaln_table(emb2, w.final_table, fin, 1, B, 2 * D, stream));
 
-    // ---- patch embedding straight into the token layout [ref | noise | pose] (dit...:99-130) ----
+    // ---- patch embedding straight into the token layout [ref_0.. | noise | pose_0..] (dit...:99-130) ----
     // SCAIL_DIT_CFG_PAIR: the two elements are one latent under two conditionings (VanillaCFG, guiders.py:41-57) and stay equal until the
     // first cross attention of layer 0 (dit...:1009-1042): patch embedding and layer 0 up to the self-attention residual run once
     const bool pair = (flags & SCAIL_DIT_CFG_PAIR) != 0 && nl > 1;
     const int64_t Be = pair ? 1 : B;
-    DIT_TRY(scail_patchify(x, ref, pose, tok, Be, n_ref, n_pose, T, H, W, KPAD, stream));
+    if (n_char == 1) {
+        DIT_TRY(scail_patchify(x, ref, pose, tok, Be, n_ref, n_pose, T, H, W, KPAD, stream));
+    } else {
+        DIT_TRY(scail_patchify_chars(x, ref, pose, tok, Be, n_ref, n_pose, n_char, T, H, W, KPAD, stream));
+    }
     for (int64_t b = 0; b < Be; ++b) {
         DIT_TRY(scail_gemm_bf16(tok + b * Ltok * KPAD, KPAD, w.patch_w, w.patch_b, hid + b * Ltok * D, D, Lrn, D, KPAD,
                                 SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
@@ -767,19 +841,31 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
 }
 
 // ---- the sampler loop (RFSampler.__call__ + VanillaCFG, sampling.py:920-982, guiders.py:41-57) ----
-extern "C" int64_t scail_dit_sample_workspace_bytes(const scail_dit* h, int64_t T, int64_t H, int64_t W) {
-    const int64_t step = scail_dit_workspace_bytes(h, 2, T, H, W);
+extern "C" int64_t scail_dit_sample_chars_workspace_bytes(const scail_dit* h, int64_t T, int64_t H, int64_t W, int64_t n_char) {
+    const int64_t step = scail_dit_chars_workspace_bytes(h, 2, T, H, W, n_char);
     if (step < 0) return -1;
     const int64_t n = T * 16 * H * W;
     return step + 2 * align256(2 * n * 4);     // + [x; x] and [v_u; v_c], fp32
+}
+extern "C" int64_t scail_dit_sample_workspace_bytes(const scail_dit* h, int64_t T, int64_t H, int64_t W) {
+    return scail_dit_sample_chars_workspace_bytes(h, T, H, W, 1);
 }
 
 extern "C" int scail_dit_sample(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps,
                                 float cfg_scale, const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose,
                                 const float* rope_cos, const float* rope_sin, int64_t T, int64_t H, int64_t W,
                                 void* workspace, int64_t workspace_bytes, void* stream) {
+    return scail_dit_sample_chars(h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose, 1, T, rope_cos, rope_sin, T, H, W, workspace,
+                                  workspace_bytes, stream);
+}
+
+extern "C" int scail_dit_sample_chars(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps,
+                                      float cfg_scale, const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose,
+                                      int64_t n_char, int64_t pose_frames, const float* rope_cos, const float* rope_sin,
+                                      int64_t T, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes, void* stream) {
+    DIT_TRY(chars_check("scail_dit_sample", n_char, pose_frames, T));
     SCAIL_REQUIRE(h != nullptr && x != nullptr && timesteps != nullptr && dsigma != nullptr && n_steps >= 0, "null argument");
-    const int64_t step_bytes = scail_dit_workspace_bytes(h, 2, T, H, W);
+    const int64_t step_bytes = scail_dit_chars_workspace_bytes(h, 2, T, H, W, n_char);
     SCAIL_REQUIRE(step_bytes >= 0, "bad latent shape");
     const int64_t n = T * 16 * H * W, pair = align256(2 * n * 4);
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= step_bytes + 2 * pair, "workspace too small (scail_dit_sample_workspace_bytes)");
@@ -794,8 +880,8 @@ extern "C" int scail_dit_sample(scail_dit* h, float* x, const float* timesteps, 
             scail_set_error("scail_dit_sample: hipMemcpyAsync failed");
             return 2;
         }
-        DIT_TRY(scail_dit_step(h, xin, timesteps + 2 * i, cond, ref, 1, pose, 1, rope_cos, rope_sin, v, 2, T, H, W, SCAIL_DIT_CFG_PAIR, workspace,
-                               step_bytes, stream));
+        DIT_TRY(scail_dit_step_chars(h, xin, timesteps + 2 * i, cond, ref, 1, pose, 1, n_char, pose_frames, rope_cos, rope_sin, v, 2, T, H, W,
+                                     SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream));
         DIT_TRY(scail_cfg_euler(x, v, n, cfg_scale, dsigma[i], stream));
     }
     return 0;

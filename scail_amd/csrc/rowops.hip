@@ -454,6 +454,71 @@ __global__ void patchify_kernel(const float* __restrict__ x, const u16* __restri
     *reinterpret_cast<uint4*>(tok + row * kpad + ch * 8) = pack8(o);
 }
 
+// Multi-character token assembly: the whole im2col matrix [ref_0..ref_{C-1} | noise | pose_0..pose_{C-1}] in one launch.
+// One thread per (token, 8-column chunk), chunks of a token on consecutive lanes: a wave stores 1 KiB of contiguous destination rows
+// (16 bytes per lane), the larger of the two streams.  A chunk is two channels x the 2x2 patch; its four (channel, patch row) pairs
+// are contiguous in the source and are read as one 4-byte (bf16) / 8-byte (fp32) access each, lanes 16 apart (the next token of a
+// character's plane) continuing the same source line.  Chunks 8 and 9 are the constant mask channels, the rest of kpad is zero:
+// neither reads anything.  Every source element is read once; with n_char == 1 the result is patchify_kernel's.
+__global__ void patchify_chars_kernel(const float* __restrict__ x, const u16* __restrict__ ref, const u16* __restrict__ pose,
+                                      u16* __restrict__ tok, int64_t n_ref, int64_t n_pose, int n_char, int T, int H, int W, int kpad,
+                                      int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int cpr = kpad >> 3;
+    const int ch = (int)(i % cpr);
+    const int64_t row = i / cpr;
+    const int h2 = H >> 1, w2 = W >> 1, h4 = H >> 2, w4 = W >> 2;
+    const int64_t Lref1 = (int64_t)h2 * w2, Lnoise = (int64_t)T * h2 * w2, Lpose1 = (int64_t)T * h4 * w4;
+    const int64_t Lref = n_char * Lref1, L = Lref + Lnoise + n_char * Lpose1;
+    const int64_t b = row / L;
+    const int64_t l = row - b * L;
+    const bool noise = l >= Lref && l < Lref + Lnoise;
+    float o[8];
+    if (ch >= 8) {                  // mask channels 16..19 (1 on ref / pose tokens, 0 on noise tokens), then the zero padding
+        const float m = (ch < 10 && !noise) ? 1.f : 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = m;
+    } else if (noise) {
+        const int64_t ll = l - Lref;
+        const int t = (int)(ll / Lref1), rem = (int)(ll % Lref1);
+        const int hh = rem / w2, ww = rem % w2;
+        const float* src = x + (((b * T + t) * 16 + 2 * ch) * H + 2 * hh) * W + 2 * ww;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {       // e = (channel, patch row)
+            const float2 v = *reinterpret_cast<const float2*>(src + ((int64_t)(e >> 1) * H + (e & 1)) * W);
+            o[2 * e] = v.x;
+            o[2 * e + 1] = v.y;
+        }
+    } else {
+        const u16* src;
+        int64_t plane, line;                // elements between two channels / two patch rows
+        if (l < Lref) {
+            const int k = (int)(l / Lref1), rem = (int)(l % Lref1);
+            const int hh = rem / w2, ww = rem % w2;
+            const int64_t bb = (n_ref == 1) ? 0 : b;
+            plane = (int64_t)H * W, line = W;
+            src = ref + (((bb * n_char + k) * 16 + 2 * ch) * H + 2 * hh) * W + 2 * ww;
+        } else {
+            const int64_t ll = l - Lref - Lnoise;
+            const int k = (int)(ll / Lpose1);
+            const int64_t rem1 = ll % Lpose1;
+            const int t = (int)(rem1 / (h4 * w4)), rem = (int)(rem1 % (h4 * w4));
+            const int hh = rem / w4, ww = rem % w4;
+            const int64_t bb = (n_pose == 1) ? 0 : b;
+            plane = (int64_t)h2 * w2, line = w2;
+            src = pose + ((((bb * n_char + k) * T + t) * 16 + 2 * ch) * h2 + 2 * hh) * w2 + 2 * ww;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t v = *reinterpret_cast<const uint32_t*>(src + (e >> 1) * plane + (e & 1) * line);
+            o[2 * e] = bf_lo(v);
+            o[2 * e + 1] = bf_hi(v);
+        }
+    }
+    *reinterpret_cast<uint4*>(tok + row * kpad + ch * 8) = pack8(o);
+}
+
 // out[b][t][c][2h+p][2w+q] = tok[b][(t,h,w)][p*32 + q*16 + c]
 __global__ void unpatchify_kernel(const u16* __restrict__ tok, float* __restrict__ out, int T, int H,
                                   int W, int64_t total) {
@@ -703,6 +768,30 @@ extern "C" int scail_patchify(const float* x, const scail_bf16* ref, const scail
                        (hipStream_t)stream, x, ref, pose, tok, n_batch, n_ref, n_pose, (int)T, (int)H, (int)W,
                        (int)kpad, total);
     return scail_check_launch("patchify");
+}
+
+extern "C" int scail_patchify_chars(const float* x, const scail_bf16* ref, const scail_bf16* pose, scail_bf16* tok, int64_t n_batch,
+                                    int64_t n_ref, int64_t n_pose, int64_t n_char, int64_t T, int64_t H, int64_t W, int64_t kpad,
+                                    void* stream) {
+    if (n_char < 1 || n_char > 64) {
+        scail_set_error("scail_patchify_chars: n_char must be 1..64, got " + std::to_string(n_char));
+        return 1;
+    }
+    SCAIL_REQUIRE(n_batch >= 0 && T >= 0 && H >= 0 && W >= 0 && H < (1 << 15) && W < (1 << 15) && T < (1 << 15), "bad shape");
+    SCAIL_REQUIRE(H % 4 == 0 && W % 4 == 0, "latent H and W must be multiples of 4 (pose is half size, patch 2)");
+    SCAIL_REQUIRE(kpad >= 80 && kpad % 8 == 0, "kpad must be >= 80 and a multiple of 8");
+    SCAIL_REQUIRE((n_ref == 1 || n_ref == n_batch) && (n_pose == 1 || n_pose == n_batch), "cond batch must be 1 or n_batch");
+    // the kernel reads pairs of neighbouring elements in one access and stores 16 bytes per thread
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(x) & 7) == 0 && (reinterpret_cast<uintptr_t>(ref) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(pose) & 3) == 0 && (reinterpret_cast<uintptr_t>(tok) & 15) == 0,
+                  "pointer alignment (x 8, ref / pose 4, tok 16 bytes)");
+    const int64_t L = (n_char + T) * (H / 2) * (W / 2) + n_char * T * (H / 4) * (W / 4);
+    const int64_t total = n_batch * L * (kpad / 8);
+    if (total == 0) return 0;
+    SCAIL_REQUIRE((total + 255) / 256 < (1ll << 31), "token matrix too large for one launch");
+    hipLaunchKernelGGL(patchify_chars_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ref, pose, tok,
+                       n_ref, n_pose, (int)n_char, (int)T, (int)H, (int)W, (int)kpad, total);
+    return scail_check_launch("patchify_chars");
 }
 
 extern "C" int scail_unpatchify(const scail_bf16* tok, float* out, int64_t n_batch, int64_t T, int64_t H,

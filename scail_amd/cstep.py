@@ -122,39 +122,40 @@ class CStep:
         L.call("scail_dit_profile_read", self._h, category, C.byref(ms), C.byref(n))
         return ms.value, n.value
 
-    def workspace_bytes(self, B, T, H, W) -> int:
-        n = L.load().scail_dit_workspace_bytes(self._h, B, T, H, W)
+    def workspace_bytes(self, B, T, H, W, n_char: int = 1) -> int:
+        n = L.load().scail_dit_chars_workspace_bytes(self._h, B, T, H, W, n_char)
         if n < 0:
-            raise L.ScailHipError("scail_dit_workspace_bytes: bad shape")
+            raise L.ScailHipError(f"scail_dit_chars_workspace_bytes: bad shape (B {B}, T {T}, H {H}, W {W}, n_char {n_char})")
         return n
 
     CFG_PAIR = 1                                                  # include/scail_dit.h SCAIL_DIT_CFG_PAIR
 
-    def step(self, x32, t32, cond: Dict, ref, pose, cos, sin, cfg_pair: bool = False) -> torch.Tensor:
+    def step(self, x32, t32, cond: Dict, ref, pose, cos, sin, cfg_pair: bool = False, n_char: int = 1) -> torch.Tensor:
         """``cfg_pair``: the caller states that x32 / t32 hold the same latent and timestep twice (VanillaCFG's batch of 2): layer 0 up to
-        its first cross attention is evaluated once (SCAIL_DIT_CFG_PAIR; bit-identical on such inputs)."""
+        its first cross attention is evaluated once (SCAIL_DIT_CFG_PAIR; bit-identical on such inputs).  ``n_char``: characters in
+        ``ref`` (n, n_char, 16, H, W) / ``pose`` (n, n_char * T, 16, H/2, W/2); cos / sin from rope.build_tables(n_char=n_char)."""
         B, T, _, H, W = x32.shape
-        need = self.workspace_bytes(B, T, H, W)
+        need = self.workspace_bytes(B, T, H, W, n_char)
         if self._ws is None or self._ws.numel() < need or self._ws.device != x32.device:
             self._ws = torch.empty(need, device=x32.device, dtype=torch.uint8)
         k_text, k_clip = cond["k_text"], cond["k_clip"]
         cc = DitCond(k_text.data_ptr(), cond["vt_text"].data_ptr(), k_clip.data_ptr(), cond["vt_clip"].data_ptr(),
                      k_text.shape[2], k_clip.shape[2], k_clip.shape[1])
         out = torch.empty(B, T, 16, H, W, device=x32.device, dtype=torch.float32)
-        L.call("scail_dit_step", self._h, x32.data_ptr(), t32.data_ptr(), C.byref(cc), ref.data_ptr(), ref.shape[0],
-               pose.data_ptr(), pose.shape[0], cos.data_ptr(), sin.data_ptr(), out.data_ptr(), B, T, H, W,
+        L.call("scail_dit_step_chars", self._h, x32.data_ptr(), t32.data_ptr(), C.byref(cc), ref.data_ptr(), ref.shape[0],
+               pose.data_ptr(), pose.shape[0], n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), out.data_ptr(), B, T, H, W,
                self.CFG_PAIR if cfg_pair else 0, self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream().cuda_stream)
         return out
 
-    def sample(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose, cos, sin) -> torch.Tensor:
-        """The whole Euler loop in one C call (scail_dit_sample).  x32 (1,T,16,H,W) fp32 is updated in place and returned;
-        ``sigmas`` is the host schedule (n_steps + 1 values); ``cond`` the batch-2 conditioning (uncond, cond)."""
+    def sample(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose, cos, sin, n_char: int = 1) -> torch.Tensor:
+        """The whole Euler loop in one C call (scail_dit_sample_chars).  x32 (1,T,16,H,W) fp32 is updated in place and returned;
+        ``sigmas`` is the host schedule (n_steps + 1 values); ``cond`` the batch-2 conditioning (uncond, cond); ``n_char`` as for step."""
         import ctypes as C2
         _, T, _, H, W = x32.shape
         lib = L.load()
-        need = lib.scail_dit_sample_workspace_bytes(self._h, T, H, W)
+        need = lib.scail_dit_sample_chars_workspace_bytes(self._h, T, H, W, n_char)
         if need < 0:
-            raise L.ScailHipError("scail_dit_sample_workspace_bytes: bad shape")
+            raise L.ScailHipError(f"scail_dit_sample_chars_workspace_bytes: bad shape (T {T}, H {H}, W {W}, n_char {n_char})")
         if self._ws is None or self._ws.numel() < need or self._ws.device != x32.device:
             self._ws = torch.empty(need, device=x32.device, dtype=torch.uint8)
         sig = sigmas.float().cpu()
@@ -166,8 +167,8 @@ class CStep:
         cc = DitCond(k_text.data_ptr(), cond["vt_text"].data_ptr(), k_clip.data_ptr(), cond["vt_clip"].data_ptr(),
                      k_text.shape[2], k_clip.shape[2], k_clip.shape[1])
         assert x32.is_contiguous() and x32.dtype == torch.float32 and ref.shape[0] == 1 and pose.shape[0] == 1
-        L.call("scail_dit_sample", self._h, x32.data_ptr(), ts.data_ptr(), C2.cast(dsa, C2.c_void_p), n, float(cfg_scale),
-               C2.byref(cc), ref.data_ptr(), pose.data_ptr(), cos.data_ptr(), sin.data_ptr(), T, H, W,
+        L.call("scail_dit_sample_chars", self._h, x32.data_ptr(), ts.data_ptr(), C2.cast(dsa, C2.c_void_p), n, float(cfg_scale),
+               C2.byref(cc), ref.data_ptr(), pose.data_ptr(), n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), T, H, W,
                self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream().cuda_stream)
         return x32
 
@@ -206,15 +207,15 @@ class CStep:
             self._ws = torch.empty(need, device=device, dtype=torch.uint8)
         return self._ws
 
-    def step_sp(self, x32, t32, cond: Dict, ref, pose, cos, sin, xch, cfg_pair: bool = False) -> torch.Tensor:
-        """One network evaluation on this rank's latent slab (scail_dit_step_sp); ``xch`` owns the exchange buffers and issues the
-        collectives from the executor's callback."""
+    def step_sp(self, x32, t32, cond: Dict, ref, pose, cos, sin, xch, cfg_pair: bool = False, n_char: int = 1) -> torch.Tensor:
+        """One network evaluation on this rank's latent slab (scail_dit_step_sp_chars); ``xch`` owns the exchange buffers and issues the
+        collectives from the executor's callback.  ``ref`` / ``pose`` are the rank's slabs of all ``n_char`` characters."""
         B, T, _, H, W = x32.shape
-        ws = self._ws_for(L.load().scail_dit_sp_workspace_bytes(self._h, xch.mode_code, xch.size, B, T, H, W), x32.device)
+        ws = self._ws_for(L.load().scail_dit_sp_chars_workspace_bytes(self._h, xch.mode_code, xch.size, B, T, H, W, n_char), x32.device)
         cc, sp = _cond_struct(cond), xch.descriptor()
         out = torch.empty(B, T, 16, H, W, device=x32.device, dtype=torch.float32)
-        self._sp_call("scail_dit_step_sp", xch, self._h, x32.data_ptr(), t32.data_ptr(), C.byref(cc), ref.data_ptr(), ref.shape[0],
-                      pose.data_ptr(), pose.shape[0], cos.data_ptr(), sin.data_ptr(), out.data_ptr(), B, T, H, W, C.byref(sp),
+        self._sp_call("scail_dit_step_sp_chars", xch, self._h, x32.data_ptr(), t32.data_ptr(), C.byref(cc), ref.data_ptr(), ref.shape[0],
+                      pose.data_ptr(), pose.shape[0], n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), out.data_ptr(), B, T, H, W, C.byref(sp),
                       self.CFG_PAIR if cfg_pair else 0, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
         return out
 

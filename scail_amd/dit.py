@@ -163,7 +163,7 @@ class DiffusionTransformer(nn.Module):
         # one C call per network evaluation (include/scail_dit.h) instead of ~25 ctypes calls per layer; env override
         self.use_c_step = os.environ.get("SCAIL_C_STEP", "1") != "0"
         self._cstep = None
-        self._c_blocks = False             # test hook: drive the executor block by block (scail_dit_block) as the multi-character path does
+        self._c_blocks = False             # test hook: drive the executor block by block (scail_dit_block per layer, the rest from the host): cross-check of the one-call step
 
     # ------------------------------------------------------------------------------------------
     # parameters (reference names / shapes)
@@ -394,7 +394,7 @@ class DiffusionTransformer(nn.Module):
         return self._rope_cache[key]
 
     def _workspace(self, B, Ltok, Lnoise, device, blocks_in_c=False):
-        """Activation scratch of the per-op path.  blocks_in_c (multi-character extension: every block is one executor call with the
+        """Activation scratch of the per-op path.  blocks_in_c (the _c_blocks cross-check: every block is one executor call with the
         executor's own block workspace): only the buffers the host-side assembly and the final layer touch."""
         key = (B, Ltok, Lnoise, blocks_in_c)
         ws = self._ws.get(key)
@@ -467,8 +467,9 @@ class DiffusionTransformer(nn.Module):
         return self._run(x32, t32, ctx, ref, pose, clip, H_shift, W_shift, cond_key, cfg_pair=cfg_pair)
 
     def sample_c(self, x32, sigmas, cfg_scale, ctx, ref, pose, clip, cond_key=None):
-        """The whole RFSampler Euler loop as ONE C call (scail_dit_sample, include/scail_dit.h): x32 (1,T,16,H,W) fp32,
-        ctx (2, Lt, text_dim) = [uncond; cond], ref (1,1,16,H,W), pose (1,T,16,H/2,W/2), clip (1,Lc,1280).  Single rank."""
+        """The whole RFSampler Euler loop as ONE C call (scail_dit_sample_chars, include/scail_dit.h): x32 (1,T,16,H,W) fp32,
+        ctx (2, Lt, text_dim) = [uncond; cond], ref (1,C,16,H,W), pose (1,C*T,16,H/2,W/2) for C >= 1 characters (C = ref.shape[1]),
+        clip (1,Lc,1280).  Single rank."""
         from .cstep import CStep
         W = self.prepare()
         dev = x32.device
@@ -478,12 +479,15 @@ class DiffusionTransformer(nn.Module):
             return ops.to_bf16(t.contiguous()) if t.dtype == torch.float32 else t.to(torch.bfloat16).contiguous()
 
         _, T, _, H, Wd = x32.shape
+        n_char = ref.shape[1]
+        if pose.shape[1] != n_char * T:
+            raise L.ScailHipError(f"concat_smpl_render needs {n_char} x {T} frames for {n_char} reference frame(s), got {pose.shape[1]}")
         cond = self._conditioning(as_bf16(ctx), as_bf16(clip), cond_key)
-        cos, sin = self._rope(T, H // 2, Wd // 2, 0, 0, dev)
+        cos, sin = self._rope(T, H // 2, Wd // 2, 0, 0, dev, n_char)
         if self._cstep is None:
             self._cstep = CStep(self, W)
         x = x32.float().contiguous().clone()
-        return self._cstep.sample(x, sigmas, cfg_scale, cond, as_bf16(ref), as_bf16(pose), cos, sin)
+        return self._cstep.sample(x, sigmas, cfg_scale, cond, as_bf16(ref), as_bf16(pose), cos, sin, n_char=n_char)
 
     def _run(self, x32, t32, ctx, ref, pose, clip, H_shift=0, W_shift=0, cond_key=None, cfg_pair=False):
         W = self.prepare()
@@ -513,12 +517,13 @@ class DiffusionTransformer(nn.Module):
             from .cstep import CStep
             self._cstep = CStep(self, W)
         xch = sp.c_exchange(nh, D, B, Ltok, dev) if (use_c and sp is not None) else None
-        if use_c and n_char == 1 and not self._c_blocks:
-            # the whole evaluation as ONE call into the library (include/scail_dit.h); same kernels, same order.  A sequence-parallel
-            # rank runs the same executor: only the collectives of the per-layer exchange come back to the host (xch)
+        if use_c and not self._c_blocks:
+            # the whole evaluation as ONE call into the library (include/scail_dit.h), for any number of characters; same kernels, same
+            # order.  A sequence-parallel rank runs the same executor: only the collectives of the per-layer exchange come back to the
+            # host (xch)
             if sp is None:
-                return self._cstep.step(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, cfg_pair=cfg_pair)
-            return self._cstep.step_sp(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, xch, cfg_pair=cfg_pair)
+                return self._cstep.step(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, cfg_pair=cfg_pair, n_char=n_char)
+            return self._cstep.step_sp(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, xch, cfg_pair=cfg_pair, n_char=n_char)
         ws = self._workspace(B, Ltok, Lnoise, dev, blocks_in_c=use_c)
 
         # ---- time / AdaLN tables (reference :1521-1555, :1025-1028, :823) ----
@@ -529,17 +534,8 @@ class DiffusionTransformer(nn.Module):
         mod = ops.adaln_table(adaln, W["adaln_tables"])                       # (layers, B, 6D) fp32
         fin = ops.adaln_table(emb.repeat(1, 2).contiguous(), W["final_table"])[0]   # (B, 2D) fp32
 
-        # ---- patch embedding straight into the token layout [ref | noise | pose] (:99-130) ----
-        if n_char == 1:
-            tok = ops.patchify(x32, ref, pose, kpad=128, out=ws["tok"])
-        else:
-            tok = ws["tok"]
-            for c in range(n_char):         # per-character assembly with the single-character kernel (glue; not a hot path)
-                tk = ops.patchify(x32, ref[:, c:c + 1].contiguous(), pose[:, c * T:(c + 1) * T].contiguous(), kpad=128)
-                tok[:, c * Lref1:(c + 1) * Lref1].copy_(tk[:, :Lref1])
-                if c == 0:
-                    tok[:, Lref:Lref + Lnoise].copy_(tk[:, Lref1:Lref1 + Lnoise])
-                tok[:, Lref + Lnoise + c * Lpose1:Lref + Lnoise + (c + 1) * Lpose1].copy_(tk[:, Lref1 + Lnoise:])
+        # ---- patch embedding straight into the token layout [ref_0.. | noise | pose_0..] (:99-130), one launch for any n_char ----
+        tok = ops.patchify(x32, ref.contiguous(), pose.contiguous(), kpad=128, out=ws["tok"], n_char=n_char)
         h = ws["h"]
         Lrn = Lref + Lnoise
         for b in range(B):
@@ -553,7 +549,7 @@ class DiffusionTransformer(nn.Module):
         for i, lw in enumerate(W["layers"]):
             m = mod[i]                                                        # (B, 6D)
             if use_c:
-                # (multi-character extension: token assembly above in the host, every block as one executor call)
+                # (_c_blocks: token assembly above in the host, every block as one executor call)
                 if sp is None:
                     self._cstep.block(i, h, m, cond, cos, sin)
                 else:

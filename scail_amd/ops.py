@@ -300,17 +300,23 @@ def adaln_table(emb, table):
     return out
 
 
-def patchify(x, ref, pose, kpad=128, out=None):
-    """x fp32 (B,T,16,H,W); ref bf16 (1|B,1,16,H,W); pose bf16 (1|B,T,16,H/2,W/2) -> (B, L, kpad) bf16."""
+def patchify(x, ref, pose, kpad=128, out=None, n_char=1):
+    """x fp32 (B,T,16,H,W); ref bf16 (1|B,n_char,16,H,W); pose bf16 (1|B,n_char*T,16,H/2,W/2) -> (B, L, kpad) bf16, token order
+    [ref_0.. | noise | pose_0..].  n_char == 1: scail_patchify; n_char > 1 (multi-character extension): ONE scail_patchify_chars launch."""
     _chk(x, f32, "patchify.x"); _chk(ref, bf16, "patchify.ref"); _chk(pose, bf16, "patchify.pose")
     assert x.is_contiguous() and ref.is_contiguous() and pose.is_contiguous()
     B, T, C, H, W = x.shape
-    assert C == 16 and ref.shape[1:] == (1, 16, H, W) and pose.shape[1:] == (T, 16, H // 2, W // 2)
-    Ltok = (1 + T) * (H // 2) * (W // 2) + T * (H // 4) * (W // 4)
+    assert C == 16 and ref.shape[1:] == (n_char, 16, H, W) and pose.shape[1:] == (n_char * T, 16, H // 2, W // 2)
+    Ltok = (n_char + T) * (H // 2) * (W // 2) + n_char * T * (H // 4) * (W // 4)
     if out is None:
         out = torch.empty(B, Ltok, kpad, device=x.device, dtype=bf16)
-    L.call("scail_patchify", x.data_ptr(), ref.data_ptr(), pose.data_ptr(), out.data_ptr(), B, ref.shape[0],
-           pose.shape[0], T, H, W, kpad, _stream())
+    assert out.is_contiguous() and out.shape == (B, Ltok, kpad)
+    if n_char == 1:
+        L.call("scail_patchify", x.data_ptr(), ref.data_ptr(), pose.data_ptr(), out.data_ptr(), B, ref.shape[0],
+               pose.shape[0], T, H, W, kpad, _stream())
+    else:
+        L.call("scail_patchify_chars", x.data_ptr(), ref.data_ptr(), pose.data_ptr(), out.data_ptr(), B, ref.shape[0],
+               pose.shape[0], n_char, T, H, W, kpad, _stream())
     return out
 
 
