@@ -279,6 +279,37 @@ int scail_dit_sample_chars(scail_dit* h, float* x, const float* timesteps, const
                            const float* rope_cos, const float* rope_sin, int64_t T, int64_t H, int64_t W,
                            void* workspace, int64_t workspace_bytes, void* stream);
 
+/*
+ * The sampling loop of RFSamplerLong (temporal tiling, sampling.py:986-1085) with VanillaCFG for one request: how this model family
+ * samples a clip longer than the trained window.  The latent x fp32 [1,T,16,H,W] (device, in / out) is denoised in n_tiles >= 2 tiles of
+ * Tt <= min(T, 64) frames each; tile k is the frames tile_frames[k][0 .. Tt-1] (any order, distinct inside a tile; every frame of [0, T)
+ * in at least one tile) and has its own pose latent pose_tiles[k] (bf16 [Tt,16,H/2,W/2]: the VAE encoding of that window on its own).
+ * With F = 16*H*W, per step i (scail_hip.h scail_tile_*):
+ *   den = 0
+ *   for k = 0 .. n_tiles-1, ascending:  xin = [x[f_k]; x[f_k]]                                                   scail_tile_gather
+ *                                       v = scail_dit_step_chars(xin, timesteps[i], cond, ref, pose_tiles[k], B = 2, T = Tt, SCAIL_DIT_CFG_PAIR)
+ *                                       d = v_u + cfg (v_c - v_u);  den[f_kj, e] = den[f_kj, e] + tile_w[k][j] * d   scail_tile_blend_acc
+ *   x[f, e] = x[f, e] + dsigma[i] * (den[f, e] * inv_wsum[f])                                                    scail_tile_finish
+ * every operation rounded on its own (no fused multiply-add), accumulation in ascending tile order: the bits of the host loop
+ * (scail_amd/sampler.py RFSamplerLong.sample_hip).  The caller computes, in fp32, tile_w[k][j] = float(m_k) * w_j with the triangular
+ * w_j = min(u, 2 - u), u = (j + 0.5) * 2 / Tt, and m_k = 1 for the first and last tile and 2 otherwise (the reference evaluates interior
+ * tiles twice with equal inputs; here once, with that multiplicity), and inv_wsum[f] = 1 / sum of the tile_w that land on frame f.
+ * timesteps DEVICE fp32 [n_steps][2], dsigma / tile_frames / tile_w / inv_wsum HOST arrays read during the call (their values travel in
+ * kernel arguments: no host-to-device copy), rope_cos / rope_sin the tables of a Tt-frame clip, shared by every tile.
+ * workspace >= scail_dit_sample_tiled_workspace_bytes(h, T, Tt, H, W) (-1: bad handle / shape, T >= 32768 or Tt outside 1..min(T, 64)) = the step workspace of (2, Tt, H, W) + the
+ * xin / v pair + den.  Nothing synchronises; the call is capturable after one warm-up call.  fp8 GEMMs work as under scail_dit_step.
+ * One character per request: tiles and the _chars forms are not combined.  Sequence-parallel ranks keep the host loop.
+ * Refused before anything is enqueued, with an error that names the value: n_tiles < 2, T >= 32768, Tt outside 1..min(T, 64), a frame index outside
+ * [0, T), an index repeated inside one tile, a frame covered by no tile, a non-finite or non-positive inv_wsum, a null pointer, a
+ * workspace that is too small.
+ */
+int64_t scail_dit_sample_tiled_workspace_bytes(const scail_dit* h, int64_t T, int64_t Tt, int64_t H, int64_t W);
+int scail_dit_sample_tiled(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                           const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose_tiles,
+                           const int32_t* tile_frames, const float* tile_w, const float* inv_wsum, int64_t n_tiles, int64_t T, int64_t Tt,
+                           const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

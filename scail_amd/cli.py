@@ -17,7 +17,12 @@ uncond_context (1,Lt,4096), clip (1,257,1280); without either synthetic inputs a
 file name with Motion-JPEG samples, container written by scail_amd/video_io.py) where the reference writes H.264 mp4.  ``--prompt TEXT --tokenizer <HF dir | spiece.model> [--t5-ckpt ..] [--clip-ckpt ..]`` runs the UMT5 and CLIP encoders
 (scail_amd/umt5.py, clip.py) on the prompt and the reference image.  Offline limits of this image: no H.264 / HEVC codec (decord,
 imageio, ffmpeg, cv2 are absent: an .mp4 with such a track is rejected by the name of its codec), no tokenizer files and no checkpoints -- hence the container formats above, the tokenizer as a path
-argument, and random-init weights unless checkpoints are given."""
+argument, and random-init weights unless checkpoints are given.
+
+Clips longer than one window (an EXTENSION: the reference CLI has no such route, it only ships the sampler): a pose clip with more latent
+frames than ``--tile-frames`` covers is sampled with ``RFSamplerLong`` (temporal tiling, sampling.py:986-1085) over the windows of
+``plan_tiles`` -- each window's pose frames VAE-encoded on their own, noise and decode for the whole latent.  A clip that fits one window
+takes the plain path above, unchanged."""
 from __future__ import annotations
 
 import argparse
@@ -62,6 +67,41 @@ def synthetic_request(H, W, frames, text_dim, Lt, device, seed=0):
     uc[:, :1] = r(1, 1, text_dim)
     return dict(ref=(torch.rand(3, 1, H, W, generator=g) * 2 - 1).to(device), pose=(torch.rand(3, frames, H // 2, W // 2, generator=g) * 2 - 1).to(device),
                 context=ctx.to(device), uncond_context=uc.to(device), clip=r(1, 257, 1280).to(device))
+
+
+def plan_tiles(T: int, Tt: int, overlap: int):
+    """Temporal windows of a T-frame latent for RFSamplerLong: contiguous tiles of Tt latent frames whose neighbours share ``overlap``
+    frames (1 <= overlap < Tt).  None when one window holds the clip (T <= Tt: the plain path).  Otherwise the tiles start at 0, s, 2s, ..
+    (s = Tt - overlap) while start + Tt < T, and a final tile ends at T: at least two tiles, every frame covered."""
+    if T < 1 or Tt < 1:
+        raise ValueError(f"plan_tiles: T and Tt must be positive, got T = {T}, Tt = {Tt}")
+    if T <= Tt:
+        return None
+    if not 1 <= overlap < Tt:
+        raise ValueError(f"plan_tiles: the overlap must be 1..Tt - 1 = {Tt - 1} latent frames, got {overlap}")
+    starts, s = [], 0
+    while s + Tt < T:
+        starts.append(s)
+        s += Tt - overlap
+    starts.append(T - Tt)
+    return [list(range(a, a + Tt)) for a in starts]
+
+
+def tile_args(tile_frames, tile_overlap, num_frames):
+    """``--tile-frames`` / ``--tile-overlap`` (pixel frames) -> (Tt, overlap) in latent frames.  Defaults: the network's window
+    (``num_frames``) and half of its latent frames."""
+    tf = num_frames if tile_frames is None else tile_frames
+    if tf < 5 or (tf - 1) % 4:
+        raise ValueError(f"--tile-frames must be 4n + 1 pixel frames with n >= 1 (the causal VAE's frame groups), got {tf}")
+    Tt = (tf - 1) // 4 + 1
+    if tile_overlap is None:
+        return Tt, max(1, Tt // 2)
+    if tile_overlap % 4 or tile_overlap < 4:
+        raise ValueError(f"--tile-overlap must be a positive multiple of 4 pixel frames (whole latent frames), got {tile_overlap}")
+    if tile_overlap // 4 >= Tt:
+        raise ValueError(f"--tile-overlap = {tile_overlap} pixel frames ({tile_overlap // 4} latent frames) must be smaller than the window of "
+                         f"{tf} pixel frames ({Tt} latent frames)")
+    return Tt, tile_overlap // 4
 
 
 REF_IMAGE_PATTERNS = ["ref.jpg", "ref.png", "ref_image.jpg", "ref_image.png"]                # sample_video.py:289
@@ -173,7 +213,7 @@ def build_engine(cfg, load=None, device="cuda"):
     return engine
 
 
-def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frames=None, engine=None):
+def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frames=None, engine=None, tile_frames=None, tile_overlap=None):
     engine = engine or build_engine(cfg, load, device)
     H, W = cfg.get("args", {}).get("sampling_image_size", [512, 896])
     net = engine.network
@@ -184,6 +224,13 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     t0 = time.perf_counter()
     # model.encode_first_stage(..., force_encode=True): VAE mean x scale_factor (sample_video.py:366, :381; diffusion_video.py:311-331)
     ref_lat = engine.encode_first_stage(req["ref"].unsqueeze(0), None, force_encode=True)
+    n_pix = req["pose"].shape[1]
+    if n_pix > (net.num_frames if tile_frames is None else tile_frames):      # longer than one window: temporal tiles (an extension)
+        if (n_pix - 1) % 4:
+            raise ValueError(f"a pose clip longer than one window needs 4n + 1 frames (the causal VAE's frame groups), got {n_pix}")
+        Tt, overlap = tile_args(tile_frames, tile_overlap, net.num_frames)
+        tiles = plan_tiles((n_pix - 1) // 4 + 1, Tt, overlap)
+        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0)
     pose_lat = engine.encode_first_stage(req["pose"].unsqueeze(0), None, force_encode=True)   # already half resolution (:350-351)
     ref_concat = ref_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)      # B C T H W -> B T C H W
     pose_latent = pose_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)
@@ -194,6 +241,11 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     uc = dict(crossattn=req["uncond_context"], **shared)
     torch.manual_seed(seed)
     z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps)
+    return _finish(engine, z, t0)
+
+
+def _finish(engine, z, t0):
+    """sampled latent (B T C H W) -> (video in [0, 1], latent (B C T H W), seconds); (None, None, seconds) off sequence-parallel rank 0"""
     if engine.sp is not None and engine.sp.size > 1 and engine.sp.rank != 0:
         torch.cuda.synchronize()
         return None, None, time.perf_counter() - t0                         # only SP rank 0 holds the gathered latent (:484)
@@ -204,7 +256,35 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     return video, z, time.perf_counter() - t0
 
 
-def main():
+def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0):
+    """A pose clip longer than one window (an extension, see the module docstring): RFSamplerLong with the configured sampler's
+    parameters over ``tiles``; every window's pose frames [4 start, 4 (start + Tt - 1)] are VAE-encoded on their own (the causal VAE treats
+    a window's first frame as a clip's first frame, which is how ``smpl_tiled[:, k]`` is used); noise and decode for the whole latent."""
+    from . import sampler as S
+    Tt = len(tiles[0])
+    ref_concat = ref_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)
+    wins = []
+    for t in tiles:
+        lat = engine.encode_first_stage(req["pose"][:, 4 * t[0]:4 * (t[0] + Tt - 1) + 1].unsqueeze(0), None, force_encode=True)
+        wins.append(lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16))
+    smpl_tiled = torch.stack(wins, 1)                                       # (1, n_tiles, Tt, 16, h/2, w/2)
+    T, C, h, w = tiles[-1][-1] + 1, ref_concat.shape[2], ref_concat.shape[3], ref_concat.shape[4]
+    shared = dict(concat_images=torch.zeros(1, device=device), ref_concat=ref_concat, smpl_tiled=smpl_tiled,
+                  image_clip_features=req["clip"].to(torch.bfloat16))
+    c = dict(crossattn=req["context"], **shared)
+    uc = dict(crossattn=req["uncond_context"], **shared)
+    params = dict(cfg["model"]["sampler_config"].get("params", {}))
+    params["device"] = device
+    plain, engine.sampler = engine.sampler, S.RFSamplerLong(**params)
+    try:
+        torch.manual_seed(seed)
+        z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, tile_indices=tiles)
+    finally:
+        engine.sampler = plain
+    return _finish(engine, z, t0)
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--base", nargs="*", default=[])
     ap.add_argument("--tiny", action="store_true")
@@ -229,8 +309,20 @@ def main():
     ap.add_argument("--gemm-precision", choices=("bf16", "fp8"), default=None,
                     help="precision of the six per-token GEMMs of every block (default: the config's, bf16); fp8 = e4m3 with per-token / "
                          "per-channel scales, single GPU")
-    a = ap.parse_args()
+    ap.add_argument("--tile-frames", type=int, default=None,
+                    help="pixel frames per temporal window, 4n + 1 (default: the network's num_frames); a pose clip with more frames is sampled "
+                         "in overlapping windows (RFSamplerLong), an extension of the reference CLI; such a clip needs 4n + 1 frames")
+    ap.add_argument("--tile-overlap", type=int, default=None,
+                    help="pixel frames shared by neighbouring windows, a multiple of 4 and smaller than the window (default: half of the "
+                         "window's latent frames, e.g. 40 for an 81-frame window)")
+    a = ap.parse_args(argv)
     cfg = TINY if a.tiny or not a.base else load_yaml_configs(*a.base)
+    if a.tile_frames is not None or a.tile_overlap is not None:         # argument errors before any model is built
+        try:
+            tile_args(a.tile_frames, a.tile_overlap, cfg["model"]["network_config"].get("params", {}).get("num_frames", 81))
+        except ValueError as e:
+            ap.error(str(e))
+    tk = dict(tile_frames=a.tile_frames, tile_overlap=a.tile_overlap)
     if a.gemm_precision is not None:
         cfg = copy.deepcopy(cfg)
         cfg["model"]["network_config"].setdefault("params", {})["gemm_precision"] = a.gemm_precision
@@ -247,7 +339,7 @@ def main():
             if a.tokenizer:
                 req.update(encode_conditioning(text, a.negative_prompt, req["ref"], td, a.tokenizer, a.t5_ckpt, a.clip_ckpt,
                                                max_length=512 if td == 4096 else 16))
-            video, z, dt = run(cfg, req, a.steps, seed=a.seed, engine=engine)
+            video, z, dt = run(cfg, req, a.steps, seed=a.seed, engine=engine, **tk)
             if video is None:
                 continue
             save_dir = os.path.join(a.output_dir, os.path.basename(os.path.normpath(input_dir)))
@@ -271,7 +363,7 @@ def main():
                 req.update(encode_conditioning(a.prompt, a.negative_prompt, req["ref"], text_dim, a.tokenizer, a.t5_ckpt, a.clip_ckpt,
                                                max_length=512 if text_dim == 4096 else 16))
             return req
-    video, z, dt = run(cfg, inputs, a.steps, a.load, a.seed)
+    video, z, dt = run(cfg, inputs, a.steps, a.load, a.seed, **tk)
     if video is None:
         return
     print(f"sampled latent {tuple(z.shape)} -> video {tuple(video.shape)} in {dt:.2f} s")

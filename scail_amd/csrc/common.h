@@ -29,6 +29,12 @@ int scail_check_launch(const char* what);
         }                                                                          \
     } while (0)
 
+// one temporal tile's frame indices (rowops.hip): Tt in 1..min(T, 64), indices in [0, T), `unique`: none twice; 0, or 1 + an error
+// that starts with `who` and names the value
+int scail_tile_check(const char* who, const int32_t* frames, int64_t Tt, int64_t T, bool unique);
+// y[0 .. n) = 0.0f, enqueued as a kernel (rowops.hip)
+int scail_zero_f32(float* y, int64_t n, void* stream);
+
 // ---- embedded code objects (codeobj.hip) ------------------------------------------------------
 // The generated kernels (scail_amd/asmgen) travel as code-object images embedded by build.py.  scail_module_function resolves kernel
 // `name` of `image` on the CURRENT device (module and function cached per device); 0, or 2 + scail_last_error "<family>: ...".

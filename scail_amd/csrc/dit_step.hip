@@ -6,6 +6,7 @@
 // a single-rank step is hipGraph-capturable.
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <vector>
 
 #include "common.h"
@@ -883,6 +884,82 @@ extern "C" int scail_dit_sample_chars(scail_dit* h, float* x, const float* times
         DIT_TRY(scail_dit_step_chars(h, xin, timesteps + 2 * i, cond, ref, 1, pose, 1, n_char, pose_frames, rope_cos, rope_sin, v, 2, T, H, W,
                                      SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream));
         DIT_TRY(scail_cfg_euler(x, v, n, cfg_scale, dsigma[i], stream));
+    }
+    return 0;
+}
+
+// ---- the tiled sampler loop (RFSamplerLong, sampling.py:986-1085; scail_amd/sampler.py RFSamplerLong.sample_hip is the host form) ----
+extern "C" int64_t scail_dit_sample_tiled_workspace_bytes(const scail_dit* h, int64_t T, int64_t Tt, int64_t H, int64_t W) {
+    if (T < 1 || Tt < 1 || Tt > T || Tt > 64 || T >= (1 << 15)) return -1;
+    const int64_t step = scail_dit_chars_workspace_bytes(h, 2, Tt, H, W, 1);
+    if (step < 0) return -1;
+    const int64_t F = 16 * H * W;
+    return step + 2 * align256(2 * Tt * F * 4) + align256(T * F * 4);     // + [x_k; x_k], [v_u; v_c] of one tile and den, fp32
+}
+
+extern "C" int scail_dit_sample_tiled(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                                      const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose_tiles,
+                                      const int32_t* tile_frames, const float* tile_w, const float* inv_wsum, int64_t n_tiles, int64_t T, int64_t Tt,
+                                      const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
+                                      void* stream) {
+    const char* who = "scail_dit_sample_tiled";
+    auto fail = [&](const std::string& msg) {
+        scail_set_error(std::string(who) + ": " + msg);
+        return 1;
+    };
+    // every refusal comes before the first enqueue, names the value, and the ones about the tiling need neither a handle nor a device
+    if (n_tiles < 2)
+        return fail("needs at least 2 tiles (a single tile leaves the weight sums of the reference at zero), got n_tiles = " + std::to_string(n_tiles));
+    if (T >= (1 << 15)) return fail("the latent must have fewer than 32768 frames, got T = " + std::to_string(T));
+    if (T < 1 || Tt < 1 || Tt > 64 || Tt > T)
+        return fail("the tile length Tt must be 1..min(T, 64), got Tt = " + std::to_string(Tt) + " with T = " + std::to_string(T));
+    if (n_steps < 0) return fail("n_steps must be >= 0, got " + std::to_string(n_steps));
+    if (tile_frames == nullptr) return fail("null pointer: tile_frames");
+    if (tile_w == nullptr) return fail("null pointer: tile_w");
+    if (inv_wsum == nullptr) return fail("null pointer: inv_wsum");
+    std::vector<char> covered((size_t)T, 0);
+    for (int64_t k = 0; k < n_tiles; ++k) {
+        DIT_TRY(scail_tile_check((std::string(who) + ": tile " + std::to_string(k)).c_str(), tile_frames + k * Tt, Tt, T, true));
+        for (int64_t j = 0; j < Tt; ++j) covered[(size_t)tile_frames[k * Tt + j]] = 1;
+    }
+    for (int64_t f = 0; f < T; ++f) {
+        if (!covered[(size_t)f]) return fail("frame " + std::to_string(f) + " of [0, T = " + std::to_string(T) + ") is covered by no tile");
+        if (!(inv_wsum[f] > 0.0f) || !std::isfinite(inv_wsum[f]))
+            return fail("inv_wsum[" + std::to_string(f) + "] = " + std::to_string(inv_wsum[f]) + " must be finite and positive");
+    }
+    if (H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0 || H >= (1 << 15) || W >= (1 << 15))
+        return fail("latent H and W must be positive multiples of 4 below 32768, got H = " + std::to_string(H) + ", W = " + std::to_string(W));
+    const int64_t F = 16 * H * W, pair = align256(2 * Tt * F * 4), den_bytes = align256(T * F * 4);
+    if (workspace_bytes < 2 * pair + den_bytes)      // the handle-independent part, so this answers without a handle too
+        return fail("workspace too small: " + std::to_string(workspace_bytes) + " bytes cannot hold the tile pair buffers and den (" +
+                    std::to_string(2 * pair + den_bytes) + " bytes) next to the step workspace (scail_dit_sample_tiled_workspace_bytes)");
+    const void* ptrs[] = {h, x, timesteps, dsigma, cond, ref, pose_tiles, rope_cos, rope_sin, workspace};
+    const char* names[] = {"handle", "x", "timesteps", "dsigma", "cond", "ref", "pose_tiles", "rope_cos", "rope_sin", "workspace"};
+    for (int i = 0; i < 10; ++i)
+        if (ptrs[i] == nullptr && !(i == 3 && n_steps == 0)) return fail(std::string("null pointer: ") + names[i]);
+    const int64_t step_bytes = scail_dit_chars_workspace_bytes(h, 2, Tt, H, W, 1);
+    if (step_bytes < 0) return fail("bad latent shape (Tt " + std::to_string(Tt) + ", H " + std::to_string(H) + ", W " + std::to_string(W) + ")");
+    if (workspace_bytes < step_bytes + 2 * pair + den_bytes)
+        return fail("workspace too small: " + std::to_string(workspace_bytes) + " bytes, needs " + std::to_string(step_bytes + 2 * pair + den_bytes) +
+                    " (scail_dit_sample_tiled_workspace_bytes)");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
+
+    char* base = static_cast<char*>(workspace);
+    float* xin = reinterpret_cast<float*>(base + step_bytes);
+    float* v = reinterpret_cast<float*>(base + step_bytes + pair);
+    float* den = reinterpret_cast<float*>(base + step_bytes + 2 * pair);
+    const int64_t pose_tile = Tt * 16 * (H / 2) * (W / 2);
+    // den starts at zero; scail_tile_finish leaves it zeroed for the next step
+    if (n_steps > 0) DIT_TRY(scail_zero_f32(den, T * F, stream));
+    for (int64_t i = 0; i < n_steps; ++i) {
+        for (int64_t k = 0; k < n_tiles; ++k) {      // ascending, the order of the host loop: the accumulation order is part of the result
+            const int32_t* fr = tile_frames + k * Tt;
+            DIT_TRY(scail_tile_gather(x, xin, fr, Tt, T, F, stream));
+            DIT_TRY(scail_dit_step_chars(h, xin, timesteps + 2 * i, cond, ref, 1, pose_tiles + k * pose_tile, 1, 1, Tt, rope_cos, rope_sin, v, 2, Tt, H,
+                                         W, SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream));
+            DIT_TRY(scail_tile_blend_acc(den, v, fr, tile_w + k * Tt, Tt, T, F, cfg_scale, stream));
+        }
+        DIT_TRY(scail_tile_finish(x, den, inv_wsum, T, F, dsigma[i], stream));
     }
     return 0;
 }

@@ -542,6 +542,55 @@ __global__ void cfg_euler_kernel(float* __restrict__ x, const float* __restrict_
     x[i] = x[i] + dsigma * (vu + cfg * (vc - vu));
 }
 
+// ---- temporal tiling (RFSamplerLong, sampling.py:986-1085; include/scail_hip.h scail_tile_*) ----
+// A latent frame is F = 16 * H * W floats.  The frame indices / weights of one tile travel BY VALUE in the kernel arguments (no
+// host-to-device copy, no synchronisation: the launches stay capturable); blockIdx.y is the tile frame, so the index is wave-uniform.
+// Every operation is rounded on its own (contraction off): each kernel gives the bits of the torch expression it replaces, unlike
+// cfg_euler_kernel above, whose multiply-adds contract.
+#define TILE_MAX 64
+struct TileArgs {
+    int32_t f[TILE_MAX];   // frame index of tile frame j (gather / blend); unused by the finish kernel
+    float w[TILE_MAX];     // blend: m_k * tile_weight[j];  finish: 1 / weight_sum of frame f0 + j
+};
+
+// xin[j, :] = xin[Tt + j, :] = x[f_j, :]   (torch.cat([x[:, idx]] * 2): the CFG batch)
+__global__ void tile_gather_kernel(const float* __restrict__ x, float* __restrict__ xin, TileArgs a, int64_t Tt, int64_t F) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= F) return;
+    const int64_t j = blockIdx.y;
+    const float v = x[(int64_t)a.f[j] * F + e];
+    xin[j * F + e] = v;
+    xin[(Tt + j) * F + e] = v;
+}
+
+// den[f_j, e] += wk_j * (vu + cfg * (vc - vu)),  v = [v_u; v_c] fp32 [2, Tt, F]; the f_j of one tile are distinct (checked on the host)
+__global__ void tile_blend_acc_kernel(float* __restrict__ den, const float* __restrict__ v, TileArgs a, int64_t Tt, int64_t F, float cfg) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= F) return;
+    const int64_t j = blockIdx.y;
+    const float vu = v[j * F + e], vc = v[(Tt + j) * F + e];
+    const float d = vu + cfg * (vc - vu);
+    const int64_t o = (int64_t)a.f[j] * F + e;
+    den[o] = den[o] + a.w[j] * d;
+}
+
+// x[f0 + j, e] += dsigma * (den[f0 + j, e] * inv_j);  den[f0 + j, e] = 0 (ready for the next step's accumulation)
+__global__ void tile_finish_kernel(float* __restrict__ x, float* __restrict__ den, TileArgs a, int64_t f0, int64_t F, float dsigma) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= F) return;
+    const int64_t j = blockIdx.y;
+    const int64_t o = (f0 + j) * F + e;
+    x[o] = x[o] + dsigma * (den[o] * a.w[j]);
+    den[o] = 0.0f;
+}
+
+__global__ void zero_f32_kernel(float* __restrict__ y, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) y[i] = 0.0f;
+}
+
 __global__ void f32_to_bf16_kernel(const float* __restrict__ x, u16* __restrict__ y, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) y[i] = f2bf(x[i]);
@@ -809,6 +858,95 @@ extern "C" int scail_cfg_euler(float* x, const float* v, int64_t n, float cfg_sc
     hipLaunchKernelGGL(cfg_euler_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        x, v, n, cfg_scale, dsigma);
     return scail_check_launch("cfg_euler");
+}
+
+// ---- temporal tiling: host-side checks (the message names the value) + launches ----
+// Tt in 1..min(T, 64), every frame index in [0, T) and, `unique`, no index twice (two tile frames would accumulate into one latent frame
+// concurrently).  Shared with the sampler entry point (dit_step.hip), which checks every tile before anything is enqueued.
+int scail_tile_check(const char* who, const int32_t* frames, int64_t Tt, int64_t T, bool unique) {
+    if (T < 1 || Tt < 1 || Tt > TILE_MAX || Tt > T) {
+        scail_set_error(std::string(who) + ": the tile length Tt must be 1..min(T, 64), got Tt = " + std::to_string(Tt) + " with T = " + std::to_string(T));
+        return 1;
+    }
+    if (frames == nullptr) {
+        scail_set_error(std::string(who) + ": null pointer: frames");
+        return 1;
+    }
+    for (int64_t j = 0; j < Tt; ++j) {
+        if (frames[j] < 0 || frames[j] >= T) {
+            scail_set_error(std::string(who) + ": frame index " + std::to_string(frames[j]) + " (tile frame " + std::to_string(j) + ") is outside [0, T = " +
+                            std::to_string(T) + ")");
+            return 1;
+        }
+        for (int64_t i = 0; unique && i < j; ++i)
+            if (frames[i] == frames[j]) {
+                scail_set_error(std::string(who) + ": frame index " + std::to_string(frames[j]) + " is repeated inside one tile (tile frames " +
+                                std::to_string(i) + " and " + std::to_string(j) + ")");
+                return 1;
+            }
+    }
+    return 0;
+}
+
+static int tile_shape_check(const char* who, int64_t F) {
+    if (F < 0 || (F + 255) / 256 >= (1ll << 31)) {
+        scail_set_error(std::string(who) + ": bad frame size F = " + std::to_string(F));
+        return 1;
+    }
+    return 0;
+}
+
+extern "C" int scail_tile_gather(const float* x, float* xin, const int32_t* frames, int64_t Tt, int64_t T, int64_t F, void* stream) {
+    if (int rc = scail_tile_check("scail_tile_gather", frames, Tt, T, false)) return rc;
+    if (int rc = tile_shape_check("scail_tile_gather", F)) return rc;
+    SCAIL_REQUIRE(x != nullptr && xin != nullptr, "null pointer");
+    if (F == 0) return 0;
+    TileArgs a = {};
+    for (int64_t j = 0; j < Tt; ++j) a.f[j] = frames[j];
+    hipLaunchKernelGGL(tile_gather_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)Tt), dim3(256), 0, (hipStream_t)stream, x, xin, a, Tt, F);
+    return scail_check_launch("tile_gather");
+}
+
+extern "C" int scail_tile_blend_acc(float* den, const float* v, const int32_t* frames, const float* wk, int64_t Tt, int64_t T, int64_t F,
+                                    float cfg_scale, void* stream) {
+    if (int rc = scail_tile_check("scail_tile_blend_acc", frames, Tt, T, true)) return rc;
+    if (int rc = tile_shape_check("scail_tile_blend_acc", F)) return rc;
+    SCAIL_REQUIRE(den != nullptr && v != nullptr && wk != nullptr, "null pointer");
+    if (F == 0) return 0;
+    TileArgs a = {};
+    for (int64_t j = 0; j < Tt; ++j) {
+        a.f[j] = frames[j];
+        a.w[j] = wk[j];
+    }
+    hipLaunchKernelGGL(tile_blend_acc_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)Tt), dim3(256), 0, (hipStream_t)stream, den, v, a, Tt, F,
+                       cfg_scale);
+    return scail_check_launch("tile_blend_acc");
+}
+
+// y[0 .. n) = 0 as a kernel launch.  Observation, cause not established: with one hipMemsetAsync in this place, the captured
+// scail_dit_sample_tiled gave wrong results from its second graph replay on (eager runs and the first replay were right); with this
+// kernel every replay is right.
+int scail_zero_f32(float* y, int64_t n, void* stream) {
+    if (n <= 0) return 0;
+    SCAIL_REQUIRE(y != nullptr && (n + 255) / 256 < (1ll << 31), "null pointer / too large");
+    hipLaunchKernelGGL(zero_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, n);
+    return scail_check_launch("zero_f32");
+}
+
+extern "C" int scail_tile_finish(float* x, float* den, const float* inv_wsum, int64_t T, int64_t F, float dsigma, void* stream) {
+    if (int rc = tile_shape_check("scail_tile_finish", F)) return rc;
+    SCAIL_REQUIRE(T >= 0 && T < (1ll << 31), "bad frame count");
+    SCAIL_REQUIRE(x != nullptr && den != nullptr && inv_wsum != nullptr, "null pointer");
+    if (F == 0) return 0;
+    for (int64_t f0 = 0; f0 < T; f0 += TILE_MAX) {      // 64 frames' factors per launch
+        const int64_t n = T - f0 < TILE_MAX ? T - f0 : TILE_MAX;
+        TileArgs a = {};
+        for (int64_t j = 0; j < n; ++j) a.w[j] = inv_wsum[f0 + j];
+        hipLaunchKernelGGL(tile_finish_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream, x, den, a, f0, F,
+                           dsigma);
+        if (int rc = scail_check_launch("tile_finish")) return rc;
+    }
+    return 0;
 }
 
 extern "C" int scail_f32_to_bf16(const float* x, scail_bf16* y, int64_t n, void* stream) {

@@ -172,6 +172,42 @@ class CStep:
                self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream().cuda_stream)
         return x32
 
+    def sample_tiled_workspace_bytes(self, T, Tt, H, W) -> int:
+        n = L.load().scail_dit_sample_tiled_workspace_bytes(self._h, T, Tt, H, W)
+        if n < 0:
+            raise L.ScailHipError(f"scail_dit_sample_tiled_workspace_bytes: bad shape (T {T}, Tt {Tt}, H {H}, W {W})")
+        return n
+
+    @staticmethod
+    def tile_tables(tile_indices, tile_w, inv_wsum):
+        """The host arrays of scail_dit_sample_tiled: (tile_frames int32 [n_tiles][Tt], tile_w fp32 [n_tiles][Tt], inv_wsum fp32 [T])."""
+        fr = [int(f) for t in tile_indices for f in t]
+        tw = tile_w.detach().cpu().float().reshape(-1).tolist()
+        iw = inv_wsum.detach().cpu().float().reshape(-1).tolist()
+        return (C.c_int32 * len(fr))(*fr), (C.c_float * len(tw))(*tw), (C.c_float * len(iw))(*iw)
+
+    def sample_tiled(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose_tiles, tile_indices, tile_w, inv_wsum, cos, sin) -> torch.Tensor:
+        """The whole RFSamplerLong loop in one C call (scail_dit_sample_tiled).  x32 (1,T,16,H,W) fp32 is updated in place and returned;
+        ``pose_tiles`` bf16 (1, n_tiles, Tt, 16, H/2, W/2); ``tile_indices`` n_tiles lists of Tt frame indices; ``tile_w`` host fp32
+        (n_tiles, Tt) = m_k * tile_weight; ``inv_wsum`` host fp32 (T); cos / sin: the tables of a Tt-frame clip."""
+        _, T, _, H, W = x32.shape
+        n_tiles = len(tile_indices)
+        Tt = len(tile_indices[0]) if n_tiles else 0
+        need = self.sample_tiled_workspace_bytes(T, Tt, H, W)
+        ws = self._ws_for(need, x32.device)
+        sig = sigmas.float().cpu()
+        n = sig.numel() - 1
+        ts = (sig[:-1] * 1000.0).repeat_interleave(2).to(x32.device).contiguous()       # (n, 2) device fp32
+        dsa = (C.c_float * n)(*[float(v) for v in (sig[1:] - sig[:-1])])
+        fr, tw, iw = self.tile_tables(tile_indices, tile_w, inv_wsum)
+        cc = _cond_struct(cond)
+        assert x32.is_contiguous() and x32.dtype == torch.float32 and ref.shape[0] == 1 and pose_tiles.is_contiguous()
+        assert pose_tiles.shape == (1, n_tiles, Tt, 16, H // 2, W // 2) and pose_tiles.dtype == torch.bfloat16
+        L.call("scail_dit_sample_tiled", self._h, x32.data_ptr(), ts.data_ptr(), C.cast(dsa, C.c_void_p), n, float(cfg_scale), C.byref(cc),
+               ref.data_ptr(), pose_tiles.data_ptr(), fr, tw, iw, n_tiles, T, Tt, cos.data_ptr(), sin.data_ptr(), H, W,
+               ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+        return x32
+
     def block(self, layer: int, hidden: torch.Tensor, mod: torch.Tensor, cond: Dict, cos, sin) -> torch.Tensor:
         """Seam B2: one transformer block in place on ``hidden`` (B, Ltok, D) bf16; ``mod`` (B, 6D) fp32 = adaLN embedding +
         this layer's table.  Returns ``hidden``."""

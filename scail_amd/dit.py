@@ -489,6 +489,31 @@ class DiffusionTransformer(nn.Module):
         x = x32.float().contiguous().clone()
         return self._cstep.sample(x, sigmas, cfg_scale, cond, as_bf16(ref), as_bf16(pose), cos, sin, n_char=n_char)
 
+    def sample_tiled_c(self, x32, sigmas, cfg_scale, ctx, ref, pose_tiles, clip, tile_indices, tile_w, inv_wsum, cond_key=None):
+        """The whole RFSamplerLong loop (temporal tiling) as ONE C call (scail_dit_sample_tiled, include/scail_dit.h): x32 (1,T,16,H,W) fp32,
+        ctx (2, Lt, text_dim) = [uncond; cond], ref (1,1,16,H,W), pose_tiles (1, n_tiles, Tt, 16, H/2, W/2), clip (1,Lc,1280);
+        tile_w (n_tiles, Tt) = m_k * tile_weight and inv_wsum (T) as RFSamplerLong.sample_hip forms them.  Single rank, one character."""
+        from .cstep import CStep
+        W = self.prepare()
+        dev = x32.device
+
+        def as_bf16(t):
+            t = t.to(dev)
+            return ops.to_bf16(t.contiguous()) if t.dtype == torch.float32 else t.to(torch.bfloat16).contiguous()
+
+        _, T, _, H, Wd = x32.shape
+        if ref.shape[1] != 1:
+            raise L.ScailHipError(f"temporal tiles take one reference frame (tiles and several characters are not combined), got {ref.shape[1]}")
+        if pose_tiles.dim() != 6 or pose_tiles.shape[1] != len(tile_indices) or pose_tiles.shape[2] != len(tile_indices[0]):
+            raise L.ScailHipError(f"smpl_tiled must be (1, n_tiles = {len(tile_indices)}, Tt = {len(tile_indices[0])}, 16, H/2, W/2), got "
+                                  f"{tuple(pose_tiles.shape)}")
+        cond = self._conditioning(as_bf16(ctx), as_bf16(clip), cond_key)
+        cos, sin = self._rope(len(tile_indices[0]), H // 2, Wd // 2, 0, 0, dev, 1)
+        if self._cstep is None:
+            self._cstep = CStep(self, W)
+        x = x32.float().contiguous().clone()
+        return self._cstep.sample_tiled(x, sigmas, cfg_scale, cond, as_bf16(ref), as_bf16(pose_tiles), tile_indices, tile_w, inv_wsum, cos, sin)
+
     def _run(self, x32, t32, ctx, ref, pose, clip, H_shift=0, W_shift=0, cond_key=None, cfg_pair=False):
         W = self.prepare()
         dev = x32.device

@@ -43,6 +43,9 @@ SIGNATURES = {
     "scail_patchify_chars": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
     "scail_unpatchify": [_p, _p, _i64, _i64, _i64, _i64, _p],
     "scail_cfg_euler": [_p, _p, _i64, _f, _f, _p],
+    "scail_tile_gather": [_p, _p, _p, _i64, _i64, _i64, _p],
+    "scail_tile_blend_acc": [_p, _p, _p, _p, _i64, _i64, _i64, _f, _p],
+    "scail_tile_finish": [_p, _p, _p, _i64, _i64, _f, _p],
     "scail_conv3d_cl": [_p, _p, _p, _p, _i64, _p, _i64, _p, _p],
     "scail_conv3d_cl_norm": [_p, _p, _p, _p, _i64, _p, _p, _p],
     "scail_conv3d_cl_resid_norm": [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p],
@@ -82,6 +85,9 @@ SIGNATURES = {
     "scail_dit_block_sp": [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _p],
     "scail_dit_sample_workspace_bytes": [_p, _i64, _i64, _i64],
     "scail_dit_sample": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _i64, _p],
+    # temporal tiling (RFSamplerLong): host arrays tile_frames / tile_w / inv_wsum after the pose tiles
+    "scail_dit_sample_tiled_workspace_bytes": [_p, _i64, _i64, _i64, _i64],
+    "scail_dit_sample_tiled": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _p],
     "scail_dit_fp8_weight_bytes": [_p, C.c_uint32],
     "scail_dit_enable_fp8": [_p, C.c_uint32, _p, _i64, _p],
     # include/scail_vae.h (scail_amd/cvae.py builds the structs)
@@ -96,7 +102,7 @@ SIGNATURES = {
 RESTYPES = {"scail_dit_destroy": None, "scail_vae_destroy": None, "scail_vae_workspace_bytes": _i64, "scail_dit_workspace_bytes": _i64, "scail_dit_sample_workspace_bytes": _i64,
             "scail_dit_block_workspace_bytes": _i64, "scail_dit_sp_workspace_bytes": _i64, "scail_dit_block_sp_workspace_bytes": _i64,
             "scail_dit_fp8_weight_bytes": _i64, "scail_dit_chars_workspace_bytes": _i64, "scail_dit_sp_chars_workspace_bytes": _i64,
-            "scail_dit_sample_chars_workspace_bytes": _i64}
+            "scail_dit_sample_chars_workspace_bytes": _i64, "scail_dit_sample_tiled_workspace_bytes": _i64}
 
 # include/scail_hip_ablation.h: only libscail_hip_abl.so (SCAIL_ABLATIONS=1) exports these
 ABLATION_SIGNATURES = {
@@ -110,7 +116,8 @@ ACT_NONE, ACT_SILU, ACT_GELU_TANH = 0, 1, 2
 # include/scail_dit.h SCAIL_DIT_FP8_*: the per-token GEMMs of a block that scail_dit_enable_fp8 switches to fp8
 FP8_GEMMS = {"qkv": 1, "o": 2, "cq": 4, "co": 8, "w1": 16, "w2": 32}
 FP8_ALL = 63
-ABI_VERSION = 7          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
+ABI_VERSION = 8          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
+                         # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);
                          # 5 = scail_rmsnorm_rope_slabs takes a slab row stride; the sequence-parallel exchange is ONE collective per direction
                          # (send / recv layouts of scail_dit.h), exchange-wait / restart categories of scail_dit_profile_read;

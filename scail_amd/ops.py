@@ -338,6 +338,58 @@ def cfg_euler_(x, v, cfg_scale, dsigma):
     return x
 
 
+# ---- temporal tiling (RFSamplerLong): the frame indices / weights are HOST values that travel in the kernel arguments ----
+def _tile_frames(frames):
+    import ctypes as C
+    fr = [int(f) for f in frames]
+    return (C.c_int32 * len(fr))(*fr), len(fr)
+
+
+def _host_f32(vals):
+    import ctypes as C
+    vals = vals.detach().cpu().float().tolist() if torch.is_tensor(vals) else [float(v) for v in vals]
+    return (C.c_float * len(vals))(*vals), len(vals)
+
+
+def tile_gather(x, frames, out=None):
+    """x fp32 (1, T, ...) -> (2, Tt, ...) = x[:, frames] twice (the CFG batch).  ``frames``: host ints, any order."""
+    _chk(x, f32, "tile_gather.x")
+    assert x.is_contiguous() and x.shape[0] == 1
+    fr, Tt = _tile_frames(frames)
+    T = x.shape[1]
+    F = x[0, 0].numel()
+    if out is None:
+        out = torch.empty((2, Tt) + tuple(x.shape[2:]), device=x.device, dtype=f32)
+    _chk(out, f32, "tile_gather.out")
+    assert out.is_contiguous() and out.numel() == 2 * Tt * F
+    L.call("scail_tile_gather", x.data_ptr(), out.data_ptr(), fr, Tt, T, F, _stream())
+    return out
+
+
+def tile_blend_acc_(den, v, frames, wk, cfg_scale):
+    """In place: den[:, frames] += wk[:, None] * (v[0] + cfg * (v[1] - v[0])), every operation rounded on its own.  den fp32 (1, T, ...),
+    v fp32 (2, Tt, ...); ``frames`` (distinct) and ``wk`` (m_k * tile_weight) are host values."""
+    _chk(den, f32, "tile_blend_acc.den"); _chk(v, f32, "tile_blend_acc.v")
+    assert den.is_contiguous() and v.is_contiguous() and den.shape[0] == 1 and v.shape[0] == 2
+    fr, Tt = _tile_frames(frames)
+    w, nw = _host_f32(wk)
+    F = den[0, 0].numel()
+    assert nw == Tt and v.numel() == 2 * Tt * F
+    L.call("scail_tile_blend_acc", den.data_ptr(), v.data_ptr(), fr, w, Tt, den.shape[1], F, float(cfg_scale), _stream())
+    return den
+
+
+def tile_finish_(x, den, inv_wsum, dsigma):
+    """In place: x += dsigma * (den * inv_wsum[:, None]), every operation rounded on its own; ``den`` is left zeroed.  x, den fp32
+    (1, T, ...); ``inv_wsum``: T host values."""
+    _chk(x, f32, "tile_finish.x"); _chk(den, f32, "tile_finish.den")
+    assert x.is_contiguous() and den.is_contiguous() and x.shape == den.shape and x.shape[0] == 1
+    w, nw = _host_f32(inv_wsum)
+    assert nw == x.shape[1]
+    L.call("scail_tile_finish", x.data_ptr(), den.data_ptr(), w, x.shape[1], x[0, 0].numel(), float(dsigma), _stream())
+    return x
+
+
 def to_bf16(x):
     _chk(x, f32, "to_bf16.x")
     x = x.contiguous()

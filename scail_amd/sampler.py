@@ -229,6 +229,22 @@ class RFSamplerLong(RFSampler):
         if any(len(t) != n0 for t in tile_indices):
             raise ValueError("all temporal tiles must have the same length")
 
+    ONE_CALL_MAX_TILE = 64        # include/scail_dit.h scail_dit_sample_tiled: a tile's indices and weights travel in kernel arguments
+
+    @classmethod
+    def _one_call_ok(cls, network, x, ref_concat, smpl_tiled, tile_indices, step_callback, chunk_dim) -> bool:
+        """Whether a request takes scail_dit_sample_tiled: RFSampler's conditions for its one-call route (C step on, no callback, no
+        chunk_dim, no timer / tap, one rank, batch 1) AND what that entry point covers -- one character, tiles of at most 64 latent
+        frames, one pose tile of Tt frames per tile.  Every other request keeps the Python loop below (several characters with
+        tiles, longer tiles, sequence-parallel ranks, instrumented runs)."""
+        Tt = len(tile_indices[0])
+        return bool(getattr(network, "use_c_step", False) and step_callback is None and chunk_dim is None
+                    and getattr(network, "kernel_timer", None) is None and getattr(network, "_tap", None) is None
+                    and (getattr(network, "sp", None) is None or network.sp.size == 1)
+                    and x.shape[0] == 1 and ref_concat.shape[0] == 1 and ref_concat.shape[1] == 1
+                    and smpl_tiled.dim() == 6 and smpl_tiled.shape[0] == 1 and smpl_tiled.shape[1] == len(tile_indices)
+                    and smpl_tiled.shape[2] == Tt and Tt <= cls.ONE_CALL_MAX_TILE and Tt <= x.shape[1] < (1 << 15))
+
     def sampler_step(self, sigma, next_sigma, denoiser, x, cond, uc=None, scale=None, fps=None, tile_indices=None,
                      smpl_tiled=None):
         """sampling.py:1036-1068 (generic protocol: any denoiser / network)."""
@@ -270,6 +286,19 @@ class RFSamplerLong(RFSampler):
         ctx = torch.cat((uc["crossattn"], cond["crossattn"]), 0)
         shared = {k: v for k, v in cond.items() if k not in ("crossattn", "smpl_tiled", "concat_smpl_render")}
         smpl_tiled = cond["smpl_tiled"]
+        if self._one_call_ok(network, x, shared["ref_concat"], smpl_tiled, tile_indices, step_callback, chunk_dim):
+            # the whole loop enqueued by ONE call into the library (scail_dit_sample_tiled): same network kernels, the gather / blend /
+            # Euler arithmetic below as HIP row kernels that round every operation on its own -- the same bits.  The weights are formed
+            # as below, on the latent's device (torch divides by a host scalar differently on the two devices), and handed over as
+            # host values once per request.
+            weight = self.tile_weight(len(tile_indices[0]), x.device)
+            tile_w = torch.stack([self._mult(k, n) * weight for k in range(n)])
+            wsum = torch.zeros(x.shape[1], device=x.device)
+            for k in range(n):
+                wsum[torch.as_tensor(list(tile_indices[k]), device=x.device, dtype=torch.long)] += tile_w[k]
+            return network.sample_tiled_c(x, sig, cfg, ctx, shared["ref_concat"], smpl_tiled, shared["image_clip_features"],
+                                          [list(map(int, t)) for t in tile_indices], tile_w.cpu(), (1.0 / wsum).cpu(),
+                                          cond_key=("sample_hip", id(cond)))
         x = x.float().contiguous().clone()
         dev = x.device
         weight = self.tile_weight(len(tile_indices[0]), dev)[:, None, None, None]
