@@ -29,7 +29,9 @@ int scail_check_launch(const char* what);
         }                                                                          \
     } while (0)
 
-// one temporal tile's frame indices (rowops.hip): Tt in 1..min(T, 64), indices in [0, T), `unique`: none twice; 0, or 1 + an error
+// a temporal tile's length (rowops.hip): Tt in 1..min(T, 64); 0, or 1 + (who != nullptr) an error that starts with `who` and names the values
+__attribute__((visibility("hidden"))) int scail_tile_len_check(const char* who, int64_t Tt, int64_t T);   // (library-internal, not an export)
+// one temporal tile's frame indices (rowops.hip): a tile length as above, indices in [0, T), `unique`: none twice; 0, or 1 + an error
 // that starts with `who` and names the value
 int scail_tile_check(const char* who, const int32_t* frames, int64_t Tt, int64_t T, bool unique);
 // y[0 .. n) = 0.0f, enqueued as a kernel (rowops.hip)

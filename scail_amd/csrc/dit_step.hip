@@ -44,9 +44,10 @@ constexpr int64_t KPAD = 128;   // patch-embedding im2col width (80 real columns
 
 inline int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
 
-// workspace layout (bytes, 256-aligned blocks)
-struct Ws {
-    int64_t tok, h, xn, qkv, att, ff, vt, xf, tokout, temb, e1, emb, adaln, mod, emb2, fin, xq, sx, total;
+// hands out the consecutive 256-byte aligned blocks of a workspace (so a total does not depend on the order of its blocks)
+struct Carve {
+    int64_t off = 0;
+    int64_t take(int64_t bytes) { const int64_t o = off; off += align256(bytes); return o; }
 };
 
 // elements of the V^T staging buffer of a (B, Ltok) block: one rank (sp_mode < 0): all heads x the local keys; ulysses: heads / ranks
@@ -58,7 +59,6 @@ int64_t vt_elems(const scail_dit_config& c, int64_t B, int64_t Ltok, int sp_mode
     return B * (sp_mode == SCAIL_SP_ULYSSES ? nh / ranks : nh) * 128 * Lfp;
 }
 
-// f8_k: the widest K of the GEMMs that run in fp8 (0: none) -- the e4m3 copy of a GEMM's input rows and their scales (xq, sx)
 // Token counts of a (T, H, W) latent (or latent slab) with C characters: [ref_0..ref_{C-1} | noise | pose_0..pose_{C-1}]
 struct TokLens {
     int64_t Lref, Lnoise, Lpose, Ltok;
@@ -74,10 +74,17 @@ TokLens tok_lens(int64_t C, int64_t T, int64_t H, int64_t W) {
 }
 // the self-attention launch takes ceil64(keys) < 2^31 (scail_flash_attn_bf16); a sequence-parallel rank attends to all ranks' keys
 constexpr int64_t MAX_KEYS = (1ll << 31) - 64;
-bool shape_ok(int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, int64_t ranks) {
-    if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0 || C < 1 || C > 64 || ranks < 1) return false;
-    if (T >= (1 << 15) || H >= (1 << 15) || W >= (1 << 15)) return false;      // (keeps the products below in 64 bits)
-    return ranks * tok_lens(C, T, H, W).Ltok < MAX_KEYS;
+// what keeps a latent (or latent slab) of C characters on `ranks` ranks from the executor: 0 nothing, 1 its sizes (or C / ranks) as
+// such, 2 the key count.  The queries answer -1 for either; dit_step_impl names which
+int shape_fault(int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, int64_t ranks) {
+    if (B <= 0 || T <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0 || C < 1 || C > 64 || ranks < 1) return 1;
+    if (T >= (1 << 15) || H >= (1 << 15) || W >= (1 << 15)) return 2;      // (keeps the products below in 64 bits)
+    return ranks * tok_lens(C, T, H, W).Ltok < MAX_KEYS ? 0 : 2;
+}
+// a sequence-parallel group the executor has a workspace for (sp_check refuses the rest of a bad descriptor, each part by name)
+bool sp_group_ok(const scail_dit_config& c, int32_t mode, int64_t ranks) {
+    if (ranks < 2 || (mode != SCAIL_SP_ALLGATHER && mode != SCAIL_SP_ULYSSES)) return false;
+    return mode != SCAIL_SP_ULYSSES || c.num_heads % ranks == 0;
 }
 
 // the character arguments of the *_chars entry points, checked first (host only; the message names the value)
@@ -92,35 +99,6 @@ int chars_check(const char* who, int64_t n_char, int64_t pose_frames, int64_t T)
         return 1;
     }
     return 0;
-}
-
-Ws layout(const scail_dit_config& c, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, int sp_mode = -1, int64_t ranks = 1, int64_t f8_k = 0) {
-    const int64_t D = c.hidden_size, FF = c.inner_hidden_size;
-    const TokLens tl = tok_lens(C, T, H, W);
-    const int64_t Lnoise = tl.Lnoise, Ltok = tl.Ltok;
-    Ws s;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { const int64_t o = off; off += align256(bytes); return o; };
-    s.tok = take(B * Ltok * KPAD * 2);
-    s.h = take(B * Ltok * D * 2);
-    s.xn = take(B * Ltok * D * 2);
-    s.qkv = take(B * Ltok * 3 * D * 2);
-    s.att = take(B * Ltok * D * 2);
-    s.ff = take(B * Ltok * FF * 2);
-    s.vt = take(vt_elems(c, B, Ltok, sp_mode, ranks) * 2);
-    s.xf = take(B * Lnoise * D * 2);
-    s.tokout = take(B * Lnoise * 64 * 2);
-    s.temb = take(B * c.time_freq_dim * 4);
-    s.e1 = take(B * c.time_embed_dim * 4);
-    s.emb = take(B * c.time_embed_dim * 4);
-    s.adaln = take(B * 6 * D * 4);
-    s.mod = take((int64_t)c.num_layers * B * 6 * D * 4);
-    s.emb2 = take(B * 2 * D * 4);
-    s.fin = take(B * 2 * D * 4);
-    s.xq = f8_k ? take(B * Ltok * f8_k) : 0;
-    s.sx = f8_k ? take(B * Ltok * 4) : 0;
-    s.total = off;
-    return s;
 }
 
 __global__ void dup_rows_kernel(const float* __restrict__ in, float* __restrict__ out, int64_t rows, int64_t w) {
@@ -165,15 +143,6 @@ struct RestartCount {
     }
     ~RestartCount() { if (on) (void)scail_flash_attn_count_restarts(nullptr); }
 };
-// one launch of category cat_, bracketed by an event pair when profiling is on
-#define DIT_PROF(cat_, call_)                                   \
-    {                                                           \
-        if (h->prof) DIT_TRY(prof_mark(h, cat_, stream));       \
-        RestartCount rc_guard_(h, cat_);                        \
-        DIT_TRY(call_);                                         \
-        if (h->prof) DIT_TRY(prof_mark(h, cat_, stream));       \
-    }
-
 // one launch of category cat_ on stream st_, bracketed by an event pair when profiling is on
 #define DIT_PROF_S(cat_, st_, call_)                            \
     {                                                           \
@@ -182,12 +151,7 @@ struct RestartCount {
         DIT_TRY(call_);                                         \
         if (h->prof) DIT_TRY(prof_mark(h, cat_, st_));          \
     }
-
-struct BlockBufs {
-    scail_bf16 *xn, *qkv, *att, *ff, *vt;
-    uint8_t* xq = nullptr;   // fp8 GEMMs only: e4m3 rows of the GEMM input and their scales (rows x the widest fp8 K)
-    float* sx = nullptr;
-};
+#define DIT_PROF(cat_, call_) DIT_PROF_S(cat_, stream, call_)
 
 // The per-token GEMMs of a block, by SCAIL_DIT_FP8_* bit index: (N, K) and the bf16 weight
 enum { G_QKV = 0, G_O, G_CQ, G_CO, G_W1, G_W2, G_COUNT };
@@ -210,6 +174,75 @@ static int64_t fp8_k(const scail_dit* h) {
             kmax = std::max(kmax, K);
         }
     return kmax;
+}
+
+// ---- workspaces: every layout is stated once; the *_workspace_bytes query and the call that checks it read the same struct ----
+struct BlockBufs {
+    scail_bf16 *xn, *qkv, *att, *ff, *vt;
+    uint8_t* xq;   // fp8 GEMMs only (else null): e4m3 rows of the GEMM input and their scales (rows x the widest fp8 K)
+    float* sx;
+};
+// The scratch of a (B, Ltok) block, xn | qkv | att | ff | vt | xq | sx, as byte offsets into a workspace from `at` on; end: the first
+// byte after it.  One rank (sp_mode < 0) or a sequence-parallel rank (bf16 only: xq / sx are empty there and without fp8 GEMMs)
+struct BlockWs {
+    int64_t xn, qkv, att, ff, vt, xq, sx, end;
+    BlockBufs bufs(void* workspace) const {
+        char* base = static_cast<char*>(workspace);
+        auto P = [&](int64_t o) { return reinterpret_cast<scail_bf16*>(base + o); };
+        const bool f8 = sx > xq;
+        return {P(xn), P(qkv), P(att), P(ff), P(vt), f8 ? reinterpret_cast<uint8_t*>(base + xq) : nullptr, f8 ? reinterpret_cast<float*>(base + sx) : nullptr};
+    }
+};
+static BlockWs block_ws(const scail_dit* h, int64_t B, int64_t Ltok, int sp_mode = -1, int64_t ranks = 1, int64_t at = 0) {
+    const int64_t D = h->cfg.hidden_size, FF = h->cfg.inner_hidden_size, rows = B * Ltok;
+    const int64_t f8_k = sp_mode < 0 ? fp8_k(h) : 0;
+    Carve c{at};
+    BlockWs s;
+    s.xn = c.take(rows * D * 2);
+    s.qkv = c.take(rows * 3 * D * 2);
+    s.att = c.take(rows * D * 2);
+    s.ff = c.take(rows * FF * 2);
+    s.vt = c.take(vt_elems(h->cfg, B, Ltok, sp_mode, ranks) * 2);
+    s.xq = c.take(rows * f8_k);
+    s.sx = c.take(f8_k ? rows * 4 : 0);
+    s.end = c.off;
+    return s;
+}
+// the step workspace: token assembly and hidden states, the block scratch, the final layer's rows, the time / AdaLN tables
+struct Ws {
+    int64_t tok, h, xf, tokout, temb, e1, emb, adaln, mod, emb2, fin, total;
+    BlockWs blk;
+};
+static Ws layout(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W, int64_t C, int sp_mode = -1, int64_t ranks = 1) {
+    const scail_dit_config& c = h->cfg;
+    const int64_t D = c.hidden_size;
+    const TokLens tl = tok_lens(C, T, H, W);
+    Ws s;
+    Carve cv;
+    s.tok = cv.take(B * tl.Ltok * KPAD * 2);
+    s.h = cv.take(B * tl.Ltok * D * 2);
+    s.blk = block_ws(h, B, tl.Ltok, sp_mode, ranks, cv.off);
+    cv.off = s.blk.end;
+    s.xf = cv.take(B * tl.Lnoise * D * 2);
+    s.tokout = cv.take(B * tl.Lnoise * 64 * 2);
+    s.temb = cv.take(B * c.time_freq_dim * 4);
+    s.e1 = cv.take(B * c.time_embed_dim * 4);
+    s.emb = cv.take(B * c.time_embed_dim * 4);
+    s.adaln = cv.take(B * 6 * D * 4);
+    s.mod = cv.take((int64_t)c.num_layers * B * 6 * D * 4);
+    s.emb2 = cv.take(B * 2 * D * 4);
+    s.fin = cv.take(B * 2 * D * 4);
+    s.total = cv.off;
+    return s;
+}
+// the sampler loops' workspace: the step workspace of the batch-2 evaluation (`step` bytes), then [x; x] and [v_u; v_c] of Tv frames and
+// (tiled) den of Tden frames, fp32.  step = 0: the part that needs no handle
+struct SampleWs {
+    int64_t xin, v, den, total;
+};
+static SampleWs sample_ws(int64_t step, int64_t Tv, int64_t H, int64_t W, int64_t Tden = 0) {
+    const int64_t F = 16 * H * W, pair = align256(2 * Tv * F * 4);
+    return {step, step + pair, step + 2 * pair, step + 2 * pair + align256(Tden * F * 4)};
 }
 
 // GEMM g of layer i: scail_gemm_bf16, or (SCAIL_DIT_FP8_* bit g enabled) the rows of x quantized to e4m3 into the block's scratch and
@@ -484,25 +517,13 @@ static int dit_block_sp(scail_dit* h, int64_t i, scail_bf16* hid, const float* m
 }
 
 // Seam B2 (SAT hook layer_forward): one block on caller-owned hidden states.  Workspace: scail_dit_block_workspace_bytes.
-// off[0..4]: xn, qkv, att, ff, vt; off[5..6]: the fp8 scratch (xq, sx; empty unless f8_k > 0)
-static int64_t block_ws(const scail_dit_config& c, int64_t B, int64_t Ltok, int sp_mode, int64_t ranks, int64_t* off, int64_t f8_k = 0) {
-    const int64_t D = c.hidden_size, FF = c.inner_hidden_size;
-    int64_t o = 0;
-    const int64_t sizes[7] = {B * Ltok * D * 2, B * Ltok * 3 * D * 2, B * Ltok * D * 2, B * Ltok * FF * 2, vt_elems(c, B, Ltok, sp_mode, ranks) * 2,
-                              B * Ltok * f8_k, f8_k ? B * Ltok * 4 : 0};
-    for (int j = 0; j < 7; ++j) { off[j] = o; o += align256(sizes[j]); }
-    return o;
-}
 extern "C" int64_t scail_dit_block_workspace_bytes(const scail_dit* h, int64_t B, int64_t Ltok) {
     if (h == nullptr || B <= 0 || Ltok <= 0) return -1;
-    int64_t off[7];
-    return block_ws(h->cfg, B, Ltok, -1, 1, off, fp8_k(h));
+    return block_ws(h, B, Ltok).end;
 }
 extern "C" int64_t scail_dit_block_sp_workspace_bytes(const scail_dit* h, int32_t mode, int32_t ranks, int64_t B, int64_t Ltok) {
-    if (h == nullptr || B <= 0 || Ltok <= 0 || ranks < 2 || (mode != SCAIL_SP_ALLGATHER && mode != SCAIL_SP_ULYSSES)) return -1;
-    if (mode == SCAIL_SP_ULYSSES && h->cfg.num_heads % ranks != 0) return -1;
-    int64_t off[7];
-    return block_ws(h->cfg, B, Ltok, mode, ranks, off);
+    if (h == nullptr || B <= 0 || Ltok <= 0 || !sp_group_ok(h->cfg, mode, ranks)) return -1;
+    return block_ws(h, B, Ltok, mode, ranks).end;
 }
 extern "C" int scail_dit_block_sp(scail_dit* h, int64_t layer, scail_bf16* hidden, const float* mod, const scail_dit_cond* cond,
                                   const float* rope_cos, const float* rope_sin, int64_t B, int64_t Ltok, const scail_dit_sp* sp,
@@ -510,32 +531,20 @@ extern "C" int scail_dit_block_sp(scail_dit* h, int64_t layer, scail_bf16* hidde
     SCAIL_REQUIRE(h != nullptr && hidden != nullptr && mod != nullptr && cond != nullptr, "null argument");
     SCAIL_REQUIRE(layer >= 0 && layer < h->cfg.num_layers && B > 0 && Ltok > 0, "bad layer / shape");
     DIT_TRY(sp_check(h, sp));
-    int64_t off[7];
-    const int64_t need = block_ws(h->cfg, B, Ltok, sp->mode, sp->ranks, off);
-    SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+    const BlockWs s = block_ws(h, B, Ltok, sp->mode, sp->ranks);
+    SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= s.end && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                   "workspace too small or not 256-byte aligned (scail_dit_block_sp_workspace_bytes)");
-    char* base = static_cast<char*>(workspace);
-    auto P = [&](int j) { return reinterpret_cast<scail_bf16*>(base + off[j]); };
-    const BlockBufs bf{P(0), P(1), P(2), P(3), P(4)};
-    return dit_block_sp(h, layer, hidden, mod, cond, rope_cos, rope_sin, B, Ltok, bf, sp, 0, Ltok, false, stream);
+    return dit_block_sp(h, layer, hidden, mod, cond, rope_cos, rope_sin, B, Ltok, s.bufs(workspace), sp, 0, Ltok, false, stream);
 }
 extern "C" int scail_dit_block(scail_dit* h, int64_t layer, scail_bf16* hidden, const float* mod, const scail_dit_cond* cond,
                                const float* rope_cos, const float* rope_sin, int64_t B, int64_t Ltok,
                                void* workspace, int64_t workspace_bytes, void* stream) {
     SCAIL_REQUIRE(h != nullptr && hidden != nullptr && mod != nullptr && cond != nullptr, "null argument");
     SCAIL_REQUIRE(layer >= 0 && layer < h->cfg.num_layers && B > 0 && Ltok > 0, "bad layer / shape");
-    int64_t off[7];
-    const int64_t need = block_ws(h->cfg, B, Ltok, -1, 1, off, fp8_k(h));
-    SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+    const BlockWs s = block_ws(h, B, Ltok);
+    SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= s.end && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                   "workspace too small or not 256-byte aligned (scail_dit_block_workspace_bytes)");
-    char* base = static_cast<char*>(workspace);
-    auto P = [&](int j) { return reinterpret_cast<scail_bf16*>(base + off[j]); };
-    BlockBufs bf{P(0), P(1), P(2), P(3), P(4)};
-    if (h->fp8) {
-        bf.xq = reinterpret_cast<uint8_t*>(base + off[5]);
-        bf.sx = reinterpret_cast<float*>(base + off[6]);
-    }
-    return dit_block(h, layer, hidden, mod, cond, rope_cos, rope_sin, B, Ltok, bf, 0, Ltok, false, stream);
+    return dit_block(h, layer, hidden, mod, cond, rope_cos, rope_sin, B, Ltok, s.bufs(workspace), 0, Ltok, false, stream);
 }
 
 extern "C" int scail_dit_create(const scail_dit_config* cfg, const scail_dit_weights* w, scail_dit** out) {
@@ -686,63 +695,19 @@ extern "C" int scail_dit_profile_read(scail_dit* h, int category, double* ms_tot
 
 // The *_chars entry points take the character count; the entry points without it are their n_char == 1 form.
 extern "C" int64_t scail_dit_chars_workspace_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W, int64_t n_char) {
-    if (h == nullptr || !shape_ok(B, T, H, W, n_char, 1)) return -1;
-    return layout(h->cfg, B, T, H, W, n_char, -1, 1, fp8_k(h)).total;
+    if (h == nullptr || shape_fault(B, T, H, W, n_char, 1) != 0) return -1;
+    return layout(h, B, T, H, W, n_char).total;
 }
 extern "C" int64_t scail_dit_workspace_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W) {
     return scail_dit_chars_workspace_bytes(h, B, T, H, W, 1);
 }
 extern "C" int64_t scail_dit_sp_chars_workspace_bytes(const scail_dit* h, int32_t mode, int32_t ranks, int64_t B, int64_t T, int64_t H, int64_t W,
                                                       int64_t n_char) {
-    if (h == nullptr || ranks < 2 || !shape_ok(B, T, H, W, n_char, ranks)) return -1;
-    if (mode != SCAIL_SP_ALLGATHER && mode != SCAIL_SP_ULYSSES) return -1;
-    if (mode == SCAIL_SP_ULYSSES && h->cfg.num_heads % ranks != 0) return -1;
-    return layout(h->cfg, B, T, H, W, n_char, mode, ranks).total;
+    if (h == nullptr || !sp_group_ok(h->cfg, mode, ranks) || shape_fault(B, T, H, W, n_char, ranks) != 0) return -1;
+    return layout(h, B, T, H, W, n_char, mode, ranks).total;
 }
 extern "C" int64_t scail_dit_sp_workspace_bytes(const scail_dit* h, int32_t mode, int32_t ranks, int64_t B, int64_t T, int64_t H, int64_t W) {
     return scail_dit_sp_chars_workspace_bytes(h, mode, ranks, B, T, H, W, 1);
-}
-
-static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
-                         const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
-                         const float* rope_cos, const float* rope_sin, float* out,
-                         int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace, int64_t workspace_bytes,
-                         void* stream);
-
-extern "C" int scail_dit_step_chars(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
-                                    const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
-                                    const float* rope_cos, const float* rope_sin, float* out,
-                                    int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes,
-                                    void* stream) {
-    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, n_char, pose_frames, rope_cos, rope_sin, out, B, T, H, W, nullptr, flags,
-                         workspace, workspace_bytes, stream);
-}
-extern "C" int scail_dit_step(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
-                              const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose,
-                              const float* rope_cos, const float* rope_sin, float* out,
-                              int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes,
-                              void* stream) {
-    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, 1, T, rope_cos, rope_sin, out, B, T, H, W, nullptr, flags, workspace,
-                         workspace_bytes, stream);
-}
-
-extern "C" int scail_dit_step_sp_chars(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
-                                       const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char,
-                                       int64_t pose_frames, const float* rope_cos, const float* rope_sin, float* out,
-                                       int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace,
-                                       int64_t workspace_bytes, void* stream) {
-    SCAIL_REQUIRE(h != nullptr, "null handle");
-    DIT_TRY(sp_check(h, sp));
-    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, n_char, pose_frames, rope_cos, rope_sin, out, B, T, H, W, sp, flags,
-                         workspace, workspace_bytes, stream);
-}
-extern "C" int scail_dit_step_sp(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
-                                 const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose,
-                                 const float* rope_cos, const float* rope_sin, float* out,
-                                 int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace,
-                                 int64_t workspace_bytes, void* stream) {
-    return scail_dit_step_sp_chars(h, x, timesteps, cond, ref, n_ref, pose, n_pose, 1, T, rope_cos, rope_sin, out, B, T, H, W, sp, flags, workspace,
-                                   workspace_bytes, stream);
 }
 
 // x (B, T, 16, H, W): the whole latent (sp == nullptr) or this rank's H- or W-slab of it (rope tables rank-shifted by the host).
@@ -759,9 +724,10 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
     SCAIL_REQUIRE((flags & ~(uint32_t)SCAIL_DIT_CFG_PAIR) == 0, "unknown step flag");
     SCAIL_REQUIRE(!(flags & SCAIL_DIT_CFG_PAIR) || (B == 2 && n_ref == 1 && n_pose == 1),
                   "SCAIL_DIT_CFG_PAIR needs B == 2 with one shared ref / pose (element 1 = element 0 except for the conditioning)");
-    SCAIL_REQUIRE(B > 0 && B <= 8 && T > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, "latent batch must be 1..8, H and W multiples of 4");
     const int64_t ranks = sp ? sp->ranks : 1;
-    if (!shape_ok(B, T, H, W, n_char, ranks)) {
+    const int bad_shape = shape_fault(B, T, H, W, n_char, ranks);
+    SCAIL_REQUIRE(B <= 8 && bad_shape != 1, "latent batch must be 1..8, H and W multiples of 4");
+    if (bad_shape != 0) {
         scail_set_error("scail_dit_step: the self-attention takes fewer than 2^31 - 64 keys, got Ltok = " + std::to_string(tok_lens(n_char, T, H, W).Ltok) +
                         " tokens x " + std::to_string(ranks) + " rank(s) (T, H, W must be below 32768)");
         return 1;
@@ -769,7 +735,7 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
     SCAIL_REQUIRE((n_ref == 1 || n_ref == B) && (n_pose == 1 || n_pose == B), "ref / pose batch must be 1 or B");
     SCAIL_REQUIRE(cond->Bc == 1 || cond->Bc == B, "clip batch must be 1 or B");
     const scail_dit_config& c = h->cfg;
-    const Ws s = sp ? layout(c, B, T, H, W, n_char, sp->mode, sp->ranks) : layout(c, B, T, H, W, n_char, -1, 1, fp8_k(h));
+    const Ws s = sp ? layout(h, B, T, H, W, n_char, sp->mode, sp->ranks) : layout(h, B, T, H, W, n_char);
     SCAIL_REQUIRE(c.time_embed_dim == c.hidden_size, "final-layer table add needs time_embed_dim == hidden_size");
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= s.total, "workspace too small (scail_dit_workspace_bytes)");
     SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
@@ -781,8 +747,7 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
     char* base = static_cast<char*>(workspace);
     auto B16 = [&](int64_t off) { return reinterpret_cast<scail_bf16*>(base + off); };
     auto F32 = [&](int64_t off) { return reinterpret_cast<float*>(base + off); };
-    scail_bf16 *tok = B16(s.tok), *hid = B16(s.h), *xn = B16(s.xn), *qkv = B16(s.qkv), *att = B16(s.att), *ff = B16(s.ff);
-    scail_bf16 *vt = B16(s.vt), *xf = B16(s.xf), *tokout = B16(s.tokout);
+    scail_bf16 *tok = B16(s.tok), *hid = B16(s.h), *xf = B16(s.xf), *tokout = B16(s.tokout);
     float *temb = F32(s.temb), *e1 = F32(s.e1), *emb = F32(s.emb), *adaln = F32(s.adaln), *mod = F32(s.mod);
     float *emb2 = F32(s.emb2), *fin = F32(s.fin);
     const scail_dit_weights& w = h->w;
@@ -817,11 +782,7 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
                                 KPAD, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
     }
 
-    BlockBufs bf{xn, qkv, att, ff, vt};
-    if (h->fp8) {
-        bf.xq = reinterpret_cast<uint8_t*>(base + s.xq);
-        bf.sx = F32(s.sx);
-    }
+    const BlockBufs bf = s.blk.bufs(workspace);
     for (int64_t i = 0; i < nl; ++i) {
         // the last layer's output is only read at the noise tokens (final layer below): queries / out-projection / cross attention /
         // MLP of its ref and pose rows are skipped (23 % of that layer's post-K/V work; same result)
@@ -841,12 +802,46 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
     return 0;
 }
 
+extern "C" int scail_dit_step_chars(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
+                                    const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
+                                    const float* rope_cos, const float* rope_sin, float* out,
+                                    int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes,
+                                    void* stream) {
+    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, n_char, pose_frames, rope_cos, rope_sin, out, B, T, H, W, nullptr, flags,
+                         workspace, workspace_bytes, stream);
+}
+extern "C" int scail_dit_step(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
+                              const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose,
+                              const float* rope_cos, const float* rope_sin, float* out,
+                              int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes,
+                              void* stream) {
+    return scail_dit_step_chars(h, x, timesteps, cond, ref, n_ref, pose, n_pose, 1, T, rope_cos, rope_sin, out, B, T, H, W, flags, workspace,
+                                workspace_bytes, stream);
+}
+
+extern "C" int scail_dit_step_sp_chars(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
+                                       const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char,
+                                       int64_t pose_frames, const float* rope_cos, const float* rope_sin, float* out,
+                                       int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace,
+                                       int64_t workspace_bytes, void* stream) {
+    SCAIL_REQUIRE(h != nullptr, "null handle");
+    DIT_TRY(sp_check(h, sp));
+    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, n_char, pose_frames, rope_cos, rope_sin, out, B, T, H, W, sp, flags,
+                         workspace, workspace_bytes, stream);
+}
+extern "C" int scail_dit_step_sp(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
+                                 const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose,
+                                 const float* rope_cos, const float* rope_sin, float* out,
+                                 int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace,
+                                 int64_t workspace_bytes, void* stream) {
+    return scail_dit_step_sp_chars(h, x, timesteps, cond, ref, n_ref, pose, n_pose, 1, T, rope_cos, rope_sin, out, B, T, H, W, sp, flags, workspace,
+                                   workspace_bytes, stream);
+}
+
 // ---- the sampler loop (RFSampler.__call__ + VanillaCFG, sampling.py:920-982, guiders.py:41-57) ----
 extern "C" int64_t scail_dit_sample_chars_workspace_bytes(const scail_dit* h, int64_t T, int64_t H, int64_t W, int64_t n_char) {
     const int64_t step = scail_dit_chars_workspace_bytes(h, 2, T, H, W, n_char);
-    if (step < 0) return -1;
-    const int64_t n = T * 16 * H * W;
-    return step + 2 * align256(2 * n * 4);     // + [x; x] and [v_u; v_c], fp32
+    return step < 0 ? -1 : sample_ws(step, T, H, W).total;
 }
 extern "C" int64_t scail_dit_sample_workspace_bytes(const scail_dit* h, int64_t T, int64_t H, int64_t W) {
     return scail_dit_sample_chars_workspace_bytes(h, T, H, W, 1);
@@ -868,11 +863,11 @@ extern "C" int scail_dit_sample_chars(scail_dit* h, float* x, const float* times
     SCAIL_REQUIRE(h != nullptr && x != nullptr && timesteps != nullptr && dsigma != nullptr && n_steps >= 0, "null argument");
     const int64_t step_bytes = scail_dit_chars_workspace_bytes(h, 2, T, H, W, n_char);
     SCAIL_REQUIRE(step_bytes >= 0, "bad latent shape");
-    const int64_t n = T * 16 * H * W, pair = align256(2 * n * 4);
-    SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= step_bytes + 2 * pair, "workspace too small (scail_dit_sample_workspace_bytes)");
+    const SampleWs ws = sample_ws(step_bytes, T, H, W);
+    SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= ws.total, "workspace too small (scail_dit_sample_workspace_bytes)");
     char* base = static_cast<char*>(workspace);
-    float* xin = reinterpret_cast<float*>(base + step_bytes);
-    float* v = reinterpret_cast<float*>(base + step_bytes + pair);
+    float *xin = reinterpret_cast<float*>(base + ws.xin), *v = reinterpret_cast<float*>(base + ws.v);
+    const int64_t n = T * 16 * H * W;
     hipStream_t s = (hipStream_t)stream;
     for (int64_t i = 0; i < n_steps; ++i) {
         // torch.cat([x] * 2) of VanillaCFG.prepare_inputs (guiders.py:56)
@@ -890,11 +885,9 @@ extern "C" int scail_dit_sample_chars(scail_dit* h, float* x, const float* times
 
 // ---- the tiled sampler loop (RFSamplerLong, sampling.py:986-1085; scail_amd/sampler.py RFSamplerLong.sample_hip is the host form) ----
 extern "C" int64_t scail_dit_sample_tiled_workspace_bytes(const scail_dit* h, int64_t T, int64_t Tt, int64_t H, int64_t W) {
-    if (T < 1 || Tt < 1 || Tt > T || Tt > 64 || T >= (1 << 15)) return -1;
+    if (T >= (1 << 15) || scail_tile_len_check(nullptr, Tt, T) != 0) return -1;
     const int64_t step = scail_dit_chars_workspace_bytes(h, 2, Tt, H, W, 1);
-    if (step < 0) return -1;
-    const int64_t F = 16 * H * W;
-    return step + 2 * align256(2 * Tt * F * 4) + align256(T * F * 4);     // + [x_k; x_k], [v_u; v_c] of one tile and den, fp32
+    return step < 0 ? -1 : sample_ws(step, Tt, H, W, T).total;
 }
 
 extern "C" int scail_dit_sample_tiled(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
@@ -911,8 +904,7 @@ extern "C" int scail_dit_sample_tiled(scail_dit* h, float* x, const float* times
     if (n_tiles < 2)
         return fail("needs at least 2 tiles (a single tile leaves the weight sums of the reference at zero), got n_tiles = " + std::to_string(n_tiles));
     if (T >= (1 << 15)) return fail("the latent must have fewer than 32768 frames, got T = " + std::to_string(T));
-    if (T < 1 || Tt < 1 || Tt > 64 || Tt > T)
-        return fail("the tile length Tt must be 1..min(T, 64), got Tt = " + std::to_string(Tt) + " with T = " + std::to_string(T));
+    DIT_TRY(scail_tile_len_check(who, Tt, T));
     if (n_steps < 0) return fail("n_steps must be >= 0, got " + std::to_string(n_steps));
     if (tile_frames == nullptr) return fail("null pointer: tile_frames");
     if (tile_w == nullptr) return fail("null pointer: tile_w");
@@ -929,26 +921,25 @@ extern "C" int scail_dit_sample_tiled(scail_dit* h, float* x, const float* times
     }
     if (H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0 || H >= (1 << 15) || W >= (1 << 15))
         return fail("latent H and W must be positive multiples of 4 below 32768, got H = " + std::to_string(H) + ", W = " + std::to_string(W));
-    const int64_t F = 16 * H * W, pair = align256(2 * Tt * F * 4), den_bytes = align256(T * F * 4);
-    if (workspace_bytes < 2 * pair + den_bytes)      // the handle-independent part, so this answers without a handle too
+    const int64_t own = sample_ws(0, Tt, H, W, T).total;      // the handle-independent part, so this answers without a handle too
+    if (workspace_bytes < own)
         return fail("workspace too small: " + std::to_string(workspace_bytes) + " bytes cannot hold the tile pair buffers and den (" +
-                    std::to_string(2 * pair + den_bytes) + " bytes) next to the step workspace (scail_dit_sample_tiled_workspace_bytes)");
+                    std::to_string(own) + " bytes) next to the step workspace (scail_dit_sample_tiled_workspace_bytes)");
     const void* ptrs[] = {h, x, timesteps, dsigma, cond, ref, pose_tiles, rope_cos, rope_sin, workspace};
     const char* names[] = {"handle", "x", "timesteps", "dsigma", "cond", "ref", "pose_tiles", "rope_cos", "rope_sin", "workspace"};
     for (int i = 0; i < 10; ++i)
         if (ptrs[i] == nullptr && !(i == 3 && n_steps == 0)) return fail(std::string("null pointer: ") + names[i]);
     const int64_t step_bytes = scail_dit_chars_workspace_bytes(h, 2, Tt, H, W, 1);
     if (step_bytes < 0) return fail("bad latent shape (Tt " + std::to_string(Tt) + ", H " + std::to_string(H) + ", W " + std::to_string(W) + ")");
-    if (workspace_bytes < step_bytes + 2 * pair + den_bytes)
-        return fail("workspace too small: " + std::to_string(workspace_bytes) + " bytes, needs " + std::to_string(step_bytes + 2 * pair + den_bytes) +
+    const SampleWs ws = sample_ws(step_bytes, Tt, H, W, T);
+    if (workspace_bytes < ws.total)
+        return fail("workspace too small: " + std::to_string(workspace_bytes) + " bytes, needs " + std::to_string(ws.total) +
                     " (scail_dit_sample_tiled_workspace_bytes)");
     SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
 
     char* base = static_cast<char*>(workspace);
-    float* xin = reinterpret_cast<float*>(base + step_bytes);
-    float* v = reinterpret_cast<float*>(base + step_bytes + pair);
-    float* den = reinterpret_cast<float*>(base + step_bytes + 2 * pair);
-    const int64_t pose_tile = Tt * 16 * (H / 2) * (W / 2);
+    float *xin = reinterpret_cast<float*>(base + ws.xin), *v = reinterpret_cast<float*>(base + ws.v), *den = reinterpret_cast<float*>(base + ws.den);
+    const int64_t F = 16 * H * W, pose_tile = Tt * 16 * (H / 2) * (W / 2);
     // den starts at zero; scail_tile_finish leaves it zeroed for the next step
     if (n_steps > 0) DIT_TRY(scail_zero_f32(den, T * F, stream));
     for (int64_t i = 0; i < n_steps; ++i) {

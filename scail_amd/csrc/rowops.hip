@@ -863,11 +863,14 @@ extern "C" int scail_cfg_euler(float* x, const float* v, int64_t n, float cfg_sc
 // ---- temporal tiling: host-side checks (the message names the value) + launches ----
 // Tt in 1..min(T, 64), every frame index in [0, T) and, `unique`, no index twice (two tile frames would accumulate into one latent frame
 // concurrently).  Shared with the sampler entry point (dit_step.hip), which checks every tile before anything is enqueued.
-int scail_tile_check(const char* who, const int32_t* frames, int64_t Tt, int64_t T, bool unique) {
-    if (T < 1 || Tt < 1 || Tt > TILE_MAX || Tt > T) {
+int scail_tile_len_check(const char* who, int64_t Tt, int64_t T) {
+    if (T >= 1 && Tt >= 1 && Tt <= TILE_MAX && Tt <= T) return 0;
+    if (who != nullptr)
         scail_set_error(std::string(who) + ": the tile length Tt must be 1..min(T, 64), got Tt = " + std::to_string(Tt) + " with T = " + std::to_string(T));
-        return 1;
-    }
+    return 1;
+}
+int scail_tile_check(const char* who, const int32_t* frames, int64_t Tt, int64_t T, bool unique) {
+    if (int rc = scail_tile_len_check(who, Tt, T)) return rc;
     if (frames == nullptr) {
         scail_set_error(std::string(who) + ": null pointer: frames");
         return 1;

@@ -90,11 +90,11 @@ class CStep:
             L.call("scail_dit_enable_fp8", self._h, 0, None, 0, torch.cuda.current_stream(device).cuda_stream)
             self._fp8_buf = None
             return
-        need = lib.scail_dit_fp8_weight_bytes(self._h, which)
-        if need < 0:
+        nbytes = lib.scail_dit_fp8_weight_bytes(self._h, which)
+        if nbytes < 0:
             raise L.ScailHipError(f"scail_dit_fp8_weight_bytes: bad mask {which}")
-        buf = torch.empty(need, device=device, dtype=torch.uint8)
-        L.call("scail_dit_enable_fp8", self._h, which, buf.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream)
+        buf = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        L.call("scail_dit_enable_fp8", self._h, which, buf.data_ptr(), nbytes, torch.cuda.current_stream(device).cuda_stream)
         self._fp8_buf = buf
 
     def close(self):
@@ -122,6 +122,22 @@ class CStep:
         L.call("scail_dit_profile_read", self._h, category, C.byref(ms), C.byref(n))
         return ms.value, n.value
 
+    def _ws_for(self, need: int, device, what: str) -> torch.Tensor:
+        """The workspace, grown to ``need`` bytes on ``device``; ``what`` names the query that answered ``need`` and what it was asked."""
+        if need < 0:
+            raise L.ScailHipError(f"{what}: the executor has no workspace for this request (bad shape / mode)")
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = torch.empty(need, device=device, dtype=torch.uint8)
+        return self._ws
+
+    @staticmethod
+    def _schedule(sigmas, device):
+        """(timesteps (n, 2) device fp32 = 1000 sigma_i twice, sigma_{i+1} - sigma_i as a host float array, n) of the host schedule"""
+        sig = sigmas.float().cpu()
+        n = sig.numel() - 1
+        ts = (sig[:-1] * 1000.0).repeat_interleave(2).to(device).contiguous()
+        return ts, (C.c_float * n)(*[float(v) for v in (sig[1:] - sig[:-1])]), n
+
     def workspace_bytes(self, B, T, H, W, n_char: int = 1) -> int:
         n = L.load().scail_dit_chars_workspace_bytes(self._h, B, T, H, W, n_char)
         if n < 0:
@@ -135,41 +151,26 @@ class CStep:
         its first cross attention is evaluated once (SCAIL_DIT_CFG_PAIR; bit-identical on such inputs).  ``n_char``: characters in
         ``ref`` (n, n_char, 16, H, W) / ``pose`` (n, n_char * T, 16, H/2, W/2); cos / sin from rope.build_tables(n_char=n_char)."""
         B, T, _, H, W = x32.shape
-        need = self.workspace_bytes(B, T, H, W, n_char)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != x32.device:
-            self._ws = torch.empty(need, device=x32.device, dtype=torch.uint8)
-        k_text, k_clip = cond["k_text"], cond["k_clip"]
-        cc = DitCond(k_text.data_ptr(), cond["vt_text"].data_ptr(), k_clip.data_ptr(), cond["vt_clip"].data_ptr(),
-                     k_text.shape[2], k_clip.shape[2], k_clip.shape[1])
+        ws = self._ws_for(self.workspace_bytes(B, T, H, W, n_char), x32.device, "scail_dit_chars_workspace_bytes")
+        cc = _cond_struct(cond)
         out = torch.empty(B, T, 16, H, W, device=x32.device, dtype=torch.float32)
         L.call("scail_dit_step_chars", self._h, x32.data_ptr(), t32.data_ptr(), C.byref(cc), ref.data_ptr(), ref.shape[0],
                pose.data_ptr(), pose.shape[0], n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), out.data_ptr(), B, T, H, W,
-               self.CFG_PAIR if cfg_pair else 0, self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream().cuda_stream)
+               self.CFG_PAIR if cfg_pair else 0, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
         return out
 
     def sample(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose, cos, sin, n_char: int = 1) -> torch.Tensor:
         """The whole Euler loop in one C call (scail_dit_sample_chars).  x32 (1,T,16,H,W) fp32 is updated in place and returned;
         ``sigmas`` is the host schedule (n_steps + 1 values); ``cond`` the batch-2 conditioning (uncond, cond); ``n_char`` as for step."""
-        import ctypes as C2
         _, T, _, H, W = x32.shape
-        lib = L.load()
-        need = lib.scail_dit_sample_chars_workspace_bytes(self._h, T, H, W, n_char)
-        if need < 0:
-            raise L.ScailHipError(f"scail_dit_sample_chars_workspace_bytes: bad shape (T {T}, H {H}, W {W}, n_char {n_char})")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != x32.device:
-            self._ws = torch.empty(need, device=x32.device, dtype=torch.uint8)
-        sig = sigmas.float().cpu()
-        n = sig.numel() - 1
-        ts = (sig[:-1] * 1000.0).repeat_interleave(2).to(x32.device).contiguous()       # (n, 2) device fp32
-        ds = (sig[1:] - sig[:-1]).contiguous()
-        dsa = (C2.c_float * n)(*[float(v) for v in ds])
-        k_text, k_clip = cond["k_text"], cond["k_clip"]
-        cc = DitCond(k_text.data_ptr(), cond["vt_text"].data_ptr(), k_clip.data_ptr(), cond["vt_clip"].data_ptr(),
-                     k_text.shape[2], k_clip.shape[2], k_clip.shape[1])
+        ws = self._ws_for(L.load().scail_dit_sample_chars_workspace_bytes(self._h, T, H, W, n_char), x32.device,
+                          f"scail_dit_sample_chars_workspace_bytes (T {T}, H {H}, W {W}, n_char {n_char})")
+        ts, dsa, n = self._schedule(sigmas, x32.device)
+        cc = _cond_struct(cond)
         assert x32.is_contiguous() and x32.dtype == torch.float32 and ref.shape[0] == 1 and pose.shape[0] == 1
-        L.call("scail_dit_sample_chars", self._h, x32.data_ptr(), ts.data_ptr(), C2.cast(dsa, C2.c_void_p), n, float(cfg_scale),
-               C2.byref(cc), ref.data_ptr(), pose.data_ptr(), n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), T, H, W,
-               self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream().cuda_stream)
+        L.call("scail_dit_sample_chars", self._h, x32.data_ptr(), ts.data_ptr(), C.cast(dsa, C.c_void_p), n, float(cfg_scale),
+               C.byref(cc), ref.data_ptr(), pose.data_ptr(), n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), T, H, W,
+               ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
         return x32
 
     def sample_tiled_workspace_bytes(self, T, Tt, H, W) -> int:
@@ -193,12 +194,8 @@ class CStep:
         _, T, _, H, W = x32.shape
         n_tiles = len(tile_indices)
         Tt = len(tile_indices[0]) if n_tiles else 0
-        need = self.sample_tiled_workspace_bytes(T, Tt, H, W)
-        ws = self._ws_for(need, x32.device)
-        sig = sigmas.float().cpu()
-        n = sig.numel() - 1
-        ts = (sig[:-1] * 1000.0).repeat_interleave(2).to(x32.device).contiguous()       # (n, 2) device fp32
-        dsa = (C.c_float * n)(*[float(v) for v in (sig[1:] - sig[:-1])])
+        ws = self._ws_for(self.sample_tiled_workspace_bytes(T, Tt, H, W), x32.device, "scail_dit_sample_tiled_workspace_bytes")
+        ts, dsa, n = self._schedule(sigmas, x32.device)
         fr, tw, iw = self.tile_tables(tile_indices, tile_w, inv_wsum)
         cc = _cond_struct(cond)
         assert x32.is_contiguous() and x32.dtype == torch.float32 and ref.shape[0] == 1 and pose_tiles.is_contiguous()
@@ -212,16 +209,12 @@ class CStep:
         """Seam B2: one transformer block in place on ``hidden`` (B, Ltok, D) bf16; ``mod`` (B, 6D) fp32 = adaLN embedding +
         this layer's table.  Returns ``hidden``."""
         B, Ltok, _ = hidden.shape
-        lib = L.load()
-        need = lib.scail_dit_block_workspace_bytes(self._h, B, Ltok)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != hidden.device:
-            self._ws = torch.empty(need, device=hidden.device, dtype=torch.uint8)
-        k_text, k_clip = cond["k_text"], cond["k_clip"]
-        cc = DitCond(k_text.data_ptr(), cond["vt_text"].data_ptr(), k_clip.data_ptr(), cond["vt_clip"].data_ptr(),
-                     k_text.shape[2], k_clip.shape[2], k_clip.shape[1])
+        ws = self._ws_for(L.load().scail_dit_block_workspace_bytes(self._h, B, Ltok), hidden.device,
+                          f"scail_dit_block_workspace_bytes (B {B}, Ltok {Ltok})")
+        cc = _cond_struct(cond)
         assert hidden.is_contiguous() and mod.is_contiguous() and mod.dtype == torch.float32
         L.call("scail_dit_block", self._h, layer, hidden.data_ptr(), mod.data_ptr(), C.byref(cc), cos.data_ptr(), sin.data_ptr(),
-               B, Ltok, self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream().cuda_stream)
+               B, Ltok, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
         return hidden
 
     # ---- sequence-parallel rank (include/scail_dit.h: scail_dit_step_sp / scail_dit_block_sp) ----
@@ -236,18 +229,12 @@ class CStep:
                 raise xch.error
             raise
 
-    def _ws_for(self, need, device):
-        if need < 0:
-            raise L.ScailHipError("sequence-parallel workspace: bad shape / mode")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, device=device, dtype=torch.uint8)
-        return self._ws
-
     def step_sp(self, x32, t32, cond: Dict, ref, pose, cos, sin, xch, cfg_pair: bool = False, n_char: int = 1) -> torch.Tensor:
         """One network evaluation on this rank's latent slab (scail_dit_step_sp_chars); ``xch`` owns the exchange buffers and issues the
         collectives from the executor's callback.  ``ref`` / ``pose`` are the rank's slabs of all ``n_char`` characters."""
         B, T, _, H, W = x32.shape
-        ws = self._ws_for(L.load().scail_dit_sp_chars_workspace_bytes(self._h, xch.mode_code, xch.size, B, T, H, W, n_char), x32.device)
+        ws = self._ws_for(L.load().scail_dit_sp_chars_workspace_bytes(self._h, xch.mode_code, xch.size, B, T, H, W, n_char), x32.device,
+                          f"scail_dit_sp_chars_workspace_bytes (mode {xch.mode_code}, {xch.size} ranks, B {B}, T {T}, H {H}, W {W}, n_char {n_char})")
         cc, sp = _cond_struct(cond), xch.descriptor()
         out = torch.empty(B, T, 16, H, W, device=x32.device, dtype=torch.float32)
         self._sp_call("scail_dit_step_sp_chars", xch, self._h, x32.data_ptr(), t32.data_ptr(), C.byref(cc), ref.data_ptr(), ref.shape[0],
@@ -258,7 +245,8 @@ class CStep:
     def block_sp(self, layer: int, hidden: torch.Tensor, mod: torch.Tensor, cond: Dict, cos, sin, xch) -> torch.Tensor:
         """Seam B2 for a sequence-parallel rank: one block in place on this rank's ``hidden`` (B, Ltok, D)."""
         B, Ltok, _ = hidden.shape
-        ws = self._ws_for(L.load().scail_dit_block_sp_workspace_bytes(self._h, xch.mode_code, xch.size, B, Ltok), hidden.device)
+        ws = self._ws_for(L.load().scail_dit_block_sp_workspace_bytes(self._h, xch.mode_code, xch.size, B, Ltok), hidden.device,
+                          f"scail_dit_block_sp_workspace_bytes (mode {xch.mode_code}, {xch.size} ranks, B {B}, Ltok {Ltok})")
         cc, sp = _cond_struct(cond), xch.descriptor()
         assert hidden.is_contiguous() and mod.is_contiguous() and mod.dtype == torch.float32
         self._sp_call("scail_dit_block_sp", xch, self._h, layer, hidden.data_ptr(), mod.data_ptr(), C.byref(cc), cos.data_ptr(), sin.data_ptr(),

@@ -57,6 +57,12 @@ def _register(root: nn.Module, path: str, p: nn.Parameter):
     mod.register_parameter(parts[-1], p)
 
 
+def _as_bf16(t: torch.Tensor, dev) -> torch.Tensor:
+    """t on ``dev`` as contiguous bf16 (fp32 through the library's own rounding kernel)"""
+    t = t.to(dev)
+    return ops.to_bf16(t.contiguous()) if t.dtype == torch.float32 else t.to(torch.bfloat16).contiguous()
+
+
 def _fp8_options(gemm_precision, fp8_gemms):
     """("bf16" | "fp8", SCAIL_DIT_FP8_* mask) from the constructor options: fp8_gemms = None (all six per-token GEMMs), an iterable of
     names from lib.FP8_GEMMS, or the mask itself."""
@@ -433,17 +439,10 @@ class DiffusionTransformer(nn.Module):
         dev = x.device
         if dev.type != "cuda":
             raise L.ScailHipError("scail_amd.DiffusionTransformer.forward needs GPU tensors (no CPU path)")
-
-        def as_bf16(t):
-            t = t.to(dev)
-            return ops.to_bf16(t.contiguous()) if t.dtype == torch.float32 else t.to(torch.bfloat16).contiguous()
-
         x32 = x.float().contiguous() if x.dtype != torch.float32 else x.contiguous()
         t32 = timesteps.to(dev).float().contiguous()
-        ctx = as_bf16(context)
-        ref = as_bf16(kwargs["ref_concat"])
-        pose = as_bf16(kwargs["concat_smpl_render"])
-        clip = as_bf16(kwargs["image_clip_features"])
+        ctx, ref, pose, clip = (_as_bf16(t, dev) for t in (context, kwargs["ref_concat"], kwargs["concat_smpl_render"],
+                                                           kwargs["image_clip_features"]))
         B, T, C, H, Wd = x32.shape
         H_shift = W_shift = 0
         chunk_dim = kwargs.get("chunk_dim", None)
@@ -466,53 +465,50 @@ class DiffusionTransformer(nn.Module):
             self._cfg_pair_checked = True
         return self._run(x32, t32, ctx, ref, pose, clip, H_shift, W_shift, cond_key, cfg_pair=cfg_pair)
 
+    def executor_ok(self, whole_loop: bool = False) -> bool:
+        """Whether the C executor (include/scail_dit.h) may run a request: C step on, no tap, no kernel timer (both instrument the per-op
+        path) and, for the calls that hold a whole sampler loop (``whole_loop``: sample_c / sample_tiled_c), one rank."""
+        return bool(self.use_c_step and self._tap is None and self.kernel_timer is None
+                    and not (whole_loop and self.sp is not None and self.sp.size > 1))
+
+    def _executor(self):
+        if self._cstep is None:
+            from .cstep import CStep
+            self._cstep = CStep(self, self.prepare())
+        return self._cstep
+
+    def _check_chars(self, n_char, T, pose_frames):
+        if pose_frames != n_char * T:
+            raise L.ScailHipError(f"concat_smpl_render needs {n_char} x {T} frames for {n_char} reference frame(s), got {pose_frames}")
+
+    def _sample_prelude(self, x32, ctx, clip, cond_key, T_rope, n_char):
+        """What the one-call samplers share: (executor, conditioning, RoPE tables of a T_rope-frame clip, the fp32 latent the call updates)"""
+        dev = x32.device
+        cond = self._conditioning(_as_bf16(ctx, dev), _as_bf16(clip, dev), cond_key)
+        cos, sin = self._rope(T_rope, x32.shape[3] // 2, x32.shape[4] // 2, 0, 0, dev, n_char)
+        return self._executor(), cond, cos, sin, x32.float().contiguous().clone()
+
     def sample_c(self, x32, sigmas, cfg_scale, ctx, ref, pose, clip, cond_key=None):
         """The whole RFSampler Euler loop as ONE C call (scail_dit_sample_chars, include/scail_dit.h): x32 (1,T,16,H,W) fp32,
         ctx (2, Lt, text_dim) = [uncond; cond], ref (1,C,16,H,W), pose (1,C*T,16,H/2,W/2) for C >= 1 characters (C = ref.shape[1]),
         clip (1,Lc,1280).  Single rank."""
-        from .cstep import CStep
-        W = self.prepare()
-        dev = x32.device
-
-        def as_bf16(t):
-            t = t.to(dev)
-            return ops.to_bf16(t.contiguous()) if t.dtype == torch.float32 else t.to(torch.bfloat16).contiguous()
-
-        _, T, _, H, Wd = x32.shape
-        n_char = ref.shape[1]
-        if pose.shape[1] != n_char * T:
-            raise L.ScailHipError(f"concat_smpl_render needs {n_char} x {T} frames for {n_char} reference frame(s), got {pose.shape[1]}")
-        cond = self._conditioning(as_bf16(ctx), as_bf16(clip), cond_key)
-        cos, sin = self._rope(T, H // 2, Wd // 2, 0, 0, dev, n_char)
-        if self._cstep is None:
-            self._cstep = CStep(self, W)
-        x = x32.float().contiguous().clone()
-        return self._cstep.sample(x, sigmas, cfg_scale, cond, as_bf16(ref), as_bf16(pose), cos, sin, n_char=n_char)
+        T, n_char, dev = x32.shape[1], ref.shape[1], x32.device
+        self._check_chars(n_char, T, pose.shape[1])
+        ex, cond, cos, sin, x = self._sample_prelude(x32, ctx, clip, cond_key, T, n_char)
+        return ex.sample(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, n_char=n_char)
 
     def sample_tiled_c(self, x32, sigmas, cfg_scale, ctx, ref, pose_tiles, clip, tile_indices, tile_w, inv_wsum, cond_key=None):
         """The whole RFSamplerLong loop (temporal tiling) as ONE C call (scail_dit_sample_tiled, include/scail_dit.h): x32 (1,T,16,H,W) fp32,
         ctx (2, Lt, text_dim) = [uncond; cond], ref (1,1,16,H,W), pose_tiles (1, n_tiles, Tt, 16, H/2, W/2), clip (1,Lc,1280);
         tile_w (n_tiles, Tt) = m_k * tile_weight and inv_wsum (T) as RFSamplerLong.sample_hip forms them.  Single rank, one character."""
-        from .cstep import CStep
-        W = self.prepare()
-        dev = x32.device
-
-        def as_bf16(t):
-            t = t.to(dev)
-            return ops.to_bf16(t.contiguous()) if t.dtype == torch.float32 else t.to(torch.bfloat16).contiguous()
-
-        _, T, _, H, Wd = x32.shape
+        dev, Tt = x32.device, len(tile_indices[0])
         if ref.shape[1] != 1:
             raise L.ScailHipError(f"temporal tiles take one reference frame (tiles and several characters are not combined), got {ref.shape[1]}")
-        if pose_tiles.dim() != 6 or pose_tiles.shape[1] != len(tile_indices) or pose_tiles.shape[2] != len(tile_indices[0]):
-            raise L.ScailHipError(f"smpl_tiled must be (1, n_tiles = {len(tile_indices)}, Tt = {len(tile_indices[0])}, 16, H/2, W/2), got "
+        if pose_tiles.dim() != 6 or pose_tiles.shape[1] != len(tile_indices) or pose_tiles.shape[2] != Tt:
+            raise L.ScailHipError(f"smpl_tiled must be (1, n_tiles = {len(tile_indices)}, Tt = {Tt}, 16, H/2, W/2), got "
                                   f"{tuple(pose_tiles.shape)}")
-        cond = self._conditioning(as_bf16(ctx), as_bf16(clip), cond_key)
-        cos, sin = self._rope(len(tile_indices[0]), H // 2, Wd // 2, 0, 0, dev, 1)
-        if self._cstep is None:
-            self._cstep = CStep(self, W)
-        x = x32.float().contiguous().clone()
-        return self._cstep.sample_tiled(x, sigmas, cfg_scale, cond, as_bf16(ref), as_bf16(pose_tiles), tile_indices, tile_w, inv_wsum, cos, sin)
+        ex, cond, cos, sin, x = self._sample_prelude(x32, ctx, clip, cond_key, Tt, 1)
+        return ex.sample_tiled(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose_tiles, dev), tile_indices, tile_w, inv_wsum, cos, sin)
 
     def _run(self, x32, t32, ctx, ref, pose, clip, H_shift=0, W_shift=0, cond_key=None, cfg_pair=False):
         W = self.prepare()
@@ -524,8 +520,7 @@ class DiffusionTransformer(nn.Module):
         # frame and one pose stream): ref (n, C, 16, H, W), pose (n, C*T, 16, H/2, W/2), tokens
         # [ref_0..ref_{C-1} | noise | pose_0..pose_{C-1}], RoPE windows of rope.build_tables(n_char=C)
         n_char = ref.shape[1]
-        if pose.shape[1] != n_char * T:
-            raise L.ScailHipError(f"concat_smpl_render needs {n_char} x {T} frames for {n_char} reference frame(s), got {pose.shape[1]}")
+        self._check_chars(n_char, T, pose.shape[1])
         Lref1, Lnoise, Lpose1 = hp * wp, T * hp * wp, T * (H // 4) * (Wd // 4)
         Lref, Lpose = n_char * Lref1, n_char * Lpose1
         Ltok = Lref + Lnoise + Lpose
@@ -534,21 +529,19 @@ class DiffusionTransformer(nn.Module):
         cond = self._conditioning(ctx, clip, cond_key)
         cos, sin = self._rope(T, hp, wp, H_shift, W_shift, dev, n_char)
         sp = self.sp if (self.sp is not None and self.sp.size > 1) else None
-        use_c = self.use_c_step and self._tap is None and self.kernel_timer is None
+        use_c = self.executor_ok()
         if self.fp8_mask and (sp is not None or not use_c):
             raise NotImplementedError("gemm_precision='fp8' runs in the C executor on a single rank only: not on sequence-parallel ranks, "
                                       "not on the per-op path (SCAIL_C_STEP=0, _tap, kernel_timer)")
-        if use_c and self._cstep is None:
-            from .cstep import CStep
-            self._cstep = CStep(self, W)
+        ex = self._executor() if use_c else None
         xch = sp.c_exchange(nh, D, B, Ltok, dev) if (use_c and sp is not None) else None
         if use_c and not self._c_blocks:
             # the whole evaluation as ONE call into the library (include/scail_dit.h), for any number of characters; same kernels, same
             # order.  A sequence-parallel rank runs the same executor: only the collectives of the per-layer exchange come back to the
             # host (xch)
             if sp is None:
-                return self._cstep.step(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, cfg_pair=cfg_pair, n_char=n_char)
-            return self._cstep.step_sp(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, xch, cfg_pair=cfg_pair, n_char=n_char)
+                return ex.step(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, cfg_pair=cfg_pair, n_char=n_char)
+            return ex.step_sp(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, xch, cfg_pair=cfg_pair, n_char=n_char)
         ws = self._workspace(B, Ltok, Lnoise, dev, blocks_in_c=use_c)
 
         # ---- time / AdaLN tables (reference :1521-1555, :1025-1028, :823) ----
@@ -576,9 +569,9 @@ class DiffusionTransformer(nn.Module):
             if use_c:
                 # (_c_blocks: token assembly above in the host, every block as one executor call)
                 if sp is None:
-                    self._cstep.block(i, h, m, cond, cos, sin)
+                    ex.block(i, h, m, cond, cos, sin)
                 else:
-                    self._cstep.block_sp(i, h, m, cond, cos, sin, xch)
+                    ex.block_sp(i, h, m, cond, cos, sin, xch)
                 continue
             sh_a, sc_a, g_a = m[:, 0:D], m[:, D:2 * D], m[:, 2 * D:3 * D]
             sh_m, sc_m, g_m = m[:, 3 * D:4 * D], m[:, 4 * D:5 * D], m[:, 5 * D:6 * D]

@@ -98,11 +98,8 @@ SIGNATURES = {
     "scail_vae_encode": [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p],
     "scail_vae_decode": [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p],
 }
-# return types other than the int status
-RESTYPES = {"scail_dit_destroy": None, "scail_vae_destroy": None, "scail_vae_workspace_bytes": _i64, "scail_dit_workspace_bytes": _i64, "scail_dit_sample_workspace_bytes": _i64,
-            "scail_dit_block_workspace_bytes": _i64, "scail_dit_sp_workspace_bytes": _i64, "scail_dit_block_sp_workspace_bytes": _i64,
-            "scail_dit_fp8_weight_bytes": _i64, "scail_dit_chars_workspace_bytes": _i64, "scail_dit_sp_chars_workspace_bytes": _i64,
-            "scail_dit_sample_chars_workspace_bytes": _i64, "scail_dit_sample_tiled_workspace_bytes": _i64}
+# return types other than the int status: every *_bytes query answers an int64_t, the destroy functions nothing
+RESTYPES = {"scail_dit_destroy": None, "scail_vae_destroy": None, **{n: _i64 for n in SIGNATURES if n.endswith("_bytes")}}
 
 # include/scail_hip_ablation.h: only libscail_hip_abl.so (SCAIL_ABLATIONS=1) exports these
 ABLATION_SIGNATURES = {

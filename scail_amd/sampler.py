@@ -135,6 +135,12 @@ class RFDiscretization:
         self.reverse = reverse
 
 
+def _executor_takes_loop(network) -> bool:
+    """Whether the network runs a whole sampler loop in one executor call (DiffusionTransformer.executor_ok); a network without that
+    method takes the generic loop"""
+    return getattr(network, "executor_ok", lambda **kw: False)(whole_loop=True)
+
+
 class RFSampler:
     """sampling.py:920-982.  Only the shipped branch (hunyuan_schedule) is implemented.
 
@@ -183,9 +189,7 @@ class RFSampler:
         cfg = float(self.guider.scale if scale is None else scale)
         ctx = torch.cat((uc["crossattn"], cond["crossattn"]), 0)
         shared = {k: v for k, v in cond.items() if k != "crossattn"}
-        if (getattr(network, "use_c_step", False) and step_callback is None and chunk_dim is None
-                and getattr(network, "kernel_timer", None) is None and getattr(network, "_tap", None) is None
-                and (network.sp is None or network.sp.size == 1)
+        if (_executor_takes_loop(network) and step_callback is None and chunk_dim is None
                 and shared["ref_concat"].shape[0] == 1 and shared["concat_smpl_render"].shape[0] == 1):
             # the whole loop enqueued by ONE call into the library (scail_dit_sample_chars; any number of reference frames / pose
             # streams); same kernels, same order
@@ -238,9 +242,7 @@ class RFSamplerLong(RFSampler):
         frames, one pose tile of Tt frames per tile.  Every other request keeps the Python loop below (several characters with
         tiles, longer tiles, sequence-parallel ranks, instrumented runs)."""
         Tt = len(tile_indices[0])
-        return bool(getattr(network, "use_c_step", False) and step_callback is None and chunk_dim is None
-                    and getattr(network, "kernel_timer", None) is None and getattr(network, "_tap", None) is None
-                    and (getattr(network, "sp", None) is None or network.sp.size == 1)
+        return bool(_executor_takes_loop(network) and step_callback is None and chunk_dim is None
                     and x.shape[0] == 1 and ref_concat.shape[0] == 1 and ref_concat.shape[1] == 1
                     and smpl_tiled.dim() == 6 and smpl_tiled.shape[0] == 1 and smpl_tiled.shape[1] == len(tile_indices)
                     and smpl_tiled.shape[2] == Tt and Tt <= cls.ONE_CALL_MAX_TILE and Tt <= x.shape[1] < (1 << 15))
@@ -275,6 +277,19 @@ class RFSamplerLong(RFSampler):
                                   tile_indices=tile_indices, smpl_tiled=smpl_tiled)
         return x
 
+    def _tile_table(self, tile_indices, T, dev):
+        """(frame index tensors, tile_w (n_tiles, Tt) = m_k * tile_weight, inv_wsum (T) = 1 / the per-frame sums of tile_w) for both
+        routes of sample_hip, formed on the latent's device: torch divides by a host scalar differently on the two devices, and the
+        one-call route has to hand the library the bits the loop below multiplies by."""
+        n = len(tile_indices)
+        weight = self.tile_weight(len(tile_indices[0]), dev)
+        idxs = [torch.as_tensor(list(t), device=dev, dtype=torch.long) for t in tile_indices]
+        tile_w = torch.stack([self._mult(k, n) * weight for k in range(n)])
+        wsum = torch.zeros(T, device=dev)
+        for k in range(n):
+            wsum[idxs[k]] += tile_w[k]
+        return idxs, tile_w, 1.0 / wsum
+
     def sample_hip(self, network, x, cond: Dict, uc: Dict, num_steps=None, scale=None, chunk_dim=None,
                    step_callback=None, tile_indices=None):
         """Fused path for the HIP network: per step and tile one batch-2 DiT forward (fp32 out); the text / CLIP
@@ -286,27 +301,17 @@ class RFSamplerLong(RFSampler):
         ctx = torch.cat((uc["crossattn"], cond["crossattn"]), 0)
         shared = {k: v for k, v in cond.items() if k not in ("crossattn", "smpl_tiled", "concat_smpl_render")}
         smpl_tiled = cond["smpl_tiled"]
+        idxs, tile_w, inv_wsum = self._tile_table(tile_indices, x.shape[1], x.device)
         if self._one_call_ok(network, x, shared["ref_concat"], smpl_tiled, tile_indices, step_callback, chunk_dim):
             # the whole loop enqueued by ONE call into the library (scail_dit_sample_tiled): same network kernels, the gather / blend /
-            # Euler arithmetic below as HIP row kernels that round every operation on its own -- the same bits.  The weights are formed
-            # as below, on the latent's device (torch divides by a host scalar differently on the two devices), and handed over as
-            # host values once per request.
-            weight = self.tile_weight(len(tile_indices[0]), x.device)
-            tile_w = torch.stack([self._mult(k, n) * weight for k in range(n)])
-            wsum = torch.zeros(x.shape[1], device=x.device)
-            for k in range(n):
-                wsum[torch.as_tensor(list(tile_indices[k]), device=x.device, dtype=torch.long)] += tile_w[k]
+            # Euler arithmetic below as HIP row kernels that round every operation on its own -- the same bits.  The weights are handed
+            # over as host values once per request.
             return network.sample_tiled_c(x, sig, cfg, ctx, shared["ref_concat"], smpl_tiled, shared["image_clip_features"],
-                                          [list(map(int, t)) for t in tile_indices], tile_w.cpu(), (1.0 / wsum).cpu(),
+                                          [list(map(int, t)) for t in tile_indices], tile_w.cpu(), inv_wsum.cpu(),
                                           cond_key=("sample_hip", id(cond)))
         x = x.float().contiguous().clone()
         dev = x.device
-        weight = self.tile_weight(len(tile_indices[0]), dev)[:, None, None, None]
-        idxs = [torch.as_tensor(list(t), device=dev, dtype=torch.long) for t in tile_indices]
-        wsum = torch.zeros(x.shape[1], device=dev)
-        for k in range(n):
-            wsum[idxs[k]] += self._mult(k, n) * weight[:, 0, 0, 0]
-        inv = (1.0 / wsum)[:, None, None, None]
+        tile_w, inv = tile_w[:, :, None, None, None], inv_wsum[:, None, None, None]
         for i in range(len(sig) - 1):
             t = (sig[i] * 1000.0).repeat(2).to(dev)
             den = torch.zeros_like(x)
@@ -315,7 +320,7 @@ class RFSamplerLong(RFSampler):
                 v = network.forward_f32(torch.cat([xt, xt], 0), t, ctx, None, cond_key=("sample_hip", id(cond)),
                                         chunk_dim=chunk_dim, concat_smpl_render=smpl_tiled[:, k], **shared)
                 d = v[0:1] + cfg * (v[1:2] - v[0:1])                     # VanillaCFG, guiders.py:41-45
-                den[:, idxs[k]] += (self._mult(k, n) * weight) * d
+                den[:, idxs[k]] += tile_w[k] * d
             x = x + float(sig[i + 1] - sig[i]) * (den * inv)
             if step_callback is not None:
                 step_callback(i, x)

@@ -169,8 +169,16 @@ def test_one_call_route_declines_what_the_entry_point_does_not_cover():
     """scail_dit_sample_tiled is one character, tiles of at most 64 latent frames, one rank: everything else the Python loop of
     RFSamplerLong.sample_hip ran before must keep running there"""
     from types import SimpleNamespace
+    from scail_amd.dit import DiffusionTransformer
     from scail_amd.sampler import RFSamplerLong as R
-    net = SimpleNamespace(use_c_step=True, kernel_timer=None, _tap=None, sp=None)
+
+    def mk(**kw):
+        """a stand-in network that answers with DiffusionTransformer's own rule from these attributes"""
+        fake = SimpleNamespace(**dict(dict(use_c_step=True, kernel_timer=None, _tap=None, sp=None), **kw))
+        fake.executor_ok = lambda **k: DiffusionTransformer.executor_ok(fake, **k)
+        return fake
+
+    net = mk()
     T, Tt, n = 9, 4, 3
     tiles = [[0, 1, 2, 3], [3, 4, 5, 6], [5, 6, 7, 8]]
     x = torch.zeros(1, T, 16, 8, 8)
@@ -193,8 +201,10 @@ def test_one_call_route_declines_what_the_entry_point_does_not_cover():
     assert ok(x=torch.zeros(2, T, 16, 8, 8)) is False and ok(ref_concat=torch.zeros(2, 1, 16, 8, 8)) is False
     assert ok(smpl_tiled=torch.zeros(2, n, Tt, 16, 4, 4)) is False and ok(smpl_tiled=torch.zeros(1, n + 1, Tt, 16, 4, 4)) is False
     for kw in (dict(use_c_step=False), dict(kernel_timer=object()), dict(_tap=object()), dict(sp=SimpleNamespace(size=2))):
-        assert ok(network=SimpleNamespace(**dict(vars(net), **kw))) is False
-    assert ok(network=SimpleNamespace(**dict(vars(net), sp=SimpleNamespace(size=1)))) is True
+        assert ok(network=mk(**kw)) is False
+    assert ok(network=mk(sp=SimpleNamespace(size=1))) is True
+    # a network that does not state the rule (any other nn.Module) keeps the generic loop
+    assert ok(network=SimpleNamespace(use_c_step=True, kernel_timer=None, _tap=None, sp=None)) is False
 
 
 def test_cli_run_refuses_a_long_clip_that_is_not_4n_plus_1_before_sampling():
