@@ -3,7 +3,9 @@
  * `WanVAE_.encode` :516-542 / `.decode` :544-568) as two calls into libscail_hip.so, composed in C++ from the
  * operator entry points of scail_hip.h (scail_conv3d_cl, scail_rms_silu, scail_gemm_bf16, scail_softmax_rows, ...).
  * Whole-sequence execution (no 1/4/4-frame chunking, no feature caches): see DESIGN.md section 4.4 for the temporal
- * rules that make it equal to the reference's streamed computation.
+ * rules that make it equal to the reference's streamed computation.  scail_vae_decode_stream is the opt-in second decode
+ * route for clips whose whole-sequence activations do not fit: the same chain, chunk by chunk, with the reference's
+ * feat_cache as a carry area in the workspace.
  *
  * Ownership: the caller owns weights, inputs, outputs and the workspace; the handle copies only the pointer tables.
  * Weights are in the kernel layout (`scail_amd.ops.prep_conv_weight`: [Cout_pad8][Kpad] bf16 with k = tap * Cin_pad + c,
@@ -78,7 +80,9 @@ void scail_vae_destroy(scail_vae* h);
  * point: the callback must order itself after the stream (enqueue its own work on the same stream, or synchronise) before reading, and
  * must not write.  The call sequence is the launch order of scail_amd/wan_vae.py's layer-by-layer path (tools/vae_exec_vs_layers.py
  * walks both); a launch with two outputs (scail_conv3d_cl_resid_norm: raw sum + the next consumer's normalised input) calls fn once per output
- * ("conv", then "conv_resid_norm").  fn == NULL switches it off (the default; nothing is called, nothing synchronises). */
+ * ("conv", then "conv_resid_norm").  fn == NULL switches it off (the default; nothing is called, nothing synchronises).
+ * scail_vae_decode_stream fires it the same way per launch, with the CHUNK's tensor (T = the chunk's frames at that stage); `index` runs on
+ * across the chunks of a call, so chunk k's launches follow chunk k - 1's. */
 typedef void (*scail_vae_trace_fn)(void* user, int index, const char* op, const void* data, int64_t T, int64_t H, int64_t W, int64_t C);
 int scail_vae_set_trace(scail_vae* h, scail_vae_trace_fn fn, void* user);
 
@@ -92,6 +96,20 @@ int scail_vae_encode(scail_vae* h, const float* video, float* latent, int64_t T,
 /* latent fp32 [z, Tl, hl, wl]  ->  video fp32 [3, 1 + 4 (Tl - 1), 8 hl, 8 wl], NOT clamped (WanVAE_.decode). */
 int scail_vae_decode(scail_vae* h, const float* latent, float* video, int64_t Tl, int64_t hl, int64_t wl,
                      void* workspace, int64_t workspace_bytes, void* stream);
+
+/* The streamed decode: scail_vae_decode's result from a workspace that depends on `chunk`, hl and wl and NOT on Tl.  The latent is walked in
+ * chunks of `chunk` >= 2 latent frames (a remainder of ONE frame joins the last chunk, so no stage sees fewer than two frames of a chunk; the
+ * workspace is sized for chunk + 1) through the same operator chain and the same kernels.  Every causal 3x3x3 convolution and the upsample3d
+ * time convolutions run the first chunk as the whole-sequence call does and every later chunk over [2 carried frames | chunk] without temporal
+ * padding; the carried frames -- the last two input frames of that convolution in the chunk before, wan_vae.py's feat_cache -- live in the
+ * workspace.  Every output voxel is computed from the same inputs as in scail_vae_decode; the two are bit-identical wherever every launch picks
+ * the same kernel for the chunk's geometry as for the clip's (every threshold of scail_conv3d_cl / scail_gemm_bf16 is passed either way at 512 x 896;
+ * DESIGN.md section 4.5 names the shapes that straddle one).  Tl <= chunk + 1 is ONE chunk: exactly the launches of scail_vae_decode.
+ * latent / video: the layouts of scail_vae_decode, on the device.  chunk < 2, a null pointer, a workspace smaller than the query's answer or not
+ * 256-byte aligned are refused before anything is enqueued. */
+int64_t scail_vae_decode_stream_workspace_bytes(const scail_vae* h, int64_t chunk, int64_t hl, int64_t wl);
+int scail_vae_decode_stream(scail_vae* h, const float* latent, float* video, int64_t Tl, int64_t hl, int64_t wl,
+                            int64_t chunk, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -213,7 +213,8 @@ def build_engine(cfg, load=None, device="cuda"):
     return engine
 
 
-def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frames=None, engine=None, tile_frames=None, tile_overlap=None):
+def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frames=None, engine=None, tile_frames=None, tile_overlap=None,
+        vae_chunk_frames=None):
     engine = engine or build_engine(cfg, load, device)
     H, W = cfg.get("args", {}).get("sampling_image_size", [512, 896])
     net = engine.network
@@ -230,7 +231,7 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
             raise ValueError(f"a pose clip longer than one window needs 4n + 1 frames (the causal VAE's frame groups), got {n_pix}")
         Tt, overlap = tile_args(tile_frames, tile_overlap, net.num_frames)
         tiles = plan_tiles((n_pix - 1) // 4 + 1, Tt, overlap)
-        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0)
+        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames)
     pose_lat = engine.encode_first_stage(req["pose"].unsqueeze(0), None, force_encode=True)   # already half resolution (:350-351)
     ref_concat = ref_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)      # B C T H W -> B T C H W
     pose_latent = pose_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)
@@ -241,22 +242,22 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     uc = dict(crossattn=req["uncond_context"], **shared)
     torch.manual_seed(seed)
     z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps)
-    return _finish(engine, z, t0)
+    return _finish(engine, z, t0, vae_chunk_frames)
 
 
-def _finish(engine, z, t0):
+def _finish(engine, z, t0, vae_chunk_frames=None):
     """sampled latent (B T C H W) -> (video in [0, 1], latent (B C T H W), seconds); (None, None, seconds) off sequence-parallel rank 0"""
     if engine.sp is not None and engine.sp.size > 1 and engine.sp.rank != 0:
         torch.cuda.synchronize()
         return None, None, time.perf_counter() - t0                         # only SP rank 0 holds the gathered latent (:484)
     z = z.permute(0, 2, 1, 3, 4).contiguous()                               # B T C H W -> B C T H W (:484-485)
-    x = engine.decode_first_stage(z.float())
+    x = engine.decode_first_stage(z.float(), chunk_frames=vae_chunk_frames)
     video = torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)                          # (:494)
     torch.cuda.synchronize()
     return video, z, time.perf_counter() - t0
 
 
-def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0):
+def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames=None):
     """A pose clip longer than one window (an extension, see the module docstring): RFSamplerLong with the configured sampler's
     parameters over ``tiles``; every window's pose frames [4 start, 4 (start + Tt - 1)] are VAE-encoded on their own (the causal VAE treats
     a window's first frame as a clip's first frame, which is how ``smpl_tiled[:, k]`` is used); noise and decode for the whole latent."""
@@ -281,7 +282,7 @@ def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0):
         z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, tile_indices=tiles)
     finally:
         engine.sampler = plain
-    return _finish(engine, z, t0)
+    return _finish(engine, z, t0, vae_chunk_frames)
 
 
 def main(argv=None):
@@ -315,14 +316,21 @@ def main(argv=None):
     ap.add_argument("--tile-overlap", type=int, default=None,
                     help="pixel frames shared by neighbouring windows, a multiple of 4 and smaller than the window (default: half of the "
                          "window's latent frames, e.g. 40 for an 81-frame window)")
+    ap.add_argument("--vae-chunk-frames", type=int, default=None,
+                    help="decode the sampled latent in chunks of this many latent frames (>= 2; one latent frame is four pixel frames): "
+                         "the VAE workspace then depends on this number and the frame size instead of the clip length (512x896: 10.9 GB with 4 instead of 85 GB "
+                         "for 161 frames), at the price of smaller launches and two frame copies per causal convolution and chunk; same video. "
+                         "Unset: one pass over the whole clip")
     a = ap.parse_args(argv)
+    if a.vae_chunk_frames is not None and a.vae_chunk_frames < 2:
+        ap.error(f"--vae-chunk-frames must be at least 2 latent frames, got {a.vae_chunk_frames}")
     cfg = TINY if a.tiny or not a.base else load_yaml_configs(*a.base)
     if a.tile_frames is not None or a.tile_overlap is not None:         # argument errors before any model is built
         try:
             tile_args(a.tile_frames, a.tile_overlap, cfg["model"]["network_config"].get("params", {}).get("num_frames", 81))
         except ValueError as e:
             ap.error(str(e))
-    tk = dict(tile_frames=a.tile_frames, tile_overlap=a.tile_overlap)
+    tk = dict(tile_frames=a.tile_frames, tile_overlap=a.tile_overlap, vae_chunk_frames=a.vae_chunk_frames)
     if a.gemm_precision is not None:
         cfg = copy.deepcopy(cfg)
         cfg["model"]["network_config"].setdefault("params", {})["gemm_precision"] = a.gemm_precision

@@ -990,6 +990,75 @@ __global__ void from_channels_last_kernel(const u16* __restrict__ x, int64_t ldx
     y[i] = fminf(fmaxf(v, lo), hi);
 }
 
+// The same two layout passes over a WINDOW of frames of a longer planar tensor (scail_vae_decode_stream walks a clip chunk by chunk): the channel
+// planes lie `plane` elements apart and the window starts `off` elements into each of them.  One thread moves V voxels x 8 channels: 16-byte rows on
+// the channels-last side; on the planar side float4 for V = 4 (plane, off and N multiples of 4, 16-byte aligned base -- every real latent / video
+// size) and dwords, coalesced over the voxels, for V = 1.  Same arithmetic as the whole-tensor kernels above.
+template <int V>
+__global__ void to_channels_last_frames_kernel(const float* __restrict__ x, u16* __restrict__ y, const float* __restrict__ a,
+                                               const float* __restrict__ b, int C, int Cpad, int64_t plane, int64_t off, int64_t N) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nv = N / V;
+    if (i >= nv * (Cpad / 8)) return;
+    const int g = (int)(i / nv);
+    const int64_t n0 = (i % nv) * V;
+    float v[V][8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int c = g * 8 + j;
+        if (c < C) {
+            const float* src = x + (int64_t)c * plane + off + n0;
+            float s[V];
+            if constexpr (V == 4) {
+                const float4 f = *reinterpret_cast<const float4*>(src);
+                s[0] = f.x; s[1] = f.y; s[2] = f.z; s[3] = f.w;
+            } else {
+                s[0] = src[0];
+            }
+#pragma unroll
+            for (int k = 0; k < V; ++k) v[k][j] = s[k] * (a ? a[c] : 1.f) + (b ? b[c] : 0.f);
+        } else {
+#pragma unroll
+            for (int k = 0; k < V; ++k) v[k][j] = 0.f;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        uint4 r;
+        r.x = (uint32_t)f2bf(v[k][0]) | ((uint32_t)f2bf(v[k][1]) << 16);
+        r.y = (uint32_t)f2bf(v[k][2]) | ((uint32_t)f2bf(v[k][3]) << 16);
+        r.z = (uint32_t)f2bf(v[k][4]) | ((uint32_t)f2bf(v[k][5]) << 16);
+        r.w = (uint32_t)f2bf(v[k][6]) | ((uint32_t)f2bf(v[k][7]) << 16);
+        *reinterpret_cast<uint4*>(y + (n0 + k) * Cpad + g * 8) = r;
+    }
+}
+
+template <int V>
+__global__ void from_channels_last_frames_kernel(const u16* __restrict__ x, int64_t ldx, float* __restrict__ y, const float* __restrict__ a,
+                                                 const float* __restrict__ b, int C, int64_t plane, int64_t off, int64_t N, float lo, float hi) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nv = N / V;
+    if (i >= nv * ((C + 7) / 8)) return;
+    const int g = (int)(i / nv);
+    const int64_t n0 = (i % nv) * V;
+    uint4 r[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) r[k] = *reinterpret_cast<const uint4*>(x + (n0 + k) * ldx + g * 8);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int c = g * 8 + j;
+        if (c >= C) break;
+        float o[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const uint32_t w = (j >> 1) == 0 ? r[k].x : (j >> 1) == 1 ? r[k].y : (j >> 1) == 2 ? r[k].z : r[k].w;
+            const float f = (bf2f((u16)((j & 1) ? (w >> 16) : (w & 0xffffu))) + (b ? b[c] : 0.f)) * (a ? a[c] : 1.f);
+            o[k] = fminf(fmaxf(f, lo), hi);
+        }
+        float* dst = y + (int64_t)c * plane + off + n0;
+        if constexpr (V == 4) *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+        else dst[0] = o[0];
+    }
+}
+
 // ================================================================================================
 // C ABI
 // ================================================================================================
@@ -1448,4 +1517,42 @@ extern "C" int scail_from_channels_last(const scail_bf16* x, int64_t ldx, float*
     hipLaunchKernelGGL(from_channels_last_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, x, ldx, y, a, b, (int)C, N, lo, hi);
     return scail_check_launch("from_channels_last");
+}
+
+// a window of frames of a longer planar tensor (kernels above): float4 on the planar side where the window allows it, else dwords
+static bool frames_vec4(const void* planar, int64_t plane, int64_t off, int64_t N) {
+    return plane % 4 == 0 && off % 4 == 0 && N % 4 == 0 && (reinterpret_cast<uintptr_t>(planar) & 15) == 0;
+}
+
+extern "C" int scail_to_channels_last_frames(const float* x, scail_bf16* y, const float* a, const float* b, int64_t C, int64_t Cpad,
+                                             int64_t plane, int64_t off, int64_t N, void* stream) {
+    SCAIL_REQUIRE(C > 0 && Cpad % 8 == 0 && C <= Cpad && Cpad < (1 << 20), "to_channels_last_frames: need 0 < C <= Cpad, Cpad a multiple of 8");
+    SCAIL_REQUIRE(off >= 0 && N >= 0 && off + N <= plane, "to_channels_last_frames: the window [off, off + N) must lie inside a plane");
+    if (N == 0) return 0;
+    SCAIL_REQUIRE(x != nullptr && y != nullptr && (reinterpret_cast<uintptr_t>(y) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 3) == 0,
+                  "to_channels_last_frames: null or misaligned pointer (y needs 16-byte rows)");
+    const bool v4 = frames_vec4(x, plane, off, N);
+    const int64_t threads = N / (v4 ? 4 : 1) * (Cpad / 8);
+    SCAIL_REQUIRE((threads + 255) / 256 < (1ll << 31), "to_channels_last_frames: too many voxels for one launch");
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (v4) hipLaunchKernelGGL(to_channels_last_frames_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, y, a, b, (int)C, (int)Cpad, plane, off, N);
+    else hipLaunchKernelGGL(to_channels_last_frames_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, y, a, b, (int)C, (int)Cpad, plane, off, N);
+    return scail_check_launch("to_channels_last_frames");
+}
+
+extern "C" int scail_from_channels_last_frames(const scail_bf16* x, int64_t ldx, float* y, const float* a, const float* b, int64_t C,
+                                               int64_t plane, int64_t off, int64_t N, float lo, float hi, void* stream) {
+    SCAIL_REQUIRE(C > 0 && ldx % 8 == 0 && ldx >= (C + 7) / 8 * 8 && ldx < (1 << 20),
+                  "from_channels_last_frames: need C > 0 and a row stride that is a multiple of 8 covering ceil8(C)");
+    SCAIL_REQUIRE(off >= 0 && N >= 0 && off + N <= plane, "from_channels_last_frames: the window [off, off + N) must lie inside a plane");
+    if (N == 0) return 0;
+    SCAIL_REQUIRE(x != nullptr && y != nullptr && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
+                  "from_channels_last_frames: null or misaligned pointer (x needs 16-byte rows)");
+    const bool v4 = frames_vec4(y, plane, off, N);
+    const int64_t threads = N / (v4 ? 4 : 1) * ((C + 7) / 8);
+    SCAIL_REQUIRE((threads + 255) / 256 < (1ll << 31), "from_channels_last_frames: too many voxels for one launch");
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    if (v4) hipLaunchKernelGGL(from_channels_last_frames_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, y, a, b, (int)C, plane, off, N, lo, hi);
+    else hipLaunchKernelGGL(from_channels_last_frames_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, y, a, b, (int)C, plane, off, N, lo, hi);
+    return scail_check_launch("from_channels_last_frames");
 }

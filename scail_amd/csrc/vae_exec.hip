@@ -1,7 +1,11 @@
 // Seam B4 in C (include/scail_vae.h): WanVAE_.encode / .decode (sgm/models/wan_vae.py:516-568) as a fixed sequence of
 // operator launches -- the C++ statement of scail_amd/wan_vae.py.  Host code only; activations are channels-last
 // (T, H, W, C) bf16 tensors living in NSLOT equally sized slots of the caller's workspace.
+// scail_vae_decode_stream walks the same chain chunk by chunk (the reference's feat_cache, stated once in causal_begin / causal_end):
+// its slots are sized for a chunk, two of them for the quarter-size activations only, and a carry area behind them keeps two frames
+// of every causal convolution's input from one chunk to the next.
 #include <cmath>
+#include <string>
 #include <vector>
 
 #include "common.h"
@@ -24,6 +28,7 @@ struct Tens {            // channels-last activation
     scail_bf16* p = nullptr;
     int64_t T = 0, H = 0, W = 0, C = 0;
     int slot = -1;
+    int64_t cap = 0;     // bytes of the slot from p on
     int64_t vox() const { return T * H * W; }
 };
 
@@ -36,6 +41,15 @@ struct Arena {
     scail_vae_trace_fn trace = nullptr;     // scail_vae_set_trace: called after every operator launch whose output is a whole activation
     void* trace_user = nullptr;
     int trace_n = 0;
+    // streamed decode only (all zero otherwise): the LAST n_small slots are small_bytes long and serve the activations that fit them; every
+    // activation starts `head` frames into its slot (room for a causal convolution's carried frames in front of it); `later`: not the clip's
+    // first chunk; the carry areas are handed out in launch order, the same in every chunk
+    int n_small = 0;
+    int64_t small_bytes = 0;
+    int head = 0;
+    bool later = false;
+    char* carry = nullptr;
+    int64_t carry_bytes = 0, carry_off = 0;
     void emit(const char* op, const Tens& t) {
         if (trace) trace(trace_user, trace_n, op, t.p, t.T, t.H, t.W, t.C);
         ++trace_n;
@@ -43,12 +57,26 @@ struct Arena {
     Tens get(int64_t T, int64_t H, int64_t W, int64_t C) {
         Tens t;
         t.T = T; t.H = H; t.W = W; t.C = C;
-        if (T * H * W * C * 2 > slot_bytes) { err = 1; scail_set_error("scail_vae: activation larger than a workspace slot"); return t; }
-        for (int i = 0; i < NSLOT; ++i)
-            if (!used[i]) { used[i] = true; t.slot = i; t.p = reinterpret_cast<scail_bf16*>(base + i * slot_bytes); return t; }
+        const int64_t front = head * H * W * C * 2, need = front + T * H * W * C * 2;
+        if (need > slot_bytes) { err = 1; scail_set_error("scail_vae: activation larger than a workspace slot"); return t; }
+        const int nbig = NSLOT - n_small;
+        for (int k = 0; k < NSLOT; ++k) {
+            const int i = need <= small_bytes ? (k + nbig) % NSLOT : k;       // what fits a small slot takes one while one is free
+            if (used[i] || (i >= nbig && need > small_bytes)) continue;
+            char* s = i < nbig ? base + i * slot_bytes : base + nbig * slot_bytes + (i - nbig) * small_bytes;
+            used[i] = true; t.slot = i; t.p = reinterpret_cast<scail_bf16*>(s + front); t.cap = (i < nbig ? slot_bytes : small_bytes) - front;
+            return t;
+        }
         err = 1;
         scail_set_error("scail_vae: out of workspace slots");
         return t;
+    }
+    scail_bf16* claim(int64_t bytes) {      // the next carry area
+        bytes = align256(bytes);
+        if (carry_off + bytes > carry_bytes) { err = 1; scail_set_error("scail_vae: carry areas exceed the workspace (scail_vae_decode_stream_workspace_bytes)"); return nullptr; }
+        scail_bf16* p = reinterpret_cast<scail_bf16*>(carry + carry_off);
+        carry_off += bytes;
+        return p;
     }
     void put(Tens& t) { if (t.slot >= 0) used[t.slot] = false; t.slot = -1; }
 };
@@ -60,16 +88,57 @@ struct Arena {
     }
 #define VAE_CHK(a_) if ((a_).err) return 1;
 
-// conv3d_cl with the defaults of scail_amd.ops.conv3d_cl: causal "same" padding (kt-1, kh/2, kw/2), stride 1
+int copy_frame(Arena& a, scail_bf16* dst, const scail_bf16* src, int64_t elems) {
+    if (hipMemcpyAsync(dst, src, elems * 2, hipMemcpyDeviceToDevice, (hipStream_t)a.stream) != hipSuccess) {
+        scail_set_error("scail_vae: hipMemcpyAsync failed");
+        return 2;
+    }
+    return 0;
+}
+
+// The temporal context of a causal convolution with kt = 3 taps in time (wan_vae.py CausalConv3d :17-36 and its feat_cache).  Whole sequence, and
+// the first chunk of a streamed decode: the input as it is, two zero frames in front (pt = 2).  Every later chunk: [2 carried frames | chunk],
+// contiguous in time, with pt = 0 -- the carried frames are the last two frames this convolution read in the chunk before; they are copied in
+// front of x, where Arena::get left `head` = 2 frames free.  causal_end, after the launch(es) that read `in`, keeps the last two frames for the
+// next chunk (one frame only, the first chunk's one-frame time_conv tail: [zeros, that frame], which is what pt = 2 showed the convolution).
+struct Causal {
+    Tens in;
+    int pt = 0;
+    scail_bf16* keep = nullptr;
+};
+int causal_begin(Arena& a, const Tens& x, int kt, Causal& c) {
+    c.in = x; c.pt = kt - 1; c.keep = nullptr;
+    if (a.head == 0 || kt != 3) return 0;
+    const int64_t fr = x.H * x.W * x.C;
+    c.keep = a.claim(2 * fr * 2); VAE_CHK(a)
+    if (a.later) {
+        VAE_TRY(copy_frame(a, x.p - 2 * fr, c.keep, 2 * fr));
+        c.in.p = x.p - 2 * fr; c.in.T = x.T + 2; c.pt = 0;
+    }
+    return 0;
+}
+int causal_end(Arena& a, const Causal& c) {
+    if (c.keep == nullptr) return 0;
+    const int64_t fr = c.in.H * c.in.W * c.in.C;
+    if (c.in.T >= 2) return copy_frame(a, c.keep, c.in.p + (c.in.T - 2) * fr, 2 * fr);
+    if (hipMemsetAsync(c.keep, 0, fr * 2, (hipStream_t)a.stream) != hipSuccess) { scail_set_error("scail_vae: hipMemsetAsync failed"); return 2; }
+    return copy_frame(a, c.keep + fr, c.in.p, fr);
+}
+
+// conv3d_cl with the defaults of scail_amd.ops.conv3d_cl: causal "same" padding (kt-1, kh/2, kw/2), stride 1 (pt < 0: the temporal context is
+// causal_begin's; a caller that passes pt has dealt with it)
 int conv(Arena& a, const Tens& x, const scail_conv_w& cw, Tens& out, int64_t To, int64_t Ho, int64_t Wo,
          int st = 1, int sh = 1, int sw = 1, int pt = -1, int ph = -1, int pw = -1, int ups = 0, int ot_mul = 1, int ot_off = 0,
          const Tens* resid = nullptr, bool alloc = true) {
-    if (pt < 0) { pt = cw.kt - 1; ph = cw.kh / 2; pw = cw.kw / 2; }
+    Causal c;
+    c.in = x;
+    if (pt < 0) { VAE_TRY(causal_begin(a, x, cw.kt, c)); pt = c.pt; ph = cw.kh / 2; pw = cw.kw / 2; }
     if (alloc) { out = a.get(To, Ho, Wo, cw.N); VAE_CHK(a) }
     SCAIL_REQUIRE(x.C == cw.Cin, "scail_vae: channel mismatch between an activation and its convolution");
-    int32_t geom[21] = {(int32_t)x.T, (int32_t)x.H, (int32_t)x.W, (int32_t)x.C, (int32_t)To, (int32_t)Ho, (int32_t)Wo,
+    int32_t geom[21] = {(int32_t)c.in.T, (int32_t)x.H, (int32_t)x.W, (int32_t)x.C, (int32_t)To, (int32_t)Ho, (int32_t)Wo,
                         cw.kt, cw.kh, cw.kw, st, sh, sw, pt, ph, pw, ups, ot_mul, ot_off, cw.N, cw.Kpad};
-    VAE_TRY(scail_conv3d_cl(x.p, cw.w, cw.b, out.p, out.C, resid ? resid->p : nullptr, resid ? resid->C : 0, geom, a.stream));
+    VAE_TRY(scail_conv3d_cl(c.in.p, cw.w, cw.b, out.p, out.C, resid ? resid->p : nullptr, resid ? resid->C : 0, geom, a.stream));
+    VAE_TRY(causal_end(a, c));
     if (ot_mul == 1) a.emit("conv", out);         // (the two interleaved halves of an upsample3d time_conv are seen through the resample conv)
     return 0;
 }
@@ -92,8 +161,10 @@ int res_block(Arena& a, const scail_vae_res& r, Tens& x, Tens* xn = nullptr, con
         VAE_TRY(scail_rms_silu(x.p, y.p, r.gamma0, x.vox(), x.C, 1, a.stream));
         a.emit("rms_silu", y);
     }
-    int32_t geom[21] = {(int32_t)y.T, (int32_t)y.H, (int32_t)y.W, (int32_t)y.C, (int32_t)x.T, (int32_t)x.H, (int32_t)x.W,
-                        3, 3, 3, 1, 1, 1, 2, 1, 1, 0, 1, 0, r.conv2.N, r.conv2.Kpad};
+    Causal c2;
+    VAE_TRY(causal_begin(a, y, r.conv2.kt, c2));
+    int32_t geom[21] = {(int32_t)c2.in.T, (int32_t)y.H, (int32_t)y.W, (int32_t)y.C, (int32_t)x.T, (int32_t)x.H, (int32_t)x.W,
+                        3, 3, 3, 1, 1, 1, r.conv2.kt == 3 ? c2.pt : 2, 1, 1, 0, 1, 0, r.conv2.N, r.conv2.Kpad};
     if (r.conv2.kt == 3 && r.conv2.kh == 3 && r.conv2.kw == 3 && y.C % 32 == 0 && r.conv2.N <= 96 &&
         (scail_conv3d_kernel_for(geom, r.conv2.N, 0, 1) == 4 || scail_conv3d_kernel_for(geom, r.conv2.N, 0, 0) != 4)) {
         // conv -> RMS_norm -> SiLU in one kernel: the raw conv output never goes to HBM (same rule as ops.conv_norm_fusable): the generated
@@ -101,26 +172,32 @@ int res_block(Arena& a, const scail_vae_res& r, Tens& x, Tens* xn = nullptr, con
         // kernel runs but its norm epilogue does not: there conv + a separate rms_silu pass beats the fused hipcc kernel (13.9 + 2.8 vs 21.0 ms
         // on the 96-channel full-resolution shape, round 3).
         y2 = a.get(x.T, x.H, x.W, r.conv2.N); VAE_CHK(a)
-        VAE_TRY(scail_conv3d_cl_norm(y.p, r.conv2.w, r.conv2.b, y2.p, y2.C, r.gamma3, geom, a.stream));
+        VAE_TRY(scail_conv3d_cl_norm(c2.in.p, r.conv2.w, r.conv2.b, y2.p, y2.C, r.gamma3, geom, a.stream));
+        VAE_TRY(causal_end(a, c2));
         a.emit("conv_norm", y2);
         a.put(y);
     } else {
-        VAE_TRY(conv(a, y, r.conv2, y2, x.T, x.H, x.W));
+        VAE_TRY(conv(a, c2.in, r.conv2, y2, x.T, x.H, x.W, 1, 1, 1, c2.pt, r.conv2.kh / 2, r.conv2.kw / 2));
+        VAE_TRY(causal_end(a, c2));
         a.put(y);
         VAE_TRY(scail_rms_silu(y2.p, y2.p, r.gamma3, y2.vox(), y2.C, 1, a.stream));
         a.emit("rms_silu", y2);
     }
-    int32_t geom6[21] = {(int32_t)y2.T, (int32_t)y2.H, (int32_t)y2.W, (int32_t)y2.C, (int32_t)x.T, (int32_t)x.H, (int32_t)x.W,
-                         r.conv6.kt, r.conv6.kh, r.conv6.kw, 1, 1, 1, r.conv6.kt - 1, r.conv6.kh / 2, r.conv6.kw / 2, 0, 1, 0, r.conv6.N, r.conv6.Kpad};
+    Causal c6;
+    VAE_TRY(causal_begin(a, y2, r.conv6.kt, c6));
+    int32_t geom6[21] = {(int32_t)c6.in.T, (int32_t)y2.H, (int32_t)y2.W, (int32_t)y2.C, (int32_t)x.T, (int32_t)x.H, (int32_t)x.W,
+                         r.conv6.kt, r.conv6.kh, r.conv6.kw, 1, 1, 1, c6.pt, r.conv6.kh / 2, r.conv6.kw / 2, 0, 1, 0, r.conv6.N, r.conv6.Kpad};
     if (xn != nullptr && next_gamma != nullptr && y2.C == r.conv6.Cin && scail_conv3d_kernel_for(geom6, r.conv6.N, h.C, 2) != 0) {
         Tens nrm = a.get(x.T, x.H, x.W, r.conv6.N); VAE_CHK(a)
         if (need_raw) { out = a.get(x.T, x.H, x.W, r.conv6.N); VAE_CHK(a) }
-        VAE_TRY(scail_conv3d_cl_resid_norm(y2.p, r.conv6.w, r.conv6.b, need_raw ? out.p : nullptr, nrm.p, r.conv6.N, h.p, h.C, next_gamma, geom6, a.stream));
+        VAE_TRY(scail_conv3d_cl_resid_norm(c6.in.p, r.conv6.w, r.conv6.b, need_raw ? out.p : nullptr, nrm.p, r.conv6.N, h.p, h.C, next_gamma, geom6, a.stream));
+        VAE_TRY(causal_end(a, c6));
         if (need_raw) a.emit("conv", out);
         a.emit("conv_resid_norm", nrm);
         *xn = nrm;
     } else {
-        VAE_TRY(conv(a, y2, r.conv6, out, x.T, x.H, x.W, 1, 1, 1, -1, -1, -1, 0, 1, 0, &h));
+        VAE_TRY(conv(a, c6.in, r.conv6, out, x.T, x.H, x.W, 1, 1, 1, c6.pt, r.conv6.kh / 2, r.conv6.kw / 2, 0, 1, 0, &h));
+        VAE_TRY(causal_end(a, c6));
     }
     a.put(y2);
     if (sc) a.put(h);
@@ -143,7 +220,7 @@ int attn_block(Arena& a, const scail_vae_attn& at, Tens& x) {
     a.emit("rms_silu", y);
     Tens tmp = a.get(1, 1, 1, 0); VAE_CHK(a)          // one slot, carved up below
     const int64_t act = align256((T * nt + 8) * C * 2);       // + 8 rows: the score GEMM reads k rows up to ceil8(nt) of the last frame
-    SCAIL_REQUIRE(4 * act + align256(nt * npad * 2) + align256(C * npad * 2) <= a.slot_bytes, "scail_vae: attention temporaries exceed a slot");
+    SCAIL_REQUIRE(4 * act + align256(nt * npad * 2) + align256(C * npad * 2) <= tmp.cap, "scail_vae: attention temporaries exceed a slot");
     char* tb = reinterpret_cast<char*>(tmp.p);
     scail_bf16 *q = reinterpret_cast<scail_bf16*>(tb), *k = reinterpret_cast<scail_bf16*>(tb + act),
                *v = reinterpret_cast<scail_bf16*>(tb + 2 * act), *o = reinterpret_cast<scail_bf16*>(tb + 3 * act),
@@ -176,14 +253,6 @@ int attn_block(Arena& a, const scail_vae_attn& at, Tens& x) {
     return 0;
 }
 
-int copy_frame(Arena& a, scail_bf16* dst, const scail_bf16* src, int64_t elems) {
-    if (hipMemcpyAsync(dst, src, elems * 2, hipMemcpyDeviceToDevice, (hipStream_t)a.stream) != hipSuccess) {
-        scail_set_error("scail_vae: hipMemcpyAsync failed");
-        return 2;
-    }
-    return 0;
-}
-
 // Resample downsample2d / downsample3d (wan_vae.py:87-96, :133-150); consumes x
 int down_stage(Arena& a, const scail_vae_stage& s, Tens& x) {
     Tens y;
@@ -204,14 +273,19 @@ int down_stage(Arena& a, const scail_vae_stage& s, Tens& x) {
 // Resample upsample2d / upsample3d (wan_vae.py:76-85, :100-131); consumes x.  next_gamma / xn as in res_block: where ONE generated kernel covers the
 // resample convolution + the next ResidualBlock's RMS_norm + SiLU, *xn returns that block's normalised input beside the raw output
 int up_stage(Arena& a, const scail_vae_stage& s, Tens& x, Tens* xn = nullptr, const float* next_gamma = nullptr) {
-    if (s.temporal && x.T > 1) {
-        Tens t2 = a.get(1 + 2 * (x.T - 1), x.H, x.W, x.C); VAE_CHK(a)
+    if (s.temporal && (x.T > 1 || a.later)) {
+        const int first = a.later ? 0 : 1;                                 // a later chunk of a streamed decode is all tail
+        Tens t2 = a.get(first + 2 * (x.T - first), x.H, x.W, x.C); VAE_CHK(a)
         const int64_t fr = x.H * x.W * x.C;
-        VAE_TRY(copy_frame(a, t2.p, x.p, fr));                             // 'Rep': the first latent frame is not doubled (:106-108)
+        if (first) VAE_TRY(copy_frame(a, t2.p, x.p, fr));                  // 'Rep': the first latent frame is not doubled (:106-108)
         Tens tail = x;                                                     // frames >= 1 never see frame 0 (:120-130)
-        tail.p = x.p + fr; tail.T = x.T - 1;
-        VAE_TRY(conv(a, tail, s.time_conv0, t2, x.T - 1, x.H, x.W, 1, 1, 1, -1, -1, -1, 0, 2, 1, nullptr, false));
-        VAE_TRY(conv(a, tail, s.time_conv1, t2, x.T - 1, x.H, x.W, 1, 1, 1, -1, -1, -1, 0, 2, 2, nullptr, false));
+        tail.p = x.p + first * fr; tail.T = x.T - first;
+        const scail_conv_w &t0 = s.time_conv0, &t1 = s.time_conv1;
+        Causal c;                                                          // one context for both output halves
+        VAE_TRY(causal_begin(a, tail, t0.kt, c));
+        VAE_TRY(conv(a, c.in, t0, t2, tail.T, x.H, x.W, 1, 1, 1, c.pt, t0.kh / 2, t0.kw / 2, 0, 2, first, nullptr, false));
+        VAE_TRY(conv(a, c.in, t1, t2, tail.T, x.H, x.W, 1, 1, 1, c.pt, t1.kh / 2, t1.kw / 2, 0, 2, first + 1, nullptr, false));
+        VAE_TRY(causal_end(a, c));
         a.put(x);
         x = t2;
     }
@@ -242,6 +316,82 @@ int64_t slot_bytes_for(const scail_vae_weights& w, int64_t T, int64_t H, int64_t
     const int64_t attn = 4 * align256((Tl * nt + 8) * C * 2) + align256(nt * npad * 2) + align256(C * npad * 2);
     const int64_t act = align256(T * H * W * dim * 2);
     return act > attn ? act : attn;
+}
+
+// The streamed decode's workspace: NSLOT - 2 slots for a chunk's largest activation -- chunk + 1 latent frames (a remainder of one frame joins
+// the last chunk) = 4 (chunk + 1) full-resolution frames behind the 2 frames of Arena::head --, 2 slots of a quarter of that for the stages up to
+// the first spatial doubling (the only place where more than NSLOT - 2 activations are alive, ResidualBlock with a shortcut; a quarter also
+// holds the interleaved time_conv output of the second upsample3d) and the attention temporaries, then one carry area of two input frames per
+// causal convolution, in launch order (causal_begin claims them in the same order).  Nothing here depends on the clip length.
+struct StreamPlan {
+    int64_t big = 0, small = 0, carry = 0;
+    int64_t total() const { return (NSLOT - 2) * big + 2 * small + carry; }
+};
+StreamPlan stream_plan(const scail_vae& h, int64_t chunk, int64_t hl, int64_t wl) {
+    const scail_vae_weights& w = h.w;
+    StreamPlan p;
+    const int64_t nt = hl * wl, npad = (nt + 63) / 64 * 64, C = w.dec_attn.C;
+    const int64_t attn = 4 * align256(((chunk + 1) * nt + 8) * C * 2) + align256(nt * npad * 2) + align256(C * npad * 2);
+    const int64_t act = align256((4 * (chunk + 1) + 2) * (8 * hl) * (8 * wl) * (int64_t)w.dec_head.Cin * 2);
+    p.big = act > attn ? act : attn;
+    const int64_t quarter = align256((p.big + 3) / 4);
+    p.small = quarter > attn ? quarter : attn;
+    int64_t H = hl, W = wl;
+    auto site = [&](const scail_conv_w& cw) { if (cw.kt == 3) p.carry += align256(2 * H * W * (int64_t)cw.Cin * 2); };
+    auto res = [&](const scail_vae_res& r) { site(r.conv2); site(r.conv6); };
+    site(w.conv2); site(w.dec_conv1);
+    res(w.dec_mid0); res(w.dec_mid2);
+    for (const scail_vae_stage& s : h.dec) {
+        if (s.kind == 0) res(s.res);
+        else if (s.kind == 2) { if (s.temporal) site(s.time_conv0); H *= 2; W *= 2; }
+    }
+    site(w.dec_head);
+    return p;
+}
+
+// The decoder chain over the latent frames [t0, t0 + n) of a clip of Tl: the whole clip (t0 = 0, n = Tl: scail_vae_decode) or one chunk of a
+// streamed decode, whose causal convolutions take their temporal context from the carry areas (a.head, a.later; causal_begin).
+int decode_frames(scail_vae* h, Arena& a, const float* latent, float* video, int64_t Tl, int64_t t0, int64_t n, int64_t hl, int64_t wl) {
+    const scail_vae_weights& w = h->w;
+    void* stream = a.stream;
+    const int64_t T = 1 + 4 * (Tl - 1), H = 8 * hl, W = 8 * wl;
+    const bool whole = t0 == 0 && n == Tl;
+    Tens x = a.get(n, hl, wl, w.z_dim); VAE_CHK(a)
+    if (whole) { VAE_TRY(scail_to_channels_last(latent, x.p, w.dec_scale, w.dec_shift, w.z_dim, w.z_dim, Tl * hl * wl, stream)); }
+    else { VAE_TRY(scail_to_channels_last_frames(latent, x.p, w.dec_scale, w.dec_shift, w.z_dim, w.z_dim, Tl * hl * wl, t0 * hl * wl, n * hl * wl, stream)); }
+    Tens y;
+    VAE_TRY(conv(a, x, w.conv2, y, x.T, x.H, x.W));
+    a.put(x);
+    x = y;
+    VAE_TRY(conv(a, x, w.dec_conv1, y, x.T, x.H, x.W));
+    a.put(x);
+    x = y;
+    VAE_TRY(res_block(a, w.dec_mid0, x));
+    VAE_TRY(attn_block(a, w.dec_attn, x));
+    VAE_TRY(res_block(a, w.dec_mid2, x));
+    Tens xn;       // the next consumer's normalised input, when its producer wrote it (res_block)
+    for (size_t i = 0; i < h->dec.size(); ++i) {
+        const scail_vae_stage& s = h->dec[i];
+        const bool last = i + 1 == h->dec.size();      // the last block feeds the head's norm and nothing else
+        if (s.kind == 0) { VAE_TRY(res_block(a, s.res, x, &xn, last ? w.dec_head_gamma : next_res_gamma(h->dec, i), !last)); }
+        else if (s.kind == 2) { VAE_TRY(up_stage(a, s, x, &xn, next_res_gamma(h->dec, i))); }
+        else { scail_set_error("scail_vae_decode: downsampling stage in the decoder table"); return 1; }
+    }
+    if (xn.p != nullptr) {             // the head's RMS_norm + SiLU came out of the last block's epilogue
+        if (x.p != nullptr) a.put(x);
+        x = xn;
+    } else {
+        VAE_TRY(scail_rms_silu(x.p, x.p, w.dec_head_gamma, x.vox(), x.C, 1, stream));
+        a.emit("rms_silu", x);
+    }
+    VAE_TRY(conv(a, x, w.dec_head, y, x.T, x.H, x.W));
+    a.put(x);
+    x = y;
+    const int64_t f0 = t0 == 0 ? 0 : 4 * t0 - 3;       // the clip's first latent frame stands for one video frame, every other one for four
+    SCAIL_REQUIRE(x.T == (t0 == 0 ? 1 + 4 * (n - 1) : 4 * n) && x.H == H && x.W == W, "scail_vae_decode: stage table does not expand (4, 8, 8)");
+    a.put(x);
+    if (whole) return scail_from_channels_last(x.p, x.C, video, nullptr, nullptr, 3, x.vox(), -3.0e38f, 3.0e38f, stream);
+    return scail_from_channels_last_frames(x.p, x.C, video, nullptr, nullptr, 3, T * H * W, f0 * H * W, x.vox(), -3.0e38f, 3.0e38f, stream);
 }
 
 }  // namespace
@@ -341,36 +491,42 @@ extern "C" int scail_vae_decode(scail_vae* h, const float* latent, float* video,
     a.trace = h->trace; a.trace_user = h->trace_user;
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= NSLOT * a.slot_bytes && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                   "workspace too small or not 256-byte aligned (scail_vae_workspace_bytes)");
-    Tens x = a.get(Tl, hl, wl, w.z_dim); VAE_CHK(a)
-    VAE_TRY(scail_to_channels_last(latent, x.p, w.dec_scale, w.dec_shift, w.z_dim, w.z_dim, Tl * hl * wl, stream));
-    Tens y;
-    VAE_TRY(conv(a, x, w.conv2, y, x.T, x.H, x.W));
-    a.put(x);
-    x = y;
-    VAE_TRY(conv(a, x, w.dec_conv1, y, x.T, x.H, x.W));
-    a.put(x);
-    x = y;
-    VAE_TRY(res_block(a, w.dec_mid0, x));
-    VAE_TRY(attn_block(a, w.dec_attn, x));
-    VAE_TRY(res_block(a, w.dec_mid2, x));
-    Tens xn;       // the next consumer's normalised input, when its producer wrote it (res_block)
-    for (size_t i = 0; i < h->dec.size(); ++i) {
-        const scail_vae_stage& s = h->dec[i];
-        const bool last = i + 1 == h->dec.size();      // the last block feeds the head's norm and nothing else
-        if (s.kind == 0) { VAE_TRY(res_block(a, s.res, x, &xn, last ? w.dec_head_gamma : next_res_gamma(h->dec, i), !last)); }
-        else if (s.kind == 2) { VAE_TRY(up_stage(a, s, x, &xn, next_res_gamma(h->dec, i))); }
-        else { scail_set_error("scail_vae_decode: downsampling stage in the decoder table"); return 1; }
+    return decode_frames(h, a, latent, video, Tl, 0, Tl, hl, wl);
+}
+
+extern "C" int64_t scail_vae_decode_stream_workspace_bytes(const scail_vae* h, int64_t chunk, int64_t hl, int64_t wl) {
+    if (h == nullptr || chunk < 2 || chunk > (1 << 20) || hl <= 0 || wl <= 0) return -1;
+    return stream_plan(*h, chunk, hl, wl).total();
+}
+
+extern "C" int scail_vae_decode_stream(scail_vae* h, const float* latent, float* video, int64_t Tl, int64_t hl, int64_t wl,
+                                       int64_t chunk, void* workspace, int64_t workspace_bytes, void* stream) {
+    SCAIL_REQUIRE(h != nullptr && video != nullptr && latent != nullptr, "null argument");
+    SCAIL_REQUIRE(Tl > 0 && hl > 0 && wl > 0, "bad latent shape");
+    SCAIL_REQUIRE(chunk >= 2 && chunk <= (1 << 20), std::string("chunk must be at least 2 latent frames (every stage needs two frames of a chunk), got ") + std::to_string(chunk));
+    const StreamPlan plan = stream_plan(*h, chunk, hl, wl);
+    SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= plan.total() && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+                  std::string("workspace too small or not 256-byte aligned (scail_vae_decode_stream_workspace_bytes): need ") +
+                      std::to_string(plan.total()) + " bytes, got " + std::to_string(workspace_bytes));
+    Arena a;
+    a.base = static_cast<char*>(workspace);
+    a.slot_bytes = plan.big;
+    a.n_small = 2; a.small_bytes = plan.small;
+    a.stream = stream;
+    a.trace = h->trace; a.trace_user = h->trace_user;
+    if (Tl <= chunk + 1) return decode_frames(h, a, latent, video, Tl, 0, Tl, hl, wl);       // one chunk: the launches of scail_vae_decode
+    a.head = 2;
+    a.carry = a.base + (NSLOT - 2) * plan.big + 2 * plan.small;
+    a.carry_bytes = plan.carry;
+    for (int64_t t0 = 0; t0 < Tl;) {
+        int64_t n = Tl - t0 < chunk ? Tl - t0 : chunk;
+        if (Tl - t0 - n == 1) ++n;                 // a remainder of one frame joins the last chunk: no stage ever sees fewer than two frames
+        a.later = t0 > 0;
+        a.carry_off = 0;
+        for (bool& u : a.used) u = false;
+        VAE_TRY(decode_frames(h, a, latent, video, Tl, t0, n, hl, wl));
+        SCAIL_REQUIRE(a.carry_off == plan.carry, "scail_vae_decode_stream: the chunk's causal convolutions do not match the carry plan");
+        t0 += n;
     }
-    if (xn.p != nullptr) {             // the head's RMS_norm + SiLU came out of the last block's epilogue
-        if (x.p != nullptr) a.put(x);
-        x = xn;
-    } else {
-        VAE_TRY(scail_rms_silu(x.p, x.p, w.dec_head_gamma, x.vox(), x.C, 1, stream));
-        a.emit("rms_silu", x);
-    }
-    VAE_TRY(conv(a, x, w.dec_head, y, x.T, x.H, x.W));
-    a.put(x);
-    x = y;
-    SCAIL_REQUIRE(x.T == T && x.H == H && x.W == W, "scail_vae_decode: stage table does not expand (4, 8, 8)");
-    return scail_from_channels_last(x.p, x.C, video, nullptr, nullptr, 3, x.vox(), -3.0e38f, 3.0e38f, stream);
+    return 0;
 }

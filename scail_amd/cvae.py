@@ -147,10 +147,27 @@ class CVae:
                torch.cuda.current_stream().cuda_stream)
         return out
 
-    def decode(self, z: torch.Tensor) -> torch.Tensor:
-        """z fp32 (zc, Tl, h, w) -> video fp32 (3, 1 + 4 (Tl - 1), 8h, 8w), not clamped."""
+    def _stream_workspace(self, chunk, h, w):
+        need = L.load().scail_vae_decode_stream_workspace_bytes(self._h, chunk, h, w)
+        if need < 0:
+            raise ValueError(f"chunk_frames must be at least 2 latent frames, got {chunk}")
+        if self._ws is None or self._ws.numel() != need:         # exactly the query's size: what a streamed decode holds does not grow with the clip
+            self._ws = None
+            self._ws = torch.empty(need, device=self._dev, dtype=torch.uint8)
+        return self._ws
+
+    def decode(self, z: torch.Tensor, chunk_frames=None) -> torch.Tensor:
+        """z fp32 (zc, Tl, h, w) -> video fp32 (3, 1 + 4 (Tl - 1), 8h, 8w), not clamped.  ``chunk_frames`` (>= 2 latent frames): the streamed
+        decode (scail_vae_decode_stream) -- same result, a workspace that depends on the chunk and not on Tl."""
         _, Tl, h, w = z.shape
         T, H, W = 1 + 4 * (Tl - 1), 8 * h, 8 * w
+        if chunk_frames is not None:
+            chunk = int(chunk_frames)
+            ws = self._stream_workspace(chunk, h, w)
+            out = torch.empty(3, T, H, W, device=z.device, dtype=torch.float32)
+            L.call("scail_vae_decode_stream", self._h, z.data_ptr(), out.data_ptr(), Tl, h, w, chunk, ws.data_ptr(), ws.numel(),
+                   torch.cuda.current_stream().cuda_stream)
+            return out
         ws = self._workspace(T, H, W)
         out = torch.empty(3, T, H, W, device=z.device, dtype=torch.float32)
         L.call("scail_vae_decode", self._h, z.data_ptr(), out.data_ptr(), Tl, h, w, ws.data_ptr(), ws.numel(),

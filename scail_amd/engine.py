@@ -96,11 +96,13 @@ class SATVideoDiffusionEngine(nn.Module):
         return samples
 
     @torch.no_grad()
-    def decode_first_stage(self, z):
-        """diffusion_video.py:298-309."""
+    def decode_first_stage(self, z, chunk_frames=None):
+        """diffusion_video.py:298-309.  ``chunk_frames`` (an extension): the VAE's streamed decode, WanVAE_.decode."""
         if self.first_stage_model is None:
             raise RuntimeError("first stage (VAE) not built; pass build_first_stage: true in the model config")
-        return self.first_stage_model.decode(1.0 / self.scale_factor * z)
+        if chunk_frames is None:
+            return self.first_stage_model.decode(1.0 / self.scale_factor * z)
+        return self.first_stage_model.decode(1.0 / self.scale_factor * z, chunk_frames=chunk_frames)
 
     @torch.no_grad()
     def encode_first_stage(self, x, batch=None, force_encode=False):

@@ -54,6 +54,8 @@ SIGNATURES = {
     "scail_transpose2d": [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p],
     "scail_to_channels_last": [_p, _p, _p, _p, _i64, _i64, _i64, _p],
     "scail_from_channels_last": [_p, _i64, _p, _p, _p, _i64, _i64, _f, _f, _p],
+    "scail_to_channels_last_frames": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p],
+    "scail_from_channels_last_frames": [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _f, _f, _p],
     "scail_attn_small": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _f, _p, _p, _p, _i64, _p],
     "scail_mul_bf16": [_p, _p, _p, _i64, _p],
     "scail_row_affine": [_p, _p, _p, _p, _i64, _i64, _i64, _p],
@@ -97,6 +99,8 @@ SIGNATURES = {
     "scail_vae_workspace_bytes": [_p, _i64, _i64, _i64],
     "scail_vae_encode": [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p],
     "scail_vae_decode": [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p],
+    "scail_vae_decode_stream_workspace_bytes": [_p, _i64, _i64, _i64],
+    "scail_vae_decode_stream": [_p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p],
 }
 # return types other than the int status: every *_bytes query answers an int64_t, the destroy functions nothing
 RESTYPES = {"scail_dit_destroy": None, "scail_vae_destroy": None, **{n: _i64 for n in SIGNATURES if n.endswith("_bytes")}}
@@ -113,7 +117,9 @@ ACT_NONE, ACT_SILU, ACT_GELU_TANH = 0, 1, 2
 # include/scail_dit.h SCAIL_DIT_FP8_*: the per-token GEMMs of a block that scail_dit_enable_fp8 switches to fp8
 FP8_GEMMS = {"qkv": 1, "o": 2, "cq": 4, "co": 8, "w1": 16, "w2": 32}
 FP8_ALL = 63
-ABI_VERSION = 8          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
+ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- scail_vae_decode_stream, its workspace query, scail_to / from_channels_last_frames --
+                         # and no existing call changed: still 8; load() fails on a library that lacks them)
+                         # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);
                          # 5 = scail_rmsnorm_rope_slabs takes a slab row stride; the sequence-parallel exchange is ONE collective per direction

@@ -301,14 +301,17 @@ class WanVAE_(nn.Module):
         return mu.unsqueeze(0)
 
     @torch.no_grad()
-    def decode(self, z: torch.Tensor, scale=None) -> torch.Tensor:
-        """z (1|-, zc, T, h, w) -> video (1, 3, 1+4(T-1), 8h, 8w) fp32, NOT clamped (wan_vae.py:544-568)."""
+    def decode(self, z: torch.Tensor, scale=None, chunk_frames=None) -> torch.Tensor:
+        """z (1|-, zc, T, h, w) -> video (1, 3, 1+4(T-1), 8h, 8w) fp32, NOT clamped (wan_vae.py:544-568).  ``chunk_frames`` (latent frames,
+        >= 2): the streamed decode of the C executor -- the same video from a workspace sized for a chunk instead of the clip."""
         if z.dim() == 5:
             assert z.shape[0] == 1
             z = z[0]
         W = self.prepare()
         if self.use_c_exec:
-            return self._c().decode(z.float().to(next(self.parameters()).device).contiguous()).unsqueeze(0)
+            return self._c().decode(z.float().to(next(self.parameters()).device).contiguous(), chunk_frames=chunk_frames).unsqueeze(0)
+        if chunk_frames is not None:
+            raise NotImplementedError("chunk_frames: the streamed decode exists in the C executor only (use_c_exec); the layer-by-layer path is whole-sequence")
         x = ops.to_channels_last(z.float().to(next(self.parameters()).device), self.z_dim, a=W["std"], b=W["mean"])
         x = ops.conv3d_cl(x, W["conv2"], x.shape[:3])
         x = ops.conv3d_cl(x, W["decoder.conv1"], x.shape[:3])
@@ -344,6 +347,6 @@ class WanVAE:
         """videos: iterable of [C, T, H, W] -> latent float (wan_vae.py:648-657)."""
         return torch.cat([self.model.encode(u.unsqueeze(0)).float() for u in videos], dim=0)
 
-    def decode(self, zs):
-        """zs: iterable of [z, T, h, w] -> float video clamped to [-1, 1] (wan_vae.py:659-666)."""
-        return torch.cat([self.model.decode(u.unsqueeze(0)).float().clamp_(-1, 1) for u in zs], dim=0)
+    def decode(self, zs, chunk_frames=None):
+        """zs: iterable of [z, T, h, w] -> float video clamped to [-1, 1] (wan_vae.py:659-666); ``chunk_frames``: WanVAE_.decode."""
+        return torch.cat([self.model.decode(u.unsqueeze(0), chunk_frames=chunk_frames).float().clamp_(-1, 1) for u in zs], dim=0)
