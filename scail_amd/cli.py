@@ -10,7 +10,8 @@ The reference's first VAE encode of [ref + zeros] (:362-365) is skipped: ``conca
 branch and is never read by the network -- a zero-size placeholder is passed.
 
 Requests: ``--ref-image ref.jpg --pose-video <frames dir | .npy | animated .webp/.png/.gif | Motion-JPEG .mp4> [--conditioning c.pt]`` runs
-the reference's preprocessing (centre crop, [-1, 1], half-resolution pose; scail_amd/preprocess.py) on files, or
+the reference's preprocessing (centre crop, [-1, 1], half-resolution pose; scail_amd/preprocess.py; ``--preprocess hip`` = on the GPU
+with the library's kernels, chunked) on files, or
 ``--inputs file.pt`` passes tensors directly: ref (3,1,H,W) in [-1,1], pose (3,T,H,W), context (1,Lt,4096),
 uncond_context (1,Lt,4096), clip (1,257,1280); without either synthetic inputs are drawn.  ``--save-dir`` writes
 ``0_output_000000.webp`` (lossless animated WebP; ``--format`` for APNG / GIF / .npy / frames, or ``.mp4`` = the reference's
@@ -172,23 +173,37 @@ def encode_conditioning(prompt: str, negative_prompt: str, ref: torch.Tensor, te
     return dict(context=ctx[0:1].contiguous(), uncond_context=ctx[1:2].contiguous(), clip=feats)
 
 
-def request_from_files(ref_image: str, pose_video: str, cfg, conditioning: str = None, device="cuda", seed=0, text_dim=4096):
+PREPROCESS_ROUTES = ("torch", "hip")
+
+
+def request_from_files(ref_image: str, pose_video: str, cfg, conditioning: str = None, device="cuda", seed=0, text_dim=4096,
+                       preprocess="torch"):
     """The reference's request assembly from files (sample_video.py:300-351): reference image + driving (pose) video ->
     centre-cropped, [-1, 1], pose at half resolution (``smpl_downsample``).  Text / CLIP conditioning comes from
     ``conditioning`` (a .pt with context, uncond_context, clip) -- the T5 tokenizer files are not available offline --
-    or is drawn synthetically."""
-    from . import preprocess, video_io
+    or is drawn synthetically.  ``preprocess``: "torch" (default) resizes on the host with torch over the whole clip; "hip" sends the
+    clip to ``device`` as uint8, a chunk of frames at a time, and resizes / crops / halves it with the library's kernels
+    (scail_amd/preprocess.py ``*_hip``; needs a GPU)."""
+    from . import preprocess as pp, video_io
+    if preprocess not in PREPROCESS_ROUTES:
+        raise ValueError(f"preprocess must be one of {PREPROCESS_ROUTES}, got {preprocess!r}")
     img = video_io.load_image_to_tensor_chw_normalized(ref_image)                       # (1, 3, H, W) in [-1, 1]
-    H, W = preprocess.target_size((img.shape[2], img.shape[3]), cfg.get("args", {}).get("sampling_image_size", [512, 896]))
-    img = preprocess.prepare_reference_image(img, (H, W))
-    pose = video_io.load_video_for_pose_sample(pose_video).permute(0, 3, 1, 2)         # T H W C -> T C H W (:339)
-    _, smpl = preprocess.prepare_pose_video(pose, (H, W), downsample=True)
-    req = synthetic_request(H, W, smpl.shape[0], text_dim, 512 if text_dim == 4096 else 12, device, seed)
+    H, W = pp.target_size((img.shape[2], img.shape[3]), cfg.get("args", {}).get("sampling_image_size", [512, 896]))
+    if preprocess == "hip":
+        img = pp.prepare_reference_image_hip(img, (H, W), device=device)
+        smpl = pp.prepare_pose_video_hip(video_io.load_video_for_pose_sample(pose_video), (H, W), device=device)[1]   # (3, T, H/2, W/2)
+        n_frames = smpl.shape[1]
+    else:
+        img = pp.prepare_reference_image(img, (H, W))
+        pose = video_io.load_video_for_pose_sample(pose_video).permute(0, 3, 1, 2)     # T H W C -> T C H W (:339)
+        smpl = pp.prepare_pose_video(pose, (H, W), downsample=True)[1].permute(1, 0, 2, 3).contiguous().to(device)   # (3, T, H/2, W/2)
+        n_frames = smpl.shape[1]
+    req = synthetic_request(H, W, n_frames, text_dim, 512 if text_dim == 4096 else 12, device, seed)
     if conditioning:
         req.update({k: v.to(device) for k, v in torch.load(conditioning, map_location="cpu").items()
                     if k in ("context", "uncond_context", "clip")})
-    req["ref"] = img.permute(1, 0, 2, 3).contiguous().to(device)                        # (3, 1, H, W)
-    req["pose"] = smpl.permute(1, 0, 2, 3).contiguous().to(device)                      # (3, T, H/2, W/2)
+    req["ref"] = img[0].unsqueeze(1).contiguous().to(device)                            # (1, 3, H, W) -> (3, 1, H, W), dense strides on either route
+    req["pose"] = smpl
     return req, (H, W)
 
 
@@ -285,7 +300,7 @@ def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_ch
     return _finish(engine, z, t0, vae_chunk_frames)
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--base", nargs="*", default=[])
     ap.add_argument("--tiny", action="store_true")
@@ -321,6 +336,15 @@ def main(argv=None):
                          "the VAE workspace then depends on this number and the frame size instead of the clip length (512x896: 10.9 GB with 4 instead of 85 GB "
                          "for 161 frames), at the price of smaller launches and two frame copies per causal convolution and chunk; same video. "
                          "Unset: one pass over the whole clip")
+    ap.add_argument("--preprocess", choices=PREPROCESS_ROUTES, default="torch",
+                    help="where the reference image and the driving video are resized, cropped and halved: torch = on the host, the whole clip "
+                         "at once as fp32; hip = on the GPU with the library's kernels, the clip crossing as uint8 a chunk of frames at a time "
+                         "(bounded host and device memory for long clips)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.vae_chunk_frames is not None and a.vae_chunk_frames < 2:
         ap.error(f"--vae-chunk-frames must be at least 2 latent frames, got {a.vae_chunk_frames}")
@@ -343,7 +367,7 @@ def main(argv=None):
         for line, cnt in lines:
             text, input_dir, image_path, pose_path = parse_request(line)
             print(cnt, ": ", text)
-            req = request_from_files(image_path, pose_path, cfg, a.conditioning, seed=a.seed, text_dim=td)[0]
+            req = request_from_files(image_path, pose_path, cfg, a.conditioning, seed=a.seed, text_dim=td, preprocess=a.preprocess)[0]
             if a.tokenizer:
                 req.update(encode_conditioning(text, a.negative_prompt, req["ref"], td, a.tokenizer, a.t5_ckpt, a.clip_ckpt,
                                                max_length=512 if td == 4096 else 16))
@@ -364,7 +388,7 @@ def main(argv=None):
         if not (a.ref_image and a.pose_video):
             ap.error("--ref-image and --pose-video go together")
         def inputs(text_dim):
-            req = request_from_files(a.ref_image, a.pose_video, cfg, a.conditioning, seed=a.seed, text_dim=text_dim)[0]
+            req = request_from_files(a.ref_image, a.pose_video, cfg, a.conditioning, seed=a.seed, text_dim=text_dim, preprocess=a.preprocess)[0]
             if a.prompt is not None:
                 if not a.tokenizer:
                     ap.error("--prompt needs --tokenizer (tokenizer files are not bundled)")

@@ -65,6 +65,8 @@ SIGNATURES = {
     "scail_bf16_to_f32": [_p, _p, _i64, _p],
     "scail_quant_fp8_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _p],
     "scail_gemm_fp8": [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _i64, _p, _i64, _i64, _p],
+    "scail_resize_crop_aa": [_p, _i, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
+    "scail_pose_half": [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p],
     # include/scail_dit.h (structs are passed by pointer; scail_amd/cstep.py builds them)
     "scail_dit_create": [_p, _p, _p],
     "scail_dit_destroy": [_p],
@@ -117,8 +119,12 @@ ACT_NONE, ACT_SILU, ACT_GELU_TANH = 0, 1, 2
 # include/scail_dit.h SCAIL_DIT_FP8_*: the per-token GEMMs of a block that scail_dit_enable_fp8 switches to fp8
 FP8_GEMMS = {"qkv": 1, "o": 2, "cq": 4, "co": 8, "w1": 16, "w2": 32}
 FP8_ALL = 63
+# include/scail_hip.h scail_resize_crop_aa: source layouts, and the largest in / out per axis its tap budget covers
+SRC_U8_NHWC, SRC_F32_NCHW = 0, 1
+RESIZE_MAX_SCALE = 16
 ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- scail_vae_decode_stream, its workspace query, scail_to / from_channels_last_frames --
-                         # and no existing call changed: still 8; load() fails on a library that lacks them)
+                         # and no existing call changed: still 8; load() fails on a library that lacks them; likewise the request
+                         # preprocessing, scail_resize_crop_aa / scail_pose_half)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);

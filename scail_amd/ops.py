@@ -390,6 +390,47 @@ def tile_finish_(x, den, inv_wsum, dsigma):
     return x
 
 
+# ---- request preprocessing (include/scail_hip.h scail_resize_crop_aa / scail_pose_half) ----
+def resize_crop_aa(src, resized_hw, top, left, out_hw, out=None):
+    """Antialiased bicubic resize to the virtual size ``resized_hw`` of which the window ``[top, top + Ho) x [left, left + Wo)``,
+    ``out_hw = (Ho, Wo)``, is computed.  src: uint8 channels-last (n, H, W, C) -- the result is rounded half-to-even and clamped to
+    [0, 255] -- or fp32 planar (n, C, H, W), not rounded.  -> fp32 planar (n, C, Ho, Wo)."""
+    if src.dtype == torch.uint8:
+        _chk(src, torch.uint8, "resize_crop_aa.src")
+        kind, (n, Hin, Win, Cc) = L.SRC_U8_NHWC, src.shape
+    else:
+        _chk(src, f32, "resize_crop_aa.src")
+        kind, (n, Cc, Hin, Win) = L.SRC_F32_NCHW, src.shape
+    assert src.is_contiguous()
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    if out is None:
+        out = torch.empty((n, Cc, Ho, Wo), device=src.device, dtype=f32)
+    _chk(out, f32, "resize_crop_aa.out")
+    assert out.is_contiguous() and tuple(out.shape) == (n, Cc, Ho, Wo)
+    L.call("scail_resize_crop_aa", src.data_ptr(), kind, out.data_ptr(), n, Cc, Hin, Win, int(resized_hw[0]), int(resized_hw[1]),
+           int(top), int(left), Ho, Wo, _stream())
+    return out
+
+
+def pose_half(x, out_half=None, want_full=False, out_full=None):
+    """x fp32 (n, C, H, W), the rounded 0..255 pixels -> (half, full): ``half`` (n, C, H/2, W/2) = the 2 x 2 block means of
+    p = (x - 127.5) / 127.5, ``full`` = p (n, C, H, W) -- with ``want_full`` or into a dense ``out_full`` -- or None.  ``out_half`` may be any (n, C, H/2, W/2) VIEW whose planes are dense
+    (e.g. ``big[:, t0:t1].permute(1, 0, 2, 3)`` of a (C, T, H/2, W/2) tensor): the chunk is written straight into its slot."""
+    _chk(x, f32, "pose_half.x")
+    assert x.is_contiguous() and x.dim() == 4
+    n, Cc, H, W = x.shape
+    if out_half is None:
+        out_half = torch.empty((n, Cc, H // 2, W // 2), device=x.device, dtype=f32)
+    _chk(out_half, f32, "pose_half.out_half")
+    assert tuple(out_half.shape) == (n, Cc, H // 2, W // 2) and (out_half.numel() == 0 or (out_half.stride(3) == 1 and out_half.stride(2) == W // 2))
+    full = torch.empty_like(x) if want_full and out_full is None else out_full
+    if full is not None:
+        _chk(full, f32, "pose_half.out_full")
+        assert full.is_contiguous() and full.shape == x.shape
+    L.call("scail_pose_half", x.data_ptr(), out_half.data_ptr(), out_half.stride(0), out_half.stride(1), _ptr(full), n, Cc, H, W, _stream())
+    return out_half, full
+
+
 def to_bf16(x):
     _chk(x, f32, "to_bf16.x")
     x = x.contiguous()
