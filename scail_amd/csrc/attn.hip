@@ -1256,15 +1256,6 @@ extern "C" int scail_cross_attn2_bf16(const scail_bf16* q, int64_t q_bs, int64_t
         a.pad = 0;
         return scail_module_launch("cross_attn2 (attn4_x2)", fn, (unsigned)a.n_wgs, 256, a, stream);
     }
-    static ScailDeviceOnce attr_set;
-    if (attr_set.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cross_attn2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, X2_LDS_BYTES);
-        if (e != hipSuccess) {
-            scail_set_error(std::string("cross_attn2: hipFuncSetAttribute failed: ") + hipGetErrorString(e));
-            return 2;
-        }
-        attr_set.done();
-    }
     Cross2Params p;
     p.q = q; p.q_bs = q_bs; p.q_rs = q_rs;
     p.k0 = k1; p.k0_bs = k1_bs; p.k0_rs = k1_rs; p.vt0 = vt1; p.vt0_bs = vt1_bs; p.Lk0 = (int)Lk1; p.Lkp0 = (int)((Lk1 + KVBLK - 1) / KVBLK * KVBLK);
@@ -1273,6 +1264,5 @@ extern "C" int scail_cross_attn2_bf16(const scail_bf16* q, int64_t q_bs, int64_t
     p.heads = (int)heads; p.Lq = (int)Lq;
     p.sl2 = prescaled ? 1.0f : scale * 1.44269504088896340736f;
     dim3 grid((unsigned)((Lq + 127) / 128), (unsigned)heads, (unsigned)n_batch);
-    hipLaunchKernelGGL(cross_attn2_kernel, grid, dim3(X2_THREADS), X2_LDS_BYTES, (hipStream_t)stream, p);
-    return scail_check_launch("cross_attn2");
+    return scail_launch_lds<cross_attn2_kernel>("cross_attn2", X2_LDS_BYTES, grid, dim3(X2_THREADS), X2_LDS_BYTES, stream, p);
 }

@@ -71,6 +71,23 @@ struct ScailDeviceOnce {
     void done() { mask.fetch_or(device_bit(), std::memory_order_release); }
 };
 
+// Launch `Kernel` with `lds` bytes of dynamic LDS; the first launch on each device opts the kernel in to `lds_max` bytes (more than the
+// 64 KB a kernel gets unasked).  0, or 2 + scail_last_error "<what>: hipFuncSetAttribute failed: ..." / "<what>: launch failed: ...".
+template <auto Kernel, class... Args>
+int scail_launch_lds(const char* what, int lds_max, dim3 grid, dim3 block, size_t lds, void* stream, const Args&... args) {
+    static ScailDeviceOnce attr_set;
+    if (attr_set.need()) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+        if (e != hipSuccess) {
+            scail_set_error(std::string(what) + ": hipFuncSetAttribute failed: " + hipGetErrorString(e));
+            return 2;
+        }
+        attr_set.done();
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, (hipStream_t)stream, args...);
+    return scail_check_launch(what);
+}
+
 // ---- bf16 <-> f32 -----------------------------------------------------------------------------
 __device__ __forceinline__ float bf2f(u16 v) { return __uint_as_float(((uint32_t)v) << 16); }
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }

@@ -13,6 +13,7 @@
 #include "common.h"
 #include <atomic>
 #include <algorithm>
+#include <cstring>
 
 #define CBM 128
 #define CBK 64
@@ -1108,53 +1109,32 @@ int scail_conv4_kernel(const char* suffix) { g_conv4_suffix = suffix ? suffix : 
 static constexpr int g_conv_halo = 4;
 #endif
 
-// the shapes the generated kernels cover: 3x3x3, stride 1, 'same' spatial extent, 0..2 padding frames in front, whole 32-channel slices and
-// 96-channel output tiles, at least one frame pair, 32-bit byte offsets inside a frame, and a tile grid whose id decode is exact: the kernel
-// divides a tile id by tiles_n, tiles_t and tiles_w with 31-bit magic numbers, exact while dividend x divisor < 2^31
+// the shapes the generated kernels cover.  All of them: 3 x 3 spatial taps, stride 1, padding 1, whole 32-channel slices, at least one frame pair,
+// 32-bit byte offsets inside a frame (row stride `ld`: the longest of the call), and a tile grid whose id decode is exact: the kernel divides a
+// tile id by tiles_n, tiles_t and tiles_w with 31-bit magic numbers, exact while dividend x divisor < 2^31
 static int64_t conv4_tiles(const ConvParams& p) { return (int64_t)((p.To + 1) / 2) * ((p.Ho + 15) / 16) * ((p.Wo + 15) / 16) * std::max(p.N / 96, 1); }
+static bool conv4_common(const ConvParams& p, int64_t ld) {
+    if (p.N <= 0 || p.To < 2 || p.Ho <= 0 || p.Wo <= 0) return false;
+    const int64_t max_div = std::max<int64_t>({p.N / 96, (p.To + 1) / 2, (p.Wo + 15) / 16});
+    return conv4_tiles(p) * max_div < (1ll << 31) && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && p.ph == 1 && p.pw == 1 &&
+           p.Cin % 32 == 0 && ld < (1 << 20) && (int64_t)p.Hi * p.Wi * p.Cin * 2 < (1ll << 31) && (int64_t)p.Ho * p.Wo * ld * 2 < (1ll << 32);
+}
+// 3x3x3, 'same' spatial extent, 0..2 padding frames in front
+static bool conv4_3x3x3(const ConvParams& p) { return p.kt == 3 && !p.ups && p.Ho == p.Hi && p.Wo == p.Wi && p.pt >= 0 && p.pt <= 2; }
+// ... with whole 96-channel output tiles
 static bool conv4_eligible(const ConvParams& p, int64_t ldc, int64_t ldr) {
-    if (p.N <= 0 || p.N % 96 != 0 || p.To < 2 || p.Ho <= 0 || p.Wo <= 0) return false;
-    const int64_t max_div = std::max<int64_t>({p.N / 96, (p.To + 1) / 2, (p.Wo + 15) / 16});
-    if (conv4_tiles(p) * max_div >= (1ll << 31)) return false;
-    return p.kt == 3 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && !p.ups && p.ph == 1 && p.pw == 1 &&
-           p.Ho == p.Hi && p.Wo == p.Wi && p.Cin % 32 == 0 && p.N % 96 == 0 && p.To >= 2 && p.pt >= 0 && p.pt <= 2 &&
-           ldc % 8 == 0 && ldr % 8 == 0 && ldc < (1 << 20) && ldr < (1 << 20) && (int64_t)p.Hi * p.Wi * p.Cin * 2 < (1ll << 31) &&
-           (int64_t)p.Ho * p.Wo * std::max(ldc, ldr) * 2 < (1ll << 32);
+    return p.N % 96 == 0 && conv4_common(p, std::max(ldc, ldr)) && conv4_3x3x3(p) && ldc % 8 == 0 && ldr % 8 == 0;
 }
-
-// the kt = 1 kernels: 1 x 3 x 3, stride 1, padding (0, 1, 1), every output frame from the input frame of the same index, same extent or
-// (ups) exactly twice the input's; otherwise the limits above (32-bit byte offsets inside an INPUT frame)
+// the kt = 1 kernels: 1 x 3 x 3, padding (0, 1, 1), every output frame from the input frame of the same index, same extent or (ups) exactly
+// twice the input's (the byte offsets are those inside an INPUT frame)
 static bool conv4u_eligible(const ConvParams& p, int64_t ldc) {
-    if (p.N <= 0 || p.N % 96 != 0 || p.To < 2 || p.Ho <= 0 || p.Wo <= 0) return false;
-    const int64_t max_div = std::max<int64_t>({p.N / 96, (p.To + 1) / 2, (p.Wo + 15) / 16});
-    if (conv4_tiles(p) * max_div >= (1ll << 31)) return false;
     const bool extent = p.ups ? (p.Ho == 2 * p.Hi && p.Wo == 2 * p.Wi) : (p.Ho == p.Hi && p.Wo == p.Wi);
-    return p.kt == 1 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && p.pt == 0 && p.ph == 1 && p.pw == 1 && extent &&
-           p.Ti == p.To && p.Cin % 32 == 0 && ldc % 8 == 0 && ldc < (1 << 20) && (int64_t)p.Hi * p.Wi * p.Cin * 2 < (1ll << 31) &&
-           (int64_t)p.Ho * p.Wo * ldc * 2 < (1ll << 32);
+    return p.N % 96 == 0 && conv4_common(p, ldc) && p.kt == 1 && p.pt == 0 && extent && p.Ti == p.To && ldc % 8 == 0;
 }
-
-// the narrow-output kernel: the 3x3x3 shapes of conv4_eligible with N = 8 or 16 output channels (one n tile, W rows past N read zeros), no
-// residual; 8-byte stores (ldc % 4 == 0)
+// the narrow-output kernel: the 3x3x3 shapes with N = 8 or 16 output channels (one n tile, W rows past N read zeros), no residual; 8-byte
+// stores (ldc % 4 == 0)
 static bool conv4n_eligible(const ConvParams& p, int64_t ldc) {
-    if (p.N != 8 && p.N != 16) return false;
-    if (p.To < 2 || p.Ho <= 0 || p.Wo <= 0) return false;
-    const int64_t max_div = std::max<int64_t>((p.To + 1) / 2, (p.Wo + 15) / 16);
-    if (conv4_tiles(p) * max_div >= (1ll << 31)) return false;
-    return p.kt == 3 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && !p.ups && p.ph == 1 && p.pw == 1 &&
-           p.Ho == p.Hi && p.Wo == p.Wi && p.Cin % 32 == 0 && p.pt >= 0 && p.pt <= 2 && ldc % 4 == 0 && ldc >= p.N && ldc < (1 << 20) &&
-           (int64_t)p.Hi * p.Wi * p.Cin * 2 < (1ll << 31) && (int64_t)p.Ho * p.Wo * ldc * 2 < (1ll << 32);
-}
-
-// the direct-gather kernel's dual-output form (conv_direct_kernel<14, 3, true>): 96 output channels, up to 14 k-steps of 16 (the encoder's stem: 3 x 3 x 3 taps
-// of 8 padded channels), no residual, no upsample; shape conditions of the plain dispatch in conv3d_impl
-static bool conv_direct_dual_eligible(const ConvParams& p, int64_t ldc) {
-    const int ksteps = (p.Ktrue + 15) / 16;
-    const int wld = ksteps * 16 + 8;
-    const int lds = (p.N * wld + 8 * 32 * CD_STRIP_LD) * 2 + 2 * p.N * 4;
-    return p.N == 96 && ksteps <= 14 && !p.ups && p.Cin % 8 == 0 && p.kt <= 30 && p.kh <= 31 && p.kw <= 31 && p.Cin < 65536 &&
-           (int64_t)(p.kt + 1) * p.Hi * p.Wi * p.Cin < (1ll << 31) && lds <= 150 * 1024 && ldc % 8 == 0 && p.M >= 4096 && p.M < (1ll << 40) &&
-           p.Ho * (int64_t)p.Wo < (1ll << 31) && p.Ho * (int64_t)p.Wo >= 32;
+    return (p.N == 8 || p.N == 16) && conv4_common(p, ldc) && conv4_3x3x3(p) && ldc % 4 == 0 && ldc >= p.N;
 }
 
 static void conv_params(ConvParams& p, const int32_t* geom) {
@@ -1169,24 +1149,199 @@ static void conv_params(ConvParams& p, const int32_t* geom) {
     p.M = (int64_t)p.To * p.Ho * p.Wo;
 }
 
-extern "C" int scail_conv3d_kernel_for(const int32_t* geom, int64_t ldc, int64_t ldr, int fused_norm) {
-    if (geom == nullptr) return 0;
+// ------------------------------------------------------------------------------------------------
+// Which kernel a convolution runs.  conv_choose is the ONE statement of it: conv3d_impl launches what it says, and the host-only queries
+// (scail_conv3d_kernel_for, scail_conv3d_norm_fused_for, scail_conv3d_kernel_name_for) are projections of the same answer.  Nothing else reads
+// a convolution option, a measurement-build knob or an eligibility predicate.
+// ------------------------------------------------------------------------------------------------
+enum ConvFamily { CONV_GEN, CONV_GEN_K1, CONV_GEN_NARROW,      // generated: 3x3x3 (conv4_eligible), kt = 1 (conv4u_eligible), narrow (conv4n_eligible)
+                  CONV_HALO, CONV_HALO_UPS, CONV_S2, CONV_DIRECT, CONV_IGEMM };      // hipcc: conv_halo_kernel (UPS: behind the 2x upsample), conv_s2_kernel, conv_direct_kernel, conv_igemm_kernel
+// the call: scail_conv3d_cl | scail_conv3d_cl_norm | scail_conv3d_cl_resid_norm with the raw output | the same without it (y == NULL)
+enum ConvForm { CONV_PLAIN = 0, CONV_NORM = 1, CONV_NEXT_NORM = 2, CONV_NEXT_NORM_ONLY = 3 };
+struct ConvChoice {
+    ConvFamily family = CONV_IGEMM;
+    bool covers = true;          // one launch of `name` is the whole call.  false: a next-norm call is the plain convolution described here + scail_rms_silu; a conv + norm call is rejected
+    std::string name;            // generated: the symbol, in the code object of conv4.s (in_conv4) or of conv4u.s;  hipcc: the template with the arguments of the instantiation ...
+    bool in_conv4 = false;
+    int (*launch)(const char* what, const ConvParams& p, unsigned grid, const ConvChoice& c, void* stream) = nullptr;      // ... and that instantiation's launch
+    int nsplit = 1, wld = 0, lds = 0;      // direct: launches (N = 384: two of 192 channels), padded W row, dynamic LDS bytes
+    int64_t tiles = 0;           // workgroups of the grid (generated: tiles that the persistent workgroups share; direct: sized by the device, 0 here)
+    int64_t vtiles = 0;          // S2: voxel tiles
+};
+
+template <int EPI, int CS, int NWB, bool SWZ = false, int BN = 96, int NF = 1, int KT = 3, bool UPS = false, int PF = 0>   // EPI 0: bias, 3: + residual, 4: + RMS_norm + SiLU
+static int launch_conv_halo_kernel(const char* what, const ConvParams& p, unsigned grid, const ConvChoice&, void* stream) {
+    constexpr int lds = HaloCfg<CS, NWB, SWZ, BN, NF, KT, UPS, PF>::LDS;
+    return scail_launch_lds<conv_halo_kernel<EPI, CS, NWB, SWZ, BN, NF, KT, UPS, PF>>(what, lds, dim3(grid), dim3(256), lds, stream, p);
+}
+template <int NF>
+static int launch_conv_s2_kernel(const char* what, const ConvParams& p, unsigned grid, const ConvChoice& c, void* stream) {
+    return scail_launch_lds<conv_s2_kernel<NF>>(what, S2Cfg<NF>::LDS, dim3(grid), dim3(256), S2Cfg<NF>::LDS, stream, p, (int)c.vtiles);
+}
+template <int KS, int NB, bool DUAL = false>
+static int launch_conv_direct_kernel(const char* what, const ConvParams& p, unsigned grid, const ConvChoice& c, void* stream) {
+    return scail_launch_lds<conv_direct_kernel<KS, NB, DUAL>>(what, 150 * 1024, dim3(grid), dim3(CD_THREADS), c.lds, stream, p, c.wld);
+}
+template <int EPI, int BN, int WM, int WN>
+static int launch_conv_igemm_kernel(const char* what, const ConvParams& p, unsigned grid, const ConvChoice&, void* stream) {
+    constexpr int lds = 2 * (CBM + BN) * CLDT * 2;
+    return scail_launch_lds<conv_igemm_kernel<EPI, BN, WM, WN>>(what, lds, dim3(grid), dim3(CONV_THREADS), lds, stream, p);
+}
+// one instantiation, by name and by launch; KERNEL_EPI: the residual epilogue where there is a residual
+#define KERNEL(K_, ...) (c.name = #K_ "<" #__VA_ARGS__ ">", c.launch = &launch_##K_<__VA_ARGS__>)
+#define KERNEL_EPI(K_, ...) (resid ? KERNEL(K_, 3, __VA_ARGS__) : KERNEL(K_, 0, __VA_ARGS__))
+
+static ConvChoice conv_choose(const ConvParams& p, int64_t ldc, int64_t ldr, bool resid, ConvForm form, bool aligned) {
+    ConvChoice c;
+    const bool fuse = form == CONV_NORM;
+    auto generated = [&](ConvFamily f, const std::string& name) {
+        c.family = f; c.name = name; c.tiles = conv4_tiles(p);        // (eligible: tiles x the largest divisor < 2^31, so the magic-number divisions are exact)
+        c.in_conv4 = name.rfind("scail_conv4_", 0) == 0;              // conv4.s holds scail_conv4_e0 / e3 and their measurement-build variants, conv4u.s every other generated convolution
+        return c;
+    };
+    // HBM-bound shapes: the direct-gather kernel (comment above conv_direct_kernel); N = 384 as two launches of 192 channels
+    // (instantiated: up to 6 k-steps with 32 / 64 / 96 / 128 / 192 channels -- the 1x1x1 convolutions of up to 96 input channels --, up to
+    // 14 k-steps with 96 channels -- the stem; 14 x 192 and 20 x 96 were built and spill 46 / 22 registers: those shapes stay on the gather kernel)
+    const int ksteps = (p.Ktrue + 15) / 16, nsplit = p.N == 384 ? 2 : 1, nn = p.N / nsplit, nb = nn / 32;
+    auto direct = [&](bool dual) {
+        const bool shape = ((ksteps <= 6 && (nb == 1 || nb == 2 || nb == 3 || nb == 4 || nb == 6)) || (ksteps <= 14 && nb == 3)) &&
+                           p.kt <= 30 && p.kh <= 31 && p.kw <= 31 && p.Cin < 65536 && (int64_t)(p.kt + 1) * p.Hi * p.Wi * p.Cin < (1ll << 31);
+        const int wld = ksteps * 16 + 8;                              // padded W row: 16 consecutive rows start in distinct 16-byte bank groups
+        const int lds = (nn * wld + 8 * 32 * CD_STRIP_LD) * 2 + 2 * nn * 4;        // W, the waves' strips, bias + gamma
+        if (!(g_conv_direct && !p.ups && !resid && p.Cin % 8 == 0 && nn % 32 == 0 && shape && (!dual || nb == 3) && lds <= 150 * 1024 && ldc % 8 == 0 &&
+              aligned && p.M >= 4096 && p.M < (1ll << 40) && p.Ho * (int64_t)p.Wo < (1ll << 31) && p.Ho * (int64_t)p.Wo >= 32))
+            return false;
+        c.family = CONV_DIRECT; c.nsplit = nsplit; c.wld = wld; c.lds = lds;
+        if (dual) KERNEL(conv_direct_kernel, 14, 3, true);
+        else if (ksteps > 6) KERNEL(conv_direct_kernel, 14, 3);
+        else nb == 1 ? KERNEL(conv_direct_kernel, 6, 1) : nb == 2 ? KERNEL(conv_direct_kernel, 6, 2) : nb == 3 ? KERNEL(conv_direct_kernel, 6, 3)
+             : nb == 4 ? KERNEL(conv_direct_kernel, 6, 4) : KERNEL(conv_direct_kernel, 6, 6);
+        return true;
+    };
+    if (form >= CONV_NEXT_NORM) {
+        // (residual sum +) the NEXT consumer's RMS_norm + SiLU in one launch: one n tile of 96 dense channels.  With a residual the 3x3x3 kernels with
+        // tile continuation (scail_conv4c_e5, e6 without the raw sum), without one the kt = 1 kernel (scail_conv4u_e7) or the direct-gather kernel's
+        // dual-output form (the encoder's stem: 3 x 3 x 3 taps of 8 padded channels); both of these write the raw output too
+        const bool dense = g_conv4 && g_conv4_resnorm && g_conv4_suffix.empty() && aligned && p.N == 96 && ldc == 96 && p.ot_mul == 1 && p.ot_off == 0;
+        if (dense && resid && g_conv4_cont && conv4_eligible(p, ldc, ldr)) return generated(CONV_GEN, form == CONV_NEXT_NORM ? "scail_conv4c_e5" : "scail_conv4c_e6");
+        if (dense && !resid && form == CONV_NEXT_NORM) {
+            if (conv4u_eligible(p, ldc)) return generated(CONV_GEN_K1, "scail_conv4u_e7");
+            if (!conv4_eligible(p, ldc, ldc) && !conv4n_eligible(p, ldc) && direct(true)) return c;
+        }
+        c = conv_choose(p, ldc, ldr, resid, CONV_PLAIN, aligned);       // everything else: the two separate calls
+        c.covers = false;
+        return c;
+    }
+    if (g_conv4 && aligned) {       // (16-byte row chunks; the arena's tensors always are)
+        // one n tile: runs of frame pairs per workgroup (a measurement-build kernel variant takes precedence)
+        const bool cont = g_conv4_cont && g_conv4_suffix.empty() && std::max(p.N / 96, 1) == 1;
+        // (measurement build: the "_prof" variant is an e0 kernel that writes its phase timers through the residual pointer)
+        const bool prof = g_conv4_suffix.find("prof") != std::string::npos;
+        if (!fuse && !resid && conv4u_eligible(p, ldc)) return generated(CONV_GEN_K1, "scail_conv4u_e0");
+        if (!fuse && !resid && conv4n_eligible(p, ldc)) return generated(CONV_GEN_NARROW, g_conv4_cont && g_conv4_suffix.empty() ? "scail_conv4cn_e0" : "scail_conv4n_e0");      // (8-byte stores)
+        // conv -> RMS_norm -> SiLU (scail_conv3d_cl_norm) on the generated kernel: one n tile of 96 channels; gamma travels in the residual argument
+        if (fuse && !resid && p.N == 96 && conv4_eligible(p, ldc, ldc)) return generated(CONV_GEN, cont ? "scail_conv4c_e4" : "scail_conv4f_e4");
+        if (!fuse && conv4_eligible(p, ldc, resid ? ldr : ldc))
+            return generated(CONV_GEN, cont ? (resid ? "scail_conv4c_e3" : "scail_conv4c_e0") : std::string(resid && !prof ? "scail_conv4_e3" : "scail_conv4_e0") + g_conv4_suffix);
+    }
+    const int64_t frame_tiles = (int64_t)((p.Ho + HT_TH - 1) / HT_TH) * ((p.Wo + HT_TW - 1) / HT_TW);
+    // 3x3x3 stride-1 causal convolutions: halo-tile kernel.  Knob conv_halo: 0 off, 1 = 48-channel slices / 1 workgroup
+    // per CU, 4 (default) = 3 with TWO output frames per workgroup (4-frame patch, every W fragment used for both frames:
+    // +22-25 % on the 96 / 192 / 384-channel shapes, bit-identical), 3 = 32-channel slices, one padded W buffer (two
+    // barriers per tap row), 2 workgroups per CU,
+    // 2 = 32-channel slices, swizzled unpadded layout with two W buffers (one barrier per tap row), 2 workgroups per CU --
+    // measured equal (283 / 490 ms vs 281 / 487 ms encode / decode): the barrier is not what bounds the kernel;
+    // 5 = 4 with the fragment prefetch one tap ahead (A/B).  conv + RMS_norm + SiLU: always the halo kernel, whatever the knob says
+    if ((g_conv_halo || fuse) && p.kt == 3 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && !p.ups &&
+        p.ph == 1 && p.pw == 1 && p.Ho == p.Hi && p.Wo == p.Wi &&
+        p.Cin % ((g_conv_halo == 1 && p.N > 32 && !fuse) ? 48 : 32) == 0 && (fuse ? p.N <= 96 : (p.N <= 32 || p.N >= 48))) {      // (fused epilogue: one N tile)
+        c.family = CONV_HALO;
+        const int bn = p.N <= 32 ? 32 : 96;
+        const int nf = ((g_conv_halo == 4 || g_conv_halo == 5 || fuse) && bn == 96 && p.To >= 2) ? 2 : 1;   // output frames per workgroup (an odd last frame pair wastes half a tile: 1 / 81)
+        c.tiles = (int64_t)((p.To + nf - 1) / nf) * frame_tiles * (fuse ? 1 : (p.N + bn - 1) / bn);
+        if (fuse) bn == 32 ? KERNEL(conv_halo_kernel, 4, 32, 1, false, 32) : nf == 2 ? KERNEL(conv_halo_kernel, 4, 32, 1, false, 96, 2) : KERNEL(conv_halo_kernel, 4, 32, 1, false, 96);
+        else if (bn == 32) KERNEL_EPI(conv_halo_kernel, 32, 1, false, 32);
+#ifdef SCAIL_ABLATIONS
+        else if (nf == 2 && g_conv_halo == 5) KERNEL_EPI(conv_halo_kernel, 32, 1, false, 96, 2, 3, false, 1);
+        else if (nf == 1 && g_conv_halo == 1) KERNEL_EPI(conv_halo_kernel, 48, 2, false, 96);
+        else if (nf == 1 && g_conv_halo == 2) KERNEL_EPI(conv_halo_kernel, 32, 2, true, 96);
+#endif
+        else nf == 2 ? KERNEL_EPI(conv_halo_kernel, 32, 1, false, 96, 2) : KERNEL_EPI(conv_halo_kernel, 32, 1, false, 96);
+        return c;
+    }
+    if (fuse) {
+        c.covers = false;
+        return c;
+    }
+    // the 1x3x3 convolution behind the nearest 2x upsample (Resample 'upsample2d/3d', wan_vae.py:110-121): halo tile with
+    // the upsampling folded into the patch load, two output frames per workgroup
+    if (g_conv_halo == 4 && p.kt == 1 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && p.ups &&
+        p.pt == 0 && p.ph == 1 && p.pw == 1 && p.Ho == 2 * p.Hi && p.Wo == 2 * p.Wi && p.To == p.Ti && p.To >= 2 &&
+        p.Cin % 32 == 0 && p.N >= 48) {
+        c.family = CONV_HALO_UPS;
+        c.tiles = (int64_t)((p.To + 1) / 2) * frame_tiles * ((p.N + 95) / 96);
+        KERNEL_EPI(conv_halo_kernel, 32, 1, false, 96, 2, 1, true);
+        return c;
+    }
+    // Resample's spatial downsampling: 1 x 3 x 3, stride (1, 2, 2), zero padding behind the last row / column only (conv_s2_kernel)
+    if (g_conv_s2 && !resid && p.kt == 1 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 2 && p.sw == 2 && !p.ups &&
+        p.pt == 0 && p.ph == 0 && p.pw == 0 && p.To == p.Ti && p.Cin % S2_CS == 0 && p.N % 96 == 0 &&
+        2 * (int64_t)p.Hi * p.Wi * p.Cin < (1ll << 31) && (int64_t)p.N * p.Kpad < (1ll << 31)) {
+        c.family = CONV_S2;
+        const int nf = (g_conv_s2 == 2 && p.To >= 2) ? 2 : 1;
+        c.vtiles = (int64_t)((p.To + nf - 1) / nf) * ((p.Ho + S2_TH - 1) / S2_TH) * ((p.Wo + S2_TW - 1) / S2_TW);
+        c.tiles = (c.vtiles + 7) / 8 * 8 * (p.N / 96);
+        nf == 2 ? KERNEL(conv_s2_kernel, 2) : KERNEL(conv_s2_kernel, 1);
+        return c;
+    }
+    if (direct(false)) return c;
+    // implicit GEMM.  N tile: of 128 / 96 / 64 the one with the fewest padding columns (ties -> the wider tile)
+    c.family = CONV_IGEMM;
+    int bn = 128;
+    int64_t best = (p.N + 127) / 128 * 128;
+    const int64_t c96 = (p.N + 95) / 96 * 96, c64 = (p.N + 63) / 64 * 64;
+    if (c96 < best) { best = c96; bn = 96; }
+    if (c64 < best) { best = c64; bn = 64; }
+    c.tiles = ((p.M + CBM - 1) / CBM) * ((p.N + bn - 1) / bn);
+    bn == 64 ? KERNEL_EPI(conv_igemm_kernel, 64, 4, 1) : bn == 96 ? KERNEL_EPI(conv_igemm_kernel, 96, 4, 1) : KERNEL_EPI(conv_igemm_kernel, 128, 2, 2);
+    return c;
+}
+#undef KERNEL
+#undef KERNEL_EPI
+
+static ConvChoice conv_choose_geom(const int32_t* geom, int64_t ldc, int64_t ldr, ConvForm form) {       // the queries: no pointers, so aligned ones
     ConvParams p;
     conv_params(p, geom);
-    if (fused_norm == 2) { // (residual sum +) the NEXT consumer's RMS_norm + SiLU (scail_conv3d_cl_resid_norm): one n tile of 96 channels; with a residual the
-                           // 3x3x3 kernels with tile continuation (scail_conv4c_e5 / e6), without one the kt = 1 kernel (scail_conv4u_e7)
-        if (!(g_conv4 && g_conv4_resnorm && g_conv4_suffix.empty() && p.N == 96 && ldc == 96 && p.ot_mul == 1 && p.ot_off == 0)) return 0;
-        if (ldr > 0) return (g_conv4_cont && conv4_eligible(p, ldc, ldr)) ? 4 : 0;
-        if (conv4u_eligible(p, ldc)) return 4;
-        // ... or, answer 2, the hipcc direct-gather kernel's dual-output form (the encoder's stem convolution): not a generated kernel, one launch all the same
-        return (g_conv_direct && !conv4_eligible(p, ldc, ldc) && !conv4n_eligible(p, ldc) && conv_direct_dual_eligible(p, ldc)) ? 2 : 0;
-    }
-    if (fused_norm)      // conv + RMS_norm + SiLU: the generated kernel where one n tile holds a voxel's 96 channels, no residual
-        return (g_conv4 && ldr == 0 && p.N == 96 && conv4_eligible(p, ldc, ldc)) ? 4 : 0;
-    return (g_conv4 && (conv4_eligible(p, ldc, ldr > 0 ? ldr : ldc) || (ldr == 0 && (conv4u_eligible(p, ldc) || conv4n_eligible(p, ldc))))) ? 4 : 0;
+    return conv_choose(p, ldc, ldr, ldr > 0, form, true);
 }
 
-// next_gamma / y_norm (scail_conv3d_cl_resid_norm, generated kernels only -- the caller checked scail_conv3d_kernel_for(.., 2)): the residual sum
+extern "C" int scail_conv3d_kernel_for(const int32_t* geom, int64_t ldc, int64_t ldr, int fused_norm) {
+    if (geom == nullptr) return 0;
+    const ConvChoice c = conv_choose_geom(geom, ldc, ldr, fused_norm == 2 ? CONV_NEXT_NORM : fused_norm ? CONV_NORM : CONV_PLAIN);
+    return !c.covers ? 0 : c.family <= CONV_GEN_NARROW ? 4 : (fused_norm == 2 && c.family == CONV_DIRECT) ? 2 : 0;
+}
+
+// ResidualBlock's residual.2 -> residual.3 -> residual.4: conv -> RMS_norm -> SiLU in one kernel (the raw conv output never goes to HBM) on the
+// generated kernel's norm epilogue where it applies (N = 96: scail_conv4f_e4), else on the hipcc halo kernel's -- except where the plain generated
+// kernel runs but its norm epilogue does not: there conv + a separate rms_silu pass beats the fused hipcc kernel (13.9 + 2.8 vs 21.0 ms on the
+// 96-channel full-resolution shape, round 3; profiles/r03_vae_kernel_stats.md).
+extern "C" int scail_conv3d_norm_fused_for(const int32_t* geom, int64_t ldc) {
+    if (geom == nullptr) return 0;
+    const ConvChoice c = conv_choose_geom(geom, ldc, 0, CONV_NORM);
+    return c.covers && (c.family == CONV_GEN || conv_choose_geom(geom, ldc, 0, CONV_PLAIN).family > CONV_GEN_NARROW);
+}
+
+extern "C" int scail_conv3d_kernel_name_for(const int32_t* geom, int64_t ldc, int64_t ldr, int form, char* buf, int64_t len) {
+    SCAIL_REQUIRE(geom != nullptr && buf != nullptr, "null argument");
+    SCAIL_REQUIRE(form >= CONV_PLAIN && form <= CONV_NEXT_NORM_ONLY, "form: 0 plain, 1 conv + norm, 2 next-norm with the raw output, 3 without it");
+    const ConvChoice c = conv_choose_geom(geom, ldc, ldr, (ConvForm)form);
+    const std::string name = (!c.covers && form == CONV_NORM) ? "rejected" : c.name + (c.nsplit > 1 ? " x 2" : "") + (c.covers ? "" : " + scail_rms_silu");
+    SCAIL_REQUIRE((int64_t)name.size() < len, "buffer too small");
+    std::memcpy(buf, name.c_str(), name.size() + 1);
+    return 0;
+}
+
+// next_gamma / y_norm (scail_conv3d_cl_resid_norm, where conv_choose says one launch covers the call): the residual sum
 // goes to y (nullptr: nowhere) and SiLU(RMS_norm(bf16(sum)) * next_gamma) to y_norm
 static int conv3d_impl(const scail_bf16* x, const scail_bf16* w, const float* bias, scail_bf16* y, int64_t ldc,
                        const scail_bf16* resid, int64_t ldr, const float* gamma, const int32_t* geom, void* stream,
@@ -1198,235 +1353,59 @@ static int conv3d_impl(const scail_bf16* x, const scail_bf16* w, const float* bi
     SCAIL_REQUIRE(p.Cin % 8 == 0, "Cin must be a multiple of 8 (pad the channels)");
     SCAIL_REQUIRE(p.N % 8 == 0 && p.Kpad % CBK == 0 && p.Kpad >= p.Ktrue, "N % 8 == 0, Kpad % 64 == 0, Kpad >= taps*Cin");
     SCAIL_REQUIRE(ldc % 4 == 0 && (resid == nullptr || ldr % 4 == 0), "output / residual row strides must be multiples of 4");
-    const bool rn = next_gamma != nullptr;
+    const bool rn = next_gamma != nullptr, fuse = gamma != nullptr;
+    const ConvForm form = fuse ? CONV_NORM : !rn ? CONV_PLAIN : y != nullptr ? CONV_NEXT_NORM : CONV_NEXT_NORM_ONLY;
     if (rn && y == nullptr) { y = y_norm; p.y = y_norm; }      // norm-only form: the one output IS the normalised tensor
     SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0 &&
                       (reinterpret_cast<uintptr_t>(y) & 7) == 0 && (reinterpret_cast<uintptr_t>(bias) & 15) == 0,
                   "pointer alignment");
     if (p.M == 0) return 0;
-    // 3x3x3 stride-1 causal convolutions: halo-tile kernel.  Knob conv_halo: 0 off, 1 = 48-channel slices / 1 workgroup
-    // per CU, 4 (default) = 3 with TWO output frames per workgroup (4-frame patch, every W fragment used for both frames:
-    // +22-25 % on the 96 / 192 / 384-channel shapes, bit-identical), 3 = 32-channel slices, one padded W buffer (two
-    // barriers per tap row), 2 workgroups per CU,
-    // 2 = 32-channel slices, swizzled unpadded layout with two W buffers (one barrier per tap row), 2 workgroups per CU --
-    // measured equal (283 / 490 ms vs 281 / 487 ms encode / decode): the barrier is not what bounds the kernel
-    const bool fuse = gamma != nullptr;       // conv + RMS_norm + SiLU: always the halo kernel, whatever the knob says
-    const bool k1 = g_conv4 && !fuse && resid == nullptr && conv4u_eligible(p, ldc) && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-    const bool nar = g_conv4 && !fuse && resid == nullptr && conv4n_eligible(p, ldc) && (reinterpret_cast<uintptr_t>(y) & 15) == 0;   // (8-byte stores)
-    // conv -> RMS_norm -> SiLU (scail_conv3d_cl_norm) on the generated kernel: one n tile of 96 channels; gamma travels in the residual argument
-    const bool fnorm = g_conv4 && fuse && resid == nullptr && p.N == 96 && conv4_eligible(p, ldc, ldc) && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-                       (reinterpret_cast<uintptr_t>(gamma) & 15) == 0;
-    if (k1 || nar || fnorm || (g_conv4 && !fuse && conv4_eligible(p, ldc, resid ? ldr : ldc) && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-               (reinterpret_cast<uintptr_t>(resid) & 15) == 0)) {      // (16-byte row chunks; the arena's tensors always are)
+    auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+    const bool aligned = ((addr(y) | addr(resid) | addr(gamma) | addr(y_norm) | addr(next_gamma)) & 15) == 0;
+    const ConvChoice c = conv_choose(p, ldc, ldr, resid != nullptr, form, aligned);
+    SCAIL_REQUIRE(c.covers || !fuse, "conv + norm fusion covers the 3x3x3 stride-1 convolutions with Cin % 32 == 0 and N <= 96 only");
+    SCAIL_REQUIRE(c.covers, "conv3d: the dual-output form was requested for a shape no dual-output kernel covers (conv_choose decides)");
+    SCAIL_REQUIRE(c.tiles < (1ll << 31), "too many tiles");
+    if (fuse && c.family == CONV_HALO) SCAIL_REQUIRE(resid == nullptr && (addr(gamma) & 15) == 0, "conv + norm fusion needs N <= 96, no residual, 16-byte aligned gamma");
+    const char* what = fuse ? "conv3d_cl_norm" : rn ? "conv3d_cl_resid_norm" : "conv3d_cl";
+    if (c.family <= CONV_GEN_NARROW) {
         Conv4Args a;
-        a.x = x; a.w = w; a.bias = bias; a.y = y; a.resid = fnorm ? static_cast<const void*>(gamma) : static_cast<const void*>(resid);
+        a.x = x; a.w = w; a.bias = bias; a.y = y; a.resid = fuse ? static_cast<const void*>(gamma) : static_cast<const void*>(resid);
         // (kt = 1 kernels: H, W are the OUTPUT extent, the `pt` argument carries the upsample shift -- there are no padding frames)
-        a.Ti = p.Ti; a.To = p.To; a.H = p.Ho; a.W = p.Wo; a.Cin = p.Cin; a.N = p.N; a.Kpad = p.Kpad; a.pt = k1 ? (p.ups ? 1 : 0) : p.pt;
+        a.Ti = p.Ti; a.To = p.To; a.H = p.Ho; a.W = p.Wo; a.Cin = p.Cin; a.N = p.N; a.Kpad = p.Kpad; a.pt = c.family == CONV_GEN_K1 ? (p.ups ? 1 : 0) : p.pt;
         a.tiles_t = (p.To + 1) / 2; a.tiles_w = (p.Wo + 15) / 16; a.tiles_n = std::max(p.N / 96, 1);
         auto magic31 = [](int d) { return (uint32_t)(((1ull << 31) + (uint64_t)d - 1) / (uint64_t)d); };
         a.magic_n = magic31(a.tiles_n); a.magic_w = magic31(a.tiles_w); a.magic_t = magic31(a.tiles_t);
         a.n_slices = p.Cin / 32; a.ot_mul = p.ot_mul; a.ot_off = p.ot_off; a.ldc = ldc; a.ldr = resid ? ldr : ldc;
-        const int64_t tiles = conv4_tiles(p);        // conv4_eligible: tiles x the largest divisor < 2^31, so the magic-number divisions are exact
         // persistent workgroups, one per compute unit; tiles are numbered n tile fastest, then frame pair; workgroup number w = (b % 8) *
         // wgs_per_xcd + b / 8.  One n tile: w takes the next tiles_per_wg (+ 1) tiles (the frame pairs of a spatial tile; consecutive pairs
         // share two input frames, the lane offsets stay).  Several n tiles (tiles_per_wg = 0): w takes tiles w, w + grid, ... so that an XCD
         // works on the n tiles of a few neighbouring frame pairs at a time and they share the patch through its L2.
         const int cus = scail_device_cus();
         if (cus <= 0) return 2;
-        a.wgs_per_xcd = (int32_t)std::min<int64_t>((tiles + 7) / 8, cus / 8);
-        a.tiles_per_wg = a.tiles_n == 1 ? (int32_t)(tiles / (8 * a.wgs_per_xcd)) : 0;
-        a.tiles = (int32_t)tiles;
+        a.wgs_per_xcd = (int32_t)std::min<int64_t>((c.tiles + 7) / 8, cus / 8);
+        a.tiles_per_wg = a.tiles_n == 1 ? (int32_t)(c.tiles / (8 * a.wgs_per_xcd)) : 0;
+        a.tiles = (int32_t)c.tiles;
         a.gamma = next_gamma;
         a.y2_delta = (rn && y != y_norm) ? (int64_t)(reinterpret_cast<const char*>(y_norm) - reinterpret_cast<const char*>(y)) : 0;
         hipFunction_t fn;
-        // (measurement build: the "_prof" variant is an e0 kernel that writes its phase timers through the residual pointer)
-        const bool prof = g_conv4_suffix.find("prof") != std::string::npos;
-        const bool cont = g_conv4_cont && !k1 && !nar && a.tiles_n == 1 && g_conv4_suffix.empty();      // one n tile: runs of frame pairs per workgroup (a measurement-build kernel variant takes precedence)
-        const std::string name = rn ? (k1 ? "scail_conv4u_e7" : y != y_norm ? "scail_conv4c_e5" : "scail_conv4c_e6")
-                                 : k1 ? "scail_conv4u_e0" : nar ? (g_conv4_cont && g_conv4_suffix.empty() ? "scail_conv4cn_e0" : "scail_conv4n_e0")
-                                 : fnorm ? (cont ? "scail_conv4c_e4" : "scail_conv4f_e4")
-                                 : cont ? (resid ? "scail_conv4c_e3" : "scail_conv4c_e0")
-                                 : std::string(resid && !prof ? "scail_conv4_e3" : "scail_conv4_e0") + g_conv4_suffix;
-        // conv4.s holds scail_conv4_e0 / e3 and their measurement-build variants, conv4u.s every other generated convolution
-        if (int rc = scail_module_function("conv4", name.rfind("scail_conv4_", 0) == 0 ? k_conv4_hsaco : k_conv4u_hsaco, name, &fn)) return rc;
+        if (int rc = scail_module_function("conv4", c.in_conv4 ? k_conv4_hsaco : k_conv4u_hsaco, c.name, &fn)) return rc;
         return scail_module_launch("conv4", fn, (unsigned)a.wgs_per_xcd * 8u, 256, a, stream);
     }
-    if (!rn && (g_conv_halo || fuse) && p.kt == 3 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && !p.ups &&
-        p.ph == 1 && p.pw == 1 && p.Ho == p.Hi && p.Wo == p.Wi &&
-        p.Cin % ((g_conv_halo == 1 && p.N > 32 && !fuse) ? 48 : 32) == 0 && (fuse || p.N <= 32 || p.N >= 48)) {
-#define HALO_LAUNCH(EPI_, CS_, NWB_, SWZ_, BN_, ...)                                                                        \
-    {                                                                                                              \
-        constexpr int lds_ = HaloCfg<CS_, NWB_, SWZ_, BN_, ##__VA_ARGS__>::LDS;                                             \
-        static ScailDeviceOnce attr_;                                                                                 \
-        if (attr_.need()) {                                                                                              \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<EPI_, CS_, NWB_, SWZ_, BN_, ##__VA_ARGS__>), \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds_) != hipSuccess) {             \
-                scail_set_error("conv3d: hipFuncSetAttribute failed");                                             \
-                return 2;                                                                                          \
-            }                                                                                                      \
-            attr_.done();                                                                                          \
-        }                                                                                                          \
-        hipLaunchKernelGGL((conv_halo_kernel<EPI_, CS_, NWB_, SWZ_, BN_, ##__VA_ARGS__>), dim3((unsigned)tiles), dim3(256), lds_, (hipStream_t)stream, p); \
+    if (c.family != CONV_DIRECT) return c.launch(what, p, (unsigned)c.tiles, c, stream);
+    const int cus = scail_device_cus();
+    if (cus <= 0) return 2;
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((p.M + 255) / 256, cus));
+    for (int part = 0, nn = p.N / c.nsplit; part < c.nsplit; ++part) {
+        ConvParams q = p;
+        q.N = nn;
+        q.w = p.w + (int64_t)part * nn * p.Kpad;
+        q.bias = p.bias ? p.bias + part * nn : nullptr;
+        q.y = p.y + part * nn;
+        if (rn) { q.gamma = next_gamma; q.y2 = y_norm; }       // dual-output form: the raw output + the consumer's normalised input
+        if (int rc = c.launch(what, q, grid, c, stream)) return rc;
     }
-        const int hbn = p.N <= 32 ? 32 : 96;
-        const int nf = ((g_conv_halo == 4 || g_conv_halo == 5 || fuse) && hbn == 96 && p.To >= 2) ? 2 : 1;   // output frames per workgroup (an odd last frame pair wastes half a tile: 1 / 81)
-        if (fuse) {                                                        // fused RMS_norm + SiLU epilogue: one N tile
-            SCAIL_REQUIRE(p.N <= 96 && resid == nullptr && (reinterpret_cast<uintptr_t>(gamma) & 15) == 0,
-                          "conv + norm fusion needs N <= 96, no residual, 16-byte aligned gamma");
-            const int64_t tiles = (int64_t)((p.To + nf - 1) / nf) * ((p.Ho + HT_TH - 1) / HT_TH) * ((p.Wo + HT_TW - 1) / HT_TW);
-            SCAIL_REQUIRE(tiles < (1ll << 31), "too many tiles");
-            if (hbn == 32) HALO_LAUNCH(4, 32, 1, false, 32) else if (nf == 2) HALO_LAUNCH(4, 32, 1, false, 96, 2) else HALO_LAUNCH(4, 32, 1, false, 96)
-            return scail_check_launch("conv3d_cl_norm");
-        }
-        const int64_t tiles = (int64_t)((p.To + nf - 1) / nf) * ((p.Ho + HT_TH - 1) / HT_TH) * ((p.Wo + HT_TW - 1) / HT_TW) * ((p.N + hbn - 1) / hbn);
-        SCAIL_REQUIRE(tiles < (1ll << 31), "too many tiles");
-        if (hbn == 32) {
-            if (resid != nullptr) HALO_LAUNCH(3, 32, 1, false, 32) else HALO_LAUNCH(0, 32, 1, false, 32)
-#ifdef SCAIL_ABLATIONS
-        } else if (nf == 2 && g_conv_halo == 5) {                          // fragment prefetch one tap ahead (A/B)
-            if (resid != nullptr) HALO_LAUNCH(3, 32, 1, false, 96, 2, 3, false, 1) else HALO_LAUNCH(0, 32, 1, false, 96, 2, 3, false, 1)
-#endif
-        } else if (nf == 2) {
-            if (resid != nullptr) HALO_LAUNCH(3, 32, 1, false, 96, 2) else HALO_LAUNCH(0, 32, 1, false, 96, 2)
-#ifdef SCAIL_ABLATIONS
-        } else if (g_conv_halo == 1) {
-            if (resid != nullptr) HALO_LAUNCH(3, 48, 2, false, 96) else HALO_LAUNCH(0, 48, 2, false, 96)
-        } else if (g_conv_halo == 2) {
-            if (resid != nullptr) HALO_LAUNCH(3, 32, 2, true, 96) else HALO_LAUNCH(0, 32, 2, true, 96)
-#endif
-        } else {
-            if (resid != nullptr) HALO_LAUNCH(3, 32, 1, false, 96) else HALO_LAUNCH(0, 32, 1, false, 96)
-        }
-        return scail_check_launch("conv3d_cl");
-    }
-    SCAIL_REQUIRE(gamma == nullptr, "conv + norm fusion covers the 3x3x3 stride-1 convolutions with Cin % 32 == 0 and N <= 96 only");
-    // the 1x3x3 convolution behind the nearest 2x upsample (Resample 'upsample2d/3d', wan_vae.py:110-121): halo tile with
-    // the upsampling folded into the patch load, two output frames per workgroup
-    if (g_conv_halo == 4 && p.kt == 1 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 1 && p.sw == 1 && p.ups &&
-        p.pt == 0 && p.ph == 1 && p.pw == 1 && p.Ho == 2 * p.Hi && p.Wo == 2 * p.Wi && p.To == p.Ti && p.To >= 2 &&
-        p.Cin % 32 == 0 && p.N >= 48) {
-        const int64_t tiles = (int64_t)((p.To + 1) / 2) * ((p.Ho + HT_TH - 1) / HT_TH) * ((p.Wo + HT_TW - 1) / HT_TW) * ((p.N + 95) / 96);
-        SCAIL_REQUIRE(tiles < (1ll << 31), "too many tiles");
-        if (resid != nullptr) HALO_LAUNCH(3, 32, 1, false, 96, 2, 1, true) else HALO_LAUNCH(0, 32, 1, false, 96, 2, 1, true)
-        return scail_check_launch("conv3d_cl");
-    }
-    // Resample's spatial downsampling: 1 x 3 x 3, stride (1, 2, 2), zero padding behind the last row / column only (conv_s2_kernel)
-    if (g_conv_s2 && !rn && resid == nullptr && p.kt == 1 && p.kh == 3 && p.kw == 3 && p.st == 1 && p.sh == 2 && p.sw == 2 && !p.ups &&
-        p.pt == 0 && p.ph == 0 && p.pw == 0 && p.To == p.Ti && p.Cin % S2_CS == 0 && p.N % 96 == 0 &&
-        2 * (int64_t)p.Hi * p.Wi * p.Cin < (1ll << 31) && (int64_t)p.N * p.Kpad < (1ll << 31)) {
-        const int nf = (g_conv_s2 == 2 && p.To >= 2) ? 2 : 1;
-        const int64_t vtiles = (int64_t)((p.To + nf - 1) / nf) * ((p.Ho + S2_TH - 1) / S2_TH) * ((p.Wo + S2_TW - 1) / S2_TW);
-        const int64_t grid = (vtiles + 7) / 8 * 8 * (p.N / 96);
-        SCAIL_REQUIRE(grid < (1ll << 31), "too many tiles");
-#define S2_LAUNCH(NF_)                                                                                                              \
-    {                                                                                                                               \
-        static ScailDeviceOnce attr_;                                                                                               \
-        if (attr_.need()) {                                                                                                         \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_s2_kernel<NF_>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    S2Cfg<NF_>::LDS) != hipSuccess) {                                                               \
-                scail_set_error("conv3d: hipFuncSetAttribute failed");                                                              \
-                return 2;                                                                                                           \
-            }                                                                                                                       \
-            attr_.done();                                                                                                           \
-        }                                                                                                                           \
-        hipLaunchKernelGGL((conv_s2_kernel<NF_>), dim3((unsigned)grid), dim3(256), S2Cfg<NF_>::LDS, (hipStream_t)stream, p, (int)vtiles); \
-    }
-        if (nf == 2) S2_LAUNCH(2) else S2_LAUNCH(1)
-#undef S2_LAUNCH
-        return scail_check_launch("conv3d_cl");
-    }
-    // HBM-bound shapes: the direct-gather kernel (comment above conv_direct_kernel); N = 384 as two launches of 192 channels
-    {
-        const int ksteps = (p.Ktrue + 15) / 16;
-        const int nsplit = p.N == 384 ? 2 : 1, nn = p.N / nsplit, nb = nn / 32;
-        // (instantiated: up to 6 k-steps with 32 / 64 / 96 / 128 / 192 channels -- the 1x1x1 convolutions of up to 96 input channels --, up to
-        // 14 k-steps with 96 channels -- the stem; 14 x 192 and 20 x 96 were built and spill 46 / 22 registers: those shapes stay on the gather kernel)
-        const bool shape = ((ksteps <= 6 && (nb == 1 || nb == 2 || nb == 3 || nb == 4 || nb == 6)) || (ksteps <= 14 && nb == 3)) &&
-                           p.kt <= 30 && p.kh <= 31 && p.kw <= 31 && p.Cin < 65536 &&
-                           (int64_t)(p.kt + 1) * p.Hi * p.Wi * p.Cin < (1ll << 31);
-        const int wld = ksteps * 16 + 8;                              // padded W row: 16 consecutive rows start in distinct 16-byte bank groups
-        const int lds = (nn * wld + 8 * 32 * CD_STRIP_LD) * 2 + 2 * nn * 4;        // W, the waves' strips, bias + gamma
-        if (g_conv_direct && !p.ups && resid == nullptr && p.Cin % 8 == 0 && nn % 32 == 0 && shape && lds <= 150 * 1024 && ldc % 8 == 0 &&
-            (reinterpret_cast<uintptr_t>(y) & 15) == 0 && p.M >= 4096 && p.M < (1ll << 40) && p.Ho * (int64_t)p.Wo < (1ll << 31) && p.Ho * (int64_t)p.Wo >= 32) {
-            const int cus = scail_device_cus();
-            if (cus <= 0) return 2;
-            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((p.M + 255) / 256, cus));
-            if (rn) {       // raw output + the consumer's normalised input (scail_conv3d_cl_resid_norm checked conv_direct_dual_eligible)
-                SCAIL_REQUIRE(nb == 3 && nsplit == 1 && ksteps <= 14 && y != y_norm, "conv3d: dual-output direct kernel needs 96 channels, <= 14 k-steps");
-                ConvParams q = p;
-                q.gamma = next_gamma;
-                q.y2 = y_norm;
-                static ScailDeviceOnce attr_;
-                if (attr_.need()) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_direct_kernel<14, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) {
-                        scail_set_error("conv3d: hipFuncSetAttribute failed");
-                        return 2;
-                    }
-                    attr_.done();
-                }
-                hipLaunchKernelGGL((conv_direct_kernel<14, 3, true>), dim3(grid), dim3(CD_THREADS), lds, (hipStream_t)stream, q, wld);
-                return scail_check_launch("conv3d_cl_resid_norm");
-            }
-#define CD_LAUNCH(KS_, NB_)                                                                                                          \
-    {                                                                                                                                \
-        static ScailDeviceOnce attr_;                                                                                                   \
-        if (attr_.need()) {                                                                                                                \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_direct_kernel<KS_, NB_>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) { \
-                scail_set_error("conv3d: hipFuncSetAttribute failed");                                                               \
-                return 2;                                                                                                            \
-            }                                                                                                                        \
-            attr_.done();                                                                                                            \
-        }                                                                                                                            \
-        hipLaunchKernelGGL((conv_direct_kernel<KS_, NB_>), dim3(grid), dim3(CD_THREADS), lds, (hipStream_t)stream, q, wld);          \
-    }
-            for (int part = 0; part < nsplit; ++part) {
-                ConvParams q = p;
-                q.N = nn;
-                q.w = p.w + (int64_t)part * nn * p.Kpad;
-                q.bias = p.bias ? p.bias + part * nn : nullptr;
-                q.y = p.y + part * nn;
-                if (ksteps <= 6) {
-                    if (nb == 1) CD_LAUNCH(6, 1) else if (nb == 2) CD_LAUNCH(6, 2) else if (nb == 3) CD_LAUNCH(6, 3) else if (nb == 4) CD_LAUNCH(6, 4) else CD_LAUNCH(6, 6)
-                } else {
-                    CD_LAUNCH(14, 3)
-                }
-            }
-#undef CD_LAUNCH
-            return scail_check_launch("conv3d_cl");
-        }
-    }
-    SCAIL_REQUIRE(!rn, "conv3d: the dual-output form was requested for a shape no dual-output kernel covers (scail_conv3d_kernel_for(.., 2) decides)");
-    // N tile: of 128 / 96 / 64 the one with the fewest padding columns (ties -> the wider tile)
-    int bn = 128;
-    {
-        int64_t best = (p.N + 127) / 128 * 128;
-        const int64_t c96 = (p.N + 95) / 96 * 96, c64 = (p.N + 63) / 64 * 64;
-        if (c96 < best) { best = c96; bn = 96; }
-        if (c64 < best) { best = c64; bn = 64; }
-    }
-#define CONV_LAUNCH(EPI_, BN_, WM_, WN_)                                                                           \
-    {                                                                                                              \
-        constexpr int lds_ = 2 * (CBM + BN_) * CLDT * 2;                                                           \
-        static ScailDeviceOnce attr_;                                                                                 \
-        if (attr_.need()) {                                                                                              \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<EPI_, BN_, WM_, WN_>),        \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, lds_) != hipSuccess) {             \
-                scail_set_error("conv3d: hipFuncSetAttribute failed");                                             \
-                return 2;                                                                                          \
-            }                                                                                                      \
-            attr_.done();                                                                                          \
-        }                                                                                                          \
-        const int64_t tiles = ((p.M + CBM - 1) / CBM) * ((p.N + BN_ - 1) / BN_);                                   \
-        SCAIL_REQUIRE(tiles < (1ll << 31), "too many tiles");                                                      \
-        hipLaunchKernelGGL((conv_igemm_kernel<EPI_, BN_, WM_, WN_>), dim3((unsigned)tiles), dim3(CONV_THREADS), lds_, \
-                           (hipStream_t)stream, p);                                                                \
-    }
-    if (resid != nullptr) {
-        if (bn == 64) CONV_LAUNCH(3, 64, 4, 1) else if (bn == 96) CONV_LAUNCH(3, 96, 4, 1) else CONV_LAUNCH(3, 128, 2, 2)
-    } else {
-        if (bn == 64) CONV_LAUNCH(0, 64, 4, 1) else if (bn == 96) CONV_LAUNCH(0, 96, 4, 1) else CONV_LAUNCH(0, 128, 2, 2)
-    }
-    return scail_check_launch("conv3d_cl");
+    return 0;
 }
 
 extern "C" int scail_conv3d_cl(const scail_bf16* x, const scail_bf16* w, const float* bias, scail_bf16* y, int64_t ldc,
@@ -1453,7 +1432,7 @@ extern "C" int scail_conv3d_cl_resid_norm(const scail_bf16* x, const scail_bf16*
     SCAIL_REQUIRE(ldc == p.N && p.ot_mul == 1 && p.ot_off == 0, "scail_conv3d_cl_resid_norm needs dense outputs: ldc == N, ot_mul = 1, ot_off = 0");
     const bool aligned = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(y_norm) | reinterpret_cast<uintptr_t>(resid) |
                            reinterpret_cast<uintptr_t>(gamma)) & 15) == 0;
-    if (aligned && scail_conv3d_kernel_for(geom, ldc, ldr, 2) != 0)       // 4: a generated kernel, 2: the direct-gather kernel's dual-output form
+    if (conv_choose(p, ldc, ldr, resid != nullptr, y != nullptr ? CONV_NEXT_NORM : CONV_NEXT_NORM_ONLY, aligned).covers)      // a generated kernel, or the direct-gather kernel's dual-output form
         return conv3d_impl(x, w, bias, y, ldc, resid, ldr, nullptr, geom, stream, gamma, y_norm);
     // everything else: the two separate calls this entry point stands for
     scail_bf16* raw = y != nullptr ? y : y_norm;

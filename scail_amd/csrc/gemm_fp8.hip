@@ -213,18 +213,8 @@ __global__ __launch_bounds__(512) void scail_gemm_fp8_kernel(GemmFp8Params P) {
 template <int EPI>
 static int launch_gemm_fp8(const GemmFp8Params& P, hipStream_t stream) {
     constexpr int lds = 2 * (256 + 256) * F8_BK;   // 128 KB
-    static ScailDeviceOnce attr_set;
-    if (attr_set.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scail_gemm_fp8_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) {
-            scail_set_error(std::string("scail_gemm_fp8: hipFuncSetAttribute: ") + hipGetErrorString(e));
-            return 2;
-        }
-        attr_set.done();
-    }
     const int tiles = ((P.e.M + 255) / 256) * ((P.e.N + 255) / 256);
-    hipLaunchKernelGGL((scail_gemm_fp8_kernel<EPI>), dim3((unsigned)tiles), dim3(512), lds, stream, P);
-    return scail_check_launch("scail_gemm_fp8");
+    return scail_launch_lds<scail_gemm_fp8_kernel<EPI>>("scail_gemm_fp8", lds, dim3((unsigned)tiles), dim3(512), lds, stream, P);
 }
 
 extern "C" int scail_gemm_fp8(const uint8_t* x, int64_t lda, const float* sx, const uint8_t* w, const float* sw, const float* bias,

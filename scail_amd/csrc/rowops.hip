@@ -616,20 +616,9 @@ static int ln_wave_launch(const scail_bf16* x, int64_t ldx, scail_bf16* y, int64
                           int64_t rows_out, int64_t src_rows_per_batch, int64_t src_row_offset, int64_t rows, int64_t D, float eps, void* stream) {
     if (!g_row_wave || D % 512 != 0 || rows_out <= 0 || rows % rows_out != 0) return -1;
 #define LN_WAVE(CPL_)                                                                                                                  \
-    case CPL_: {                                                                                                                       \
-        constexpr int lds_ = 2 * 512 * CPL_ * 4;                                                                                       \
-        static ScailDeviceOnce attr_;                                                                                                     \
-        if (attr_.need()) {                                                                                                                  \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&ln_wave_kernel<MODE, CPL_>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_) != hipSuccess) { \
-                scail_set_error("ln_wave: hipFuncSetAttribute failed");                                                                \
-                return 2;                                                                                                              \
-            }                                                                                                                          \
-            attr_.done();                                                                                                              \
-        }                                                                                                                              \
-        hipLaunchKernelGGL((ln_wave_kernel<MODE, CPL_>), dim3((unsigned)(n_batch * wpb)), dim3(256), lds_, (hipStream_t)stream, x, ldx, y, ldy, \
-                           p0, p1, mod_stride, rows_out, src_rows_per_batch, src_row_offset, (int)wpb, eps);                           \
-        return scail_check_launch("ln_wave");                                                                                          \
-    }
+    case CPL_:                                                                                                                         \
+        return scail_launch_lds<ln_wave_kernel<MODE, CPL_>>("ln_wave", 2 * 512 * CPL_ * 4, dim3((unsigned)(n_batch * wpb)), dim3(256), 2 * 512 * CPL_ * 4, stream, \
+                                                            x, ldx, y, ldy, p0, p1, mod_stride, rows_out, src_rows_per_batch, src_row_offset, (int)wpb, eps);
     // persistent workgroups: about three per compute unit (157 VGPRs, 40 KB of LDS), dealt evenly to the batch elements
     const int64_t n_batch = rows / rows_out;
     const int cus = scail_device_cus();
@@ -1071,17 +1060,10 @@ extern "C" int scail_attn_small(const scail_bf16* q, const scail_bf16* k, const 
     const size_t lds = (size_t)Lk * (head_dim + 8) * 2 + (size_t)Lk * head_dim * 2 + 4 * Lk * 4 + 4 * head_dim * 4;
     SCAIL_REQUIRE(lds <= 160 * 1024, "K and V of one head must fit in LDS (Lk * head_dim too large for this kernel)");
     if (Lq == 0 || n_batch == 0) return 0;
-    static size_t lds_set = 0;
-    if (lds > lds_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { scail_set_error("attn_small: hipFuncSetAttribute failed"); return 2; }
-        lds_set = lds;
-    }
     dim3 grid((unsigned)((Lq + SA_ROWS - 1) / SA_ROWS), (unsigned)heads, (unsigned)n_batch);
-    hipLaunchKernelGGL(attn_small_kernel, grid, dim3(256), lds, (hipStream_t)stream, q, k, v, o, strides[0], strides[1], strides[2],
-                       strides[3], strides[4], strides[5], strides[6], strides[7], (int)Lq, (int)Lk, (int)head_dim, scale, bucket, bias_tab,
-                       (int)heads, key_mask, key_mask_bs);
-    return scail_check_launch("attn_small");
+    return scail_launch_lds<attn_small_kernel>("attn_small", 160 * 1024, grid, dim3(256), lds, stream, q, k, v, o, strides[0], strides[1], strides[2],       // (opt-in: the bound above)
+                                               strides[3], strides[4], strides[5], strides[6], strides[7], (int)Lq, (int)Lk, (int)head_dim, scale, bucket, bias_tab,
+                                               (int)heads, key_mask, key_mask_bs);
 }
 
 extern "C" int scail_mul_bf16(const scail_bf16* a, const scail_bf16* b, scail_bf16* y, int64_t n, void* stream) {

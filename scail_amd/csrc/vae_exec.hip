@@ -165,12 +165,8 @@ int res_block(Arena& a, const scail_vae_res& r, Tens& x, Tens* xn = nullptr, con
     VAE_TRY(causal_begin(a, y, r.conv2.kt, c2));
     int32_t geom[21] = {(int32_t)c2.in.T, (int32_t)y.H, (int32_t)y.W, (int32_t)y.C, (int32_t)x.T, (int32_t)x.H, (int32_t)x.W,
                         3, 3, 3, 1, 1, 1, r.conv2.kt == 3 ? c2.pt : 2, 1, 1, 0, 1, 0, r.conv2.N, r.conv2.Kpad};
-    if (r.conv2.kt == 3 && r.conv2.kh == 3 && r.conv2.kw == 3 && y.C % 32 == 0 && r.conv2.N <= 96 &&
-        (scail_conv3d_kernel_for(geom, r.conv2.N, 0, 1) == 4 || scail_conv3d_kernel_for(geom, r.conv2.N, 0, 0) != 4)) {
-        // conv -> RMS_norm -> SiLU in one kernel: the raw conv output never goes to HBM (same rule as ops.conv_norm_fusable): the generated
-        // kernel's norm epilogue where it applies (N = 96: scail_conv4f_e4), else the hipcc halo kernel's -- except where the plain generated
-        // kernel runs but its norm epilogue does not: there conv + a separate rms_silu pass beats the fused hipcc kernel (13.9 + 2.8 vs 21.0 ms
-        // on the 96-channel full-resolution shape, round 3).
+    if (r.conv2.kt == 3 && r.conv2.kh == 3 && r.conv2.kw == 3 && scail_conv3d_norm_fused_for(geom, r.conv2.N)) {
+        // conv -> RMS_norm -> SiLU in one kernel: the raw conv output never goes to HBM (the rule, with its measured reason, is csrc/conv.hip's)
         y2 = a.get(x.T, x.H, x.W, r.conv2.N); VAE_CHK(a)
         VAE_TRY(scail_conv3d_cl_norm(c2.in.p, r.conv2.w, r.conv2.b, y2.p, y2.C, r.gamma3, geom, a.stream));
         VAE_TRY(causal_end(a, c2));

@@ -499,30 +499,36 @@ def conv3d_cl(x, wp, out_shape, stride=(1, 1, 1), pad=None, ups=False, out=None,
     return out
 
 
+def _causal_geom(wp, x_shape):
+    import ctypes as C
+    T, H, W, Cin = x_shape
+    kt, kh, kw = wp["k"]
+    return C.cast((C.c_int32 * 21)(T, H, W, Cin, T, H, W, kt, kh, kw, 1, 1, 1, kt - 1, kh // 2, kw // 2, 0, 1, 0, wp["N"], wp["Kpad"]), C.c_void_p)
+
+
+def conv_norm_fused(wp, x_shape) -> bool:
+    """Whether a ResidualBlock runs conv -> RMS_norm -> SiLU of an activation of shape (T, H, W, Cin) as ONE conv3d_cl_norm call, or as
+    conv3d_cl + rms_silu (scail_conv3d_norm_fused_for: the rule csrc/vae_exec.hip and the layer path of wan_vae.py share)."""
+    return L.load().scail_conv3d_norm_fused_for(_causal_geom(wp, x_shape), wp["N"]) == 1
+
+
 def conv_norm_fusable(wp, x_channels: int) -> bool:
-    """Whether conv3d_cl_norm covers this convolution (3x3x3, Cin % 32 == 0, at most 96 output channels)."""
-    return tuple(wp["k"]) == (3, 3, 3) and x_channels % 32 == 0 and wp["N"] <= 96
+    """Whether conv3d_cl_norm covers this causal 'same' convolution (3x3x3, Cin % 32 == 0, at most 96 output channels), by the library's own word."""
+    import ctypes as C
+    buf = C.create_string_buffer(128)
+    L.call("scail_conv3d_kernel_name_for", _causal_geom(wp, (2, 16, 16, x_channels)), wp["N"], 0, 1, buf, len(buf))
+    return buf.value != b"rejected"
 
 
 def conv_norm_generated(wp, x_shape) -> bool:
     """Whether conv3d_cl_norm of an activation of shape (T, H, W, Cin) runs the generated kernel's norm epilogue (scail_conv4f_e4: 96 output
     channels; scail_conv3d_kernel_for(..., fused_norm = 1) == 4)."""
-    import ctypes as C
-    T, H, W, Cin = x_shape
-    kt, kh, kw = wp["k"]
-    geom = (C.c_int32 * 21)(T, H, W, Cin, T, H, W, kt, kh, kw, 1, 1, 1, kt - 1, kh // 2, kw // 2, 0, 1, 0, wp["N"], wp["Kpad"])
-    return L.load().scail_conv3d_kernel_for(C.cast(geom, C.c_void_p), wp["N"], 0, 1) == 4
+    return L.load().scail_conv3d_kernel_for(_causal_geom(wp, x_shape), wp["N"], 0, 1) == 4
 
 
 def conv_generated(wp, x_shape) -> bool:
-    """Whether the causal 'same' conv3d_cl of an activation of shape (T, H, W, Cin) runs the generated kernels (scail_conv3d_kernel_for == 4).
-    The VAE then prefers conv3d_cl + rms_silu over the fused conv3d_cl_norm of the hipcc halo kernel: 13.9 + 2.8 ms against 21.0 ms on the
-    96-channel full-resolution shape (profiles/r03_vae_kernel_stats.md)."""
-    import ctypes as C
-    T, H, W, Cin = x_shape
-    kt, kh, kw = wp["k"]
-    geom = (C.c_int32 * 21)(T, H, W, Cin, T, H, W, kt, kh, kw, 1, 1, 1, kt - 1, kh // 2, kw // 2, 0, 1, 0, wp["N"], wp["Kpad"])
-    return L.load().scail_conv3d_kernel_for(C.cast(geom, C.c_void_p), wp["N"], 0, 0) == 4
+    """Whether the causal 'same' conv3d_cl of an activation of shape (T, H, W, Cin) runs the generated kernels (scail_conv3d_kernel_for == 4)."""
+    return L.load().scail_conv3d_kernel_for(_causal_geom(wp, x_shape), wp["N"], 0, 0) == 4
 
 
 def conv3d_cl_norm(x, wp, gamma, out=None):

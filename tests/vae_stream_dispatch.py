@@ -4,52 +4,24 @@ from the same inputs as the whole-sequence decode; the two are bit-identical onl
 geometry as for the clip's.  tests/test_vae_stream_gpu.py asserts that precondition with this walk before it compares bits, so that a
 mismatch reads as a dispatch difference and not as wrong arithmetic.
 
-The generated kernels are asked for through the library's own host-only query (scail_conv3d_kernel_for, scail_gemm_kernel_for); the order
-and thresholds of the hipcc kernels behind them are restated from conv3d_impl: the halo-tile kernel (3x3x3, Cin % 32 == 0, N <= 32 or
-N >= 48; two frames per workgroup where the tile is 96 channels wide and To >= 2), the halo kernel behind the 2x upsample (To >= 2), the
-direct-gather kernel (no residual, up to 6 k-steps of 16 with 32 / 64 / 96 / 128 / 192 channels or up to 14 with 96, M >= 4096 and
-Ho * Wo >= 32) and the implicit-GEMM kernel for everything else.  Needs no GPU."""
+Every convolution's kernel is the library's own word: scail_conv3d_kernel_name_for names the kernel csrc/conv.hip picks (conv_choose, the
+rule its launches follow), scail_conv3d_norm_fused_for says how a ResidualBlock runs residual.2.  No threshold, shape table or kernel order of
+the convolutions is restated here (the GEMM's still is, in _gemm).  Needs no GPU."""
 import ctypes as C
 
 
-def _kernel_for(lib, geom, ldc, ldr, mode):
-    return lib.scail_conv3d_kernel_for(C.cast((C.c_int32 * 21)(*geom), C.c_void_p), ldc, ldr, mode)
-
-
 def _conv(lib, Cin, N, k, Ti, To, H, W, pt, resid=False, ups=False, fuse=None, ot_mul=1, ot_off=0):
-    """the kernel of one convolution launch; fuse: None plain, "norm" scail_conv3d_cl_norm's rule, "dual" scail_conv3d_cl_resid_norm's"""
+    """the kernel of one convolution launch; fuse: None plain, "norm" residual.2 of a ResidualBlock, "dual" scail_conv3d_cl_resid_norm"""
+    from scail_amd import lib as L
     kt, kh, kw = k
     Cin, N = (Cin + 7) // 8 * 8, (N + 7) // 8 * 8
     Ho, Wo = (2 * H, 2 * W) if ups else (H, W)
     kpad = (kt * kh * kw * Cin + 63) // 64 * 64
-    geom = (Ti, H, W, Cin, To, Ho, Wo, kt, kh, kw, 1, 1, 1, pt, kh // 2, kw // 2, int(ups), ot_mul, ot_off, N, kpad)
-    ldr = N if resid else 0
-    M = To * Ho * Wo
-    k0, k1, k2 = (_kernel_for(lib, geom, N, ldr, m) for m in (0, 1, 2))
-    halo = k == (3, 3, 3) and Cin % 32 == 0 and (N <= 32 or N >= 48) and not ups
-    nf = 2 if (N > 32 and To >= 2) else 1
-    if fuse == "dual" and k2 != 0:
-        return ("generated dual", k2)
-    if fuse == "norm":
-        if not (k == (3, 3, 3) and Cin % 32 == 0 and N <= 96 and (k1 == 4 or k0 != 4)):
-            fuse = None                     # res_block: conv + a separate rms_silu pass
-        elif k1 == 4:
-            return ("generated norm",)
-        else:
-            return ("halo norm", nf)
-    if k0 == 4:
-        return ("generated",)
-    if halo:
-        return ("halo", nf)
-    if k == (1, 3, 3) and ups and To >= 2 and Cin % 32 == 0 and N >= 48:
-        return ("halo ups",)
-    ksteps = (kt * kh * kw * Cin + 15) // 16
-    nn = N // 2 if N == 384 else N
-    nb = nn // 32
-    shape = (ksteps <= 6 and nb in (1, 2, 3, 4, 6)) or (ksteps <= 14 and nb == 3)
-    if not ups and not resid and nn % 32 == 0 and shape and M >= 4096 and Ho * Wo >= 32:
-        return ("direct",)
-    return ("igemm",)
+    geom = C.cast((C.c_int32 * 21)(Ti, H, W, Cin, To, Ho, Wo, kt, kh, kw, 1, 1, 1, pt, kh // 2, kw // 2, int(ups), ot_mul, ot_off, N, kpad), C.c_void_p)
+    form = 2 if fuse == "dual" else 1 if fuse == "norm" and lib.scail_conv3d_norm_fused_for(geom, N) else 0
+    buf = C.create_string_buffer(128)
+    L.call("scail_conv3d_kernel_name_for", geom, N, N if resid else 0, form, buf, len(buf))
+    return buf.value.decode()
 
 
 def _gemm(lib, M, N, K, resid=False):
