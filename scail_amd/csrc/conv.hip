@@ -1434,7 +1434,8 @@ extern "C" int scail_conv3d_cl_resid_norm(const scail_bf16* x, const scail_bf16*
                            reinterpret_cast<uintptr_t>(gamma)) & 15) == 0;
     if (conv_choose(p, ldc, ldr, resid != nullptr, y != nullptr ? CONV_NEXT_NORM : CONV_NEXT_NORM_ONLY, aligned).covers)      // a generated kernel, or the direct-gather kernel's dual-output form
         return conv3d_impl(x, w, bias, y, ldc, resid, ldr, nullptr, geom, stream, gamma, y_norm);
-    // everything else: the two separate calls this entry point stands for
+    // everything else: the two separate calls this entry point stands for; what the second one requires is checked before the first is launched
+    SCAIL_REQUIRE(p.N % 8 == 0 && p.N <= 512, "scail_conv3d_cl_resid_norm as two calls: the norm pass needs N % 8 == 0, N <= 512 (scail_rms_silu)");
     scail_bf16* raw = y != nullptr ? y : y_norm;
     if (int rc = conv3d_impl(x, w, bias, raw, ldc, resid, ldr, nullptr, geom, stream)) return rc;
     return scail_rms_silu(raw, y_norm, gamma, p.M, p.N, 1, stream);
