@@ -18,6 +18,7 @@
 #include "gemm_epi.h"
 #include <atomic>
 #include <algorithm>
+#include <cstring>
 #include <map>
 #include <tuple>
 #include <mutex>
@@ -425,49 +426,6 @@ static int launch_gemm_q8(const GemmParams& p, hipStream_t stream) {
     return scail_launch_lds<gemm_bf16_q8_kernel<EPI, ABL>>("gemm_bf16", lds, dim3((unsigned)tiles), dim3(512), lds, stream, p);
 }
 
-template <int EPI>
-static int launch_gemm(const GemmParams& p, hipStream_t stream) {
-#ifdef SCAIL_ABLATIONS
-    // forced tiles / schedules and timing ablations of the measurement build (scail_gemm_tune)
-    if (g_gemm_tile == 261) return launch_gemm_q8<EPI>(p, stream);
-    if (g_gemm_tile == 266) return launch_gemm_t<256, 256, 2, 2, EPI, true>(p, stream);   // 4 waves, 128 x 128 per wave (AGPR accumulators)
-    if (EPI == 0 && g_gemm_tile == 1101) return launch_gemm_q8<0, 1>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1102) return launch_gemm_q8<0, 2>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1103) return launch_gemm_q8<0, 3>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1104) return launch_gemm_q8<0, 4>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1108) return launch_gemm_q8<0, 8>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1112) return launch_gemm_q8<0, 12>(p, stream);
-    if (g_gemm_tile == 262) return launch_gemm_q8<EPI, 32>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1300) return launch_gemm_q8<0, 128>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1301) return launch_gemm_q8<0, 129>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1302) return launch_gemm_q8<0, 130>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1303) return launch_gemm_q8<0, 131>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1364) return launch_gemm_q8<0, 192>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1256) return launch_gemm_q8<0, 256>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1512) return launch_gemm_q8<0, 512>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1164) return launch_gemm_q8<0, 64>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1116) return launch_gemm_q8<0, 16>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1124) return launch_gemm_q8<0, 24>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1001) return launch_gemm_t<256, 256, 2, 4, 0, true, 1>(p, stream);   // ablations
-    if (EPI == 0 && g_gemm_tile == 1002) return launch_gemm_t<256, 256, 2, 4, 0, true, 2>(p, stream);
-    if (g_gemm_tile == 260) return launch_gemm_t<256, 256, 2, 4, EPI, true, 4>(p, stream);   // DMA issue spread over the k-steps
-    if (EPI == 0 && g_gemm_tile == 1008) return launch_gemm_t<256, 256, 2, 4, EPI, true, 8>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1024) return launch_gemm_t<256, 256, 2, 4, EPI, true, 24>(p, stream);
-    if (EPI == 0 && g_gemm_tile == 1003) return launch_gemm_t<256, 256, 2, 4, 0, true, 3>(p, stream);
-    // measured at M = 97 664 (profiles/r01_pmc.md): 128 tile 820, 256 tile 1000, 256 + LDS-DMA 1090, 256 + DMA ring
-    // of half k-tiles with counted vmcnt 1025, ping-pong 1000, quadrant-phase q8 1240-1290 TFLOP/s (default for the
-    // big per-token GEMMs; the vendor library's assembly kernel reaches 1500 on the same shapes)
-    if (g_gemm_tile == 256) return launch_gemm_t<256, 256, 2, 4, EPI, false>(p, stream);
-    if (g_gemm_tile == 257) return launch_gemm_t<256, 256, 2, 4, EPI, true>(p, stream);
-    if (g_gemm_tile == 128) return launch_gemm_t<128, 128, 2, 2, EPI, false>(p, stream);
-#endif
-    const bool big = p.M >= 2048 && p.N >= 1024;
-    // q8 addresses a tile through a 2 GB buffer descriptor with 32-bit lane offsets
-    if (big && 512 * p.lda + 2 * (int64_t)p.K < (1ll << 31) && 514 * (int64_t)p.K < (1ll << 31)) return launch_gemm_q8<EPI>(p, stream);
-    if (big) return launch_gemm_t<256, 256, 2, 4, EPI, true>(p, stream);
-    return launch_gemm_t<128, 128, 2, 2, EPI, false>(p, stream);
-}
-
 // ================================================================================================
 // gemm4: the hand-scheduled 4-wave kernels (256 x 256 x 64 tile, one wave per SIMD, wave tile 128 x 128 as 8 x 8 blocks of
 // v_mfma_f32_16x16x32_bf16, the 256 accumulators of a lane in a[0:255], LDS-DMA staging two tiles deep inside two 64 KB slots, the
@@ -594,9 +552,130 @@ static bool gemm4_eligible(int64_t lda, int64_t ldc, int64_t ldr, int64_t M, int
            M * ldc < lim && M * std::max<int64_t>(ldr, 1) < lim && 256 * lda < lim;
 }
 
-extern "C" int scail_gemm_kernel_for(int64_t lda, int64_t ldc, int64_t ldr, int64_t M, int64_t N, int64_t K, int epilogue) {
+// ------------------------------------------------------------------------------------------------
+// Which kernel a bf16 GEMM runs.  gemm_choose is the ONE statement of it: scail_gemm_bf16 launches what it says, and the host-only queries
+// (scail_gemm_kernel_for, scail_gemm_kernel_name_for) are projections of the same answer.  Nothing else reads option "gemm4", the
+// measurement build's gemm_tile / gemm4 knobs or gemm4_eligible.
+// ------------------------------------------------------------------------------------------------
+enum GemmKernel { GEMM_GEN,                                           // generated (csrc/gemm4.s; measurement build: gemm8, the A/B variants)
+                  GEMM_T128, GEMM_T256_DMA, GEMM_Q8,                  // hipcc: gemm_bf16_kernel<128, ..>, gemm_bf16_kernel<256, .., DMA>, gemm_bf16_q8_kernel
+                  GEMM_T256, GEMM_T256_DMA_SPREAD, GEMM_T256_4W, GEMM_Q8_PRIO, GEMM_TIMING };      // measurement build, forced by gemm_tile only
+struct GemmChoice {
+    GemmKernel kernel = GEMM_T128;
+    int generated = 0;       // 4 / 8: a generated kernel of gemm4.s / gemm8.s (scail_gemm_kernel_for's answer); 0: a hipcc kernel
+    int forced = 0;          // measurement build: the gemm_tile code that forced the kernel (0: chosen by shape)
+    int epilogue = 0;        // SCAIL_EPI_*
+    bool gated = false;      // the residual epilogue has a gate (the generated kernels have one entry point for each form)
+};
+
+#ifdef SCAIL_ABLATIONS
+// gemm_tile codes >= 1000: timing ablations of the big-tile kernels (wrong results on purpose; bias epilogue only; tools/microbench.py)
+static const struct { int code; int (*launch)(const GemmParams&, hipStream_t); } k_gemm_timing[] = {
+    {1101, launch_gemm_q8<0, 1>},   {1102, launch_gemm_q8<0, 2>},   {1103, launch_gemm_q8<0, 3>},   {1104, launch_gemm_q8<0, 4>},
+    {1108, launch_gemm_q8<0, 8>},   {1112, launch_gemm_q8<0, 12>},  {1300, launch_gemm_q8<0, 128>}, {1301, launch_gemm_q8<0, 129>},
+    {1302, launch_gemm_q8<0, 130>}, {1303, launch_gemm_q8<0, 131>}, {1364, launch_gemm_q8<0, 192>}, {1256, launch_gemm_q8<0, 256>},
+    {1512, launch_gemm_q8<0, 512>}, {1164, launch_gemm_q8<0, 64>},  {1116, launch_gemm_q8<0, 16>},  {1124, launch_gemm_q8<0, 24>},
+    {1001, launch_gemm_t<256, 256, 2, 4, 0, true, 1>}, {1002, launch_gemm_t<256, 256, 2, 4, 0, true, 2>}, {1003, launch_gemm_t<256, 256, 2, 4, 0, true, 3>},
+    {1008, launch_gemm_t<256, 256, 2, 4, 0, true, 8>}, {1024, launch_gemm_t<256, 256, 2, 4, 0, true, 24>},
+};
+#endif
+
+static GemmChoice gemm_choose(int64_t lda, int64_t ldc, int64_t ldr, int64_t M, int64_t N, int64_t K, int epilogue, bool gated) {
+    GemmChoice c;
+    c.epilogue = epilogue;
+    c.gated = gated;
+#ifdef SCAIL_ABLATIONS
+    // forced tiles / schedules and timing ablations of the measurement build (scail_gemm_tune): a forced tile never runs a generated kernel
+    c.forced = g_gemm_tile;
+    switch (c.forced) {
+        case 128: c.kernel = GEMM_T128; return c;
+        case 256: c.kernel = GEMM_T256; return c;
+        case 257: c.kernel = GEMM_T256_DMA; return c;
+        case 260: c.kernel = GEMM_T256_DMA_SPREAD; return c;      // DMA issue spread over the k-steps
+        case 261: c.kernel = GEMM_Q8; return c;
+        case 262: c.kernel = GEMM_Q8_PRIO; return c;              // q8, issue priority to the MFMA wave
+        case 266: c.kernel = GEMM_T256_4W; return c;              // 4 waves, 128 x 128 per wave (AGPR accumulators)
+        default: break;
+    }
+    if (c.forced && epilogue == SCAIL_EPI_BIAS)
+        for (const auto& t : k_gemm_timing)
+            if (t.code == c.forced) { c.kernel = GEMM_TIMING; return c; }
+    // (a timing code with another epilogue: the hipcc kernels by shape)
+#endif
     const int mode = g_gemm4_mode;
-    return (mode && gemm4_eligible(lda, ldc, ldr, M, N, K, epilogue)) ? mode : 0;
+    if (mode && !c.forced && gemm4_eligible(lda, ldc, ldr, M, N, K, epilogue)) {
+        c.kernel = GEMM_GEN;
+        c.generated = mode;
+        return c;
+    }
+    // measured at M = 97 664 (profiles/r01_pmc.md): 128 tile 820, 256 tile 1000, 256 + LDS-DMA 1090, 256 + DMA ring
+    // of half k-tiles with counted vmcnt 1025, ping-pong 1000, quadrant-phase q8 1240-1290 TFLOP/s (default for the
+    // big shapes the generated kernels refuse; the vendor library's assembly kernel reaches 1500 on the same shapes)
+    const bool big = M >= 2048 && N >= 1024;
+    // q8 addresses a tile through a 2 GB buffer descriptor with 32-bit lane offsets
+    c.kernel = !big ? GEMM_T128 : (512 * lda + 2 * K < (1ll << 31) && 514 * K < (1ll << 31)) ? GEMM_Q8 : GEMM_T256_DMA;
+    return c;
+}
+
+// The choice in words (scail_gemm_kernel_name_for; the launch of a generated kernel resolves its symbol by it): a generated kernel's symbol, a
+// hipcc kernel's template with the arguments of the instantiation, "gemm_tile <code>: " in front where the measurement build forced it.
+static std::string gemm_choice_name(const GemmChoice& c) {
+    if (c.kernel == GEMM_GEN) {
+        const int epi4 = c.epilogue == SCAIL_EPI_RESID ? (c.gated ? 3 : 4) : c.epilogue;
+        std::string name = std::string(c.generated == 8 ? "scail_gemm8_e" : "scail_gemm4_e") + std::to_string(epi4);
+        if (epi4 == 0 || g_gemm4_suffix == "_pst" || g_gemm4_suffix == "_part" || g_gemm4_suffix == "_stgnt") name += g_gemm4_suffix;      // A/B variants: bias epilogue only, except the persistent set (ablation build)
+        return name;
+    }
+    const std::string e = std::to_string(c.epilogue), t256 = "gemm_bf16_kernel<256, 256, 2, 4, " + e;
+    std::string name;
+    switch (c.kernel) {
+        case GEMM_T128: name = "gemm_bf16_kernel<128, 128, 2, 2, " + e + ", false>"; break;
+        case GEMM_T256: name = t256 + ", false>"; break;
+        case GEMM_T256_DMA: name = t256 + ", true>"; break;
+        case GEMM_T256_DMA_SPREAD: name = t256 + ", true, 4>"; break;
+        case GEMM_T256_4W: name = "gemm_bf16_kernel<256, 256, 2, 2, " + e + ", true>"; break;
+        case GEMM_Q8: name = "gemm_bf16_q8_kernel<" + e + ">"; break;
+        case GEMM_Q8_PRIO: name = "gemm_bf16_q8_kernel<" + e + ", 32>"; break;
+        default: name = "timing ablation"; break;
+    }
+    return c.forced ? "gemm_tile " + std::to_string(c.forced) + ": " + name : name;
+}
+
+template <int EPI>
+static int launch_gemm(const GemmChoice& c, const GemmParams& p, hipStream_t stream) {
+    switch (c.kernel) {
+        case GEMM_T128: return launch_gemm_t<128, 128, 2, 2, EPI, false>(p, stream);
+        case GEMM_T256_DMA: return launch_gemm_t<256, 256, 2, 4, EPI, true>(p, stream);
+        case GEMM_Q8: return launch_gemm_q8<EPI>(p, stream);
+#ifdef SCAIL_ABLATIONS
+        case GEMM_T256: return launch_gemm_t<256, 256, 2, 4, EPI, false>(p, stream);
+        case GEMM_T256_DMA_SPREAD: return launch_gemm_t<256, 256, 2, 4, EPI, true, 4>(p, stream);
+        case GEMM_T256_4W: return launch_gemm_t<256, 256, 2, 2, EPI, true>(p, stream);
+        case GEMM_Q8_PRIO: return launch_gemm_q8<EPI, 32>(p, stream);
+        case GEMM_TIMING:
+            for (const auto& t : k_gemm_timing)
+                if (t.code == c.forced) return t.launch(p, stream);
+            break;
+#endif
+        default: break;
+    }
+    scail_set_error("scail_gemm_bf16: no hipcc kernel for the choice " + gemm_choice_name(c));
+    return 2;
+}
+
+extern "C" int scail_gemm_kernel_for(int64_t lda, int64_t ldc, int64_t ldr, int64_t M, int64_t N, int64_t K, int epilogue) {
+    return gemm_choose(lda, ldc, ldr, M, N, K, epilogue, false).generated;
+}
+
+extern "C" int scail_gemm_kernel_name_for(int64_t lda, int64_t ldc, int64_t ldr, int64_t M, int64_t N, int64_t K, int epilogue, int gated,
+                                          char* buf, int64_t len) {
+    SCAIL_REQUIRE(buf != nullptr, "null argument");
+    SCAIL_REQUIRE(epilogue >= SCAIL_EPI_BIAS && epilogue <= SCAIL_EPI_RESID, "unknown epilogue");
+    SCAIL_REQUIRE(K > 0 && K % BK == 0 && N % 8 == 0, "K must be a positive multiple of 64, N a multiple of 8");
+    const std::string name = gemm_choice_name(gemm_choose(lda, ldc, ldr, M, N, K, epilogue, epilogue == SCAIL_EPI_RESID && gated != 0));
+    SCAIL_REQUIRE((int64_t)name.size() < len, "buffer too small");
+    std::memcpy(buf, name.c_str(), name.size() + 1);
+    return 0;
 }
 
 // load the embedded code object and resolve the four shipped kernels now (see scail_attn4_preload)
@@ -637,16 +716,10 @@ extern "C" int scail_gemm_bf16(const scail_bf16* x, int64_t lda, const scail_bf1
         SCAIL_REQUIRE(resid != nullptr && ldr % 4 == 0, "RESID epilogue needs resid with ldr % 4 == 0");
         SCAIL_REQUIRE(gate == nullptr || (rows_per_batch > 0 && gate_stride % 4 == 0), "gate needs rows_per_batch > 0, gate_stride % 4 == 0");
     }
-#ifdef SCAIL_ABLATIONS
-    const bool forced_tile = g_gemm_tile != 0;
-#else
-    const bool forced_tile = false;
-#endif
-    if (g_gemm4_mode && !forced_tile && gemm4_eligible(lda, ldc, ldr, M, N, K, epilogue)) {
-        const int epi4 = epilogue == SCAIL_EPI_RESID ? (gate != nullptr ? 3 : 4) : epilogue;
-        const bool is8 = g_gemm4_mode == 8;
-        std::string name = std::string(is8 ? "scail_gemm8_e" : "scail_gemm4_e") + std::to_string(epi4);
-        if (epi4 == 0 || g_gemm4_suffix == "_pst" || g_gemm4_suffix == "_part" || g_gemm4_suffix == "_stgnt") name += g_gemm4_suffix;      // A/B variants: bias epilogue only, except the persistent set (ablation build)
+    const GemmChoice choice = gemm_choose(lda, ldc, ldr, M, N, K, epilogue, epilogue == SCAIL_EPI_RESID && gate != nullptr);
+    if (choice.kernel == GEMM_GEN) {
+        const bool is8 = choice.generated == 8;
+        const std::string name = gemm_choice_name(choice);
 #ifdef SCAIL_ABLATIONS
         const void* image = is8 ? k_gemm8_hsaco : k_gemm4_hsaco;
 #else
@@ -681,13 +754,13 @@ extern "C" int scail_gemm_bf16(const scail_bf16* x, int64_t lda, const scail_bf1
     p.group_m = g_group_m;
     hipStream_t s = (hipStream_t)stream;
     switch (epilogue) {
-        case SCAIL_EPI_BIAS: return launch_gemm<SCAIL_EPI_BIAS>(p, s);
-        case SCAIL_EPI_GELU_TANH: return launch_gemm<SCAIL_EPI_GELU_TANH>(p, s);
-        case SCAIL_EPI_GELU_ERF: return launch_gemm<SCAIL_EPI_GELU_ERF>(p, s);
+        case SCAIL_EPI_BIAS: return launch_gemm<SCAIL_EPI_BIAS>(choice, p, s);
+        case SCAIL_EPI_GELU_TANH: return launch_gemm<SCAIL_EPI_GELU_TANH>(choice, p, s);
+        case SCAIL_EPI_GELU_ERF: return launch_gemm<SCAIL_EPI_GELU_ERF>(choice, p, s);
         case SCAIL_EPI_RESID:
             SCAIL_REQUIRE(resid != nullptr && ldr % 4 == 0, "RESID epilogue needs resid with ldr % 4 == 0");
             SCAIL_REQUIRE(gate == nullptr || (rows_per_batch > 0 && gate_stride % 4 == 0), "gate needs rows_per_batch > 0, gate_stride % 4 == 0");
-            return launch_gemm<SCAIL_EPI_RESID>(p, s);
+            return launch_gemm<SCAIL_EPI_RESID>(choice, p, s);
         default:
             scail_set_error("scail_gemm_bf16: unknown epilogue");
             return 1;

@@ -33,6 +33,7 @@ SIGNATURES = {
     "scail_comm_standin": [_p, _p, _i64, C.c_int32, _i64, _p],
     "scail_cross_attn2_kernel_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64],
     "scail_gemm_kernel_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i],
+    "scail_gemm_kernel_name_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _p, _i64],
     "scail_conv3d_kernel_for": [_p, _i64, _i64, _i],
     "scail_conv3d_norm_fused_for": [_p, _i64],
     "scail_conv3d_kernel_name_for": [_p, _i64, _i64, _i, _p, _i64],
@@ -127,7 +128,7 @@ RESIZE_MAX_SCALE = 16
 ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- scail_vae_decode_stream, its workspace query, scail_to / from_channels_last_frames --
                          # and no existing call changed: still 8; load() fails on a library that lacks them; likewise the request
                          # preprocessing, scail_resize_crop_aa / scail_pose_half, and the convolution queries scail_conv3d_norm_fused_for /
-                         # scail_conv3d_kernel_name_for)
+                         # scail_conv3d_kernel_name_for, and the GEMM query scail_gemm_kernel_name_for)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);

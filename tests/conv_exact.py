@@ -331,7 +331,7 @@ def kernel_name(case, form, ldc, ldr, ot_mul=1, ot_off=0):
 OPTION_DEFAULTS = {"conv4": 1, "conv4_cont": 1, "conv4_resnorm": 1, "conv_direct": 1, "conv_s2": 1}
 
 
-def with_options(opts, fn):
+def with_options(opts, fn, defaults=OPTION_DEFAULTS):
     """fn() under the library options ``opts``; the defaults (everything on, conv_s2 = 1) are back afterwards, whatever happens"""
     from scail_amd import lib as L
     try:
@@ -340,4 +340,4 @@ def with_options(opts, fn):
         return fn()
     finally:
         for name in opts:
-            L.set_option(name, OPTION_DEFAULTS[name])
+            L.set_option(name, defaults[name])
