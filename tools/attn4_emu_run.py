@@ -52,18 +52,23 @@ def reference(q, k, v, heads):
 
 
 def run(cfg: attn4.Cfg, q: np.ndarray, ksegs, vsegs, heads: int, lazy: bool = True, thr_log2: float = 8.0, program=None, mode=None,
-        raw_scale: bool = False, launches=None, count_restarts: bool = True):
+        raw_scale: bool = False, launches=None, count_restarts: bool = True, sl2=None):
     """q (B, Lq, H*128) fp32; ksegs / vsegs: lists (one per segment) of (B, Lk, H*128) fp32.  Returns O (B, Lq, H*128) fp32
     and the emulator statistics of the last workgroup.  raw_scale (qscale kernels): q goes in UNSCALED with sl2 = scale * log2(e)
-    as the kernel argument (the prologue multiplies the fragments), instead of pre-multiplied with sl2 = 0."""
+    as the kernel argument (the prologue multiplies the fragments), instead of pre-multiplied with sl2 = 0.  ``sl2`` (fold kernels): q goes
+    in AS GIVEN and scores count sl2 log2 units each -- 1.0: q is in log2 units already; any other value is the raw-scale argument."""
     B, Lq, D = q.shape
     n_seg = len(ksegs)
     Lk = ksegs[0].shape[1]
     assert Lk % 64 == 0 or getattr(cfg, "ragged", False)
     Lkp = (Lk + 63) // 64 * 64
     mem = E.Memory(size=1 << 26)
-    sl2 = (1.0 / math.sqrt(128.0)) * 1.4426950408889634
     fold = getattr(cfg, "fold", False)
+    if sl2 is not None:
+        assert fold and not raw_scale, "an explicit sl2 is for the kernels that work in log2 units"
+        raw_scale = sl2 != 1.0
+    else:
+        sl2 = (1.0 / math.sqrt(128.0)) * 1.4426950408889634
     # fold: the caller hands over q already multiplied by scale * log2(e) (one rounding to bf16, as scail_rmsnorm_rope_scaled does)
     qb = to_bf16_bits(q * np.float32(sl2)) if (fold and not raw_scale) else to_bf16_bits(q)
     kb = np.stack([to_bf16_bits(x) for x in ksegs])                       # (S, B, Lk, D)
@@ -99,15 +104,21 @@ def run(cfg: attn4.Cfg, q: np.ndarray, ksegs, vsegs, heads: int, lazy: bool = Tr
 
 
 def run_x2(cfg: attn4.Cfg, q: np.ndarray, k1, v1, k2, v2, heads: int, n_wgs: int = 2, lazy: bool = True, thr_log2: float = 8.0, raw_scale: bool = False,
-           program=None):
+           program=None, sl2=None):
     """The two-key-set cross attention kernel (Cfg.x2): q (B, Lq, H*128) fp32; k1 / v1 (B, Lk1, H*128), k2 / v2 (B2, Lk2, H*128) with B2 in
-    {1, B} (a shared CLIP set has batch stride 0).  ``n_wgs`` persistent workgroups walk over the items.  Returns O and the statistics."""
+    {1, B} (a shared CLIP set has batch stride 0).  ``n_wgs`` persistent workgroups walk over the items.  ``sl2``: as in run().  Returns O and
+    the statistics."""
     B, Lq, D = q.shape
     Lk1, Lk2 = k1.shape[1], k2.shape[1]
     Lkp1, Lkp2 = (Lk1 + 63) // 64 * 64, (Lk2 + 63) // 64 * 64
     mem = E.Memory(size=1 << 26)
-    sl2 = (1.0 / math.sqrt(128.0)) * 1.4426950408889634
-    qb = to_bf16_bits(q) if raw_scale else to_bf16_bits(q * np.float32(sl2))
+    given = sl2 is not None
+    if given:
+        assert not raw_scale
+        raw_scale = sl2 != 1.0
+    else:
+        sl2 = (1.0 / math.sqrt(128.0)) * 1.4426950408889634
+    qb = to_bf16_bits(q) if (raw_scale or given) else to_bf16_bits(q * np.float32(sl2))
     pq = mem.alloc("q", qb)
     pk1 = mem.alloc("k1", to_bf16_bits(k1))
     pv1 = mem.alloc("vt1", transpose_v(to_bf16_bits(v1), heads))
