@@ -111,6 +111,17 @@ int64_t scail_vae_decode_stream_workspace_bytes(const scail_vae* h, int64_t chun
 int scail_vae_decode_stream(scail_vae* h, const float* latent, float* video, int64_t Tl, int64_t hl, int64_t wl,
                             int64_t chunk, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The opt-in uint8 output route: scail_vae_decode / scail_vae_decode_stream with ONE difference -- the last launch (of each chunk) is
+ * scail_frames_u8 (scail_hip.h) on the chunk's frame window in place of the fp32 layout pass, so the clip comes out as the pixels a file writer
+ * takes and no fp32 video buffer exists anywhere in the call.  frames: the dense uint8 clip [T][H][W][3] on the device, T = 1 + 4 (Tl - 1),
+ * H = 8 hl, W = 8 wl, channel order R, G, B; a pixel is trunc(255 * clamp((v + 1) / 2, 0, 1)) of the bf16 value v the fp32 call would have
+ * widened (NaN -> 0).  Operator chain, kernel choices, workspace sizes and their queries, carry plan, the one-frame-remainder rule, the trace
+ * callback and the refusals are those of the fp32 calls: the same code. */
+int scail_vae_decode_u8(scail_vae* h, const float* latent, uint8_t* frames, int64_t Tl, int64_t hl, int64_t wl,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int scail_vae_decode_stream_u8(scail_vae* h, const float* latent, uint8_t* frames, int64_t Tl, int64_t hl, int64_t wl,
+                               int64_t chunk, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

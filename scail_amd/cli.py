@@ -11,7 +11,8 @@ branch and is never read by the network -- a zero-size placeho
 
 Requests: ``--ref-image ref.jpg --pose-video <frames dir | .npy | animated .webp/.png/.gif | Motion-JPEG .mp4> [--conditioning c.pt]`` runs
 the reference's preprocessing (centre crop, [-1, 1], half-resolution pose; scail_amd/preprocess.py; ``--preprocess hip`` = on the GPU
-with the library's kernels, chunked) on files, or
+with the library's kernels, chunked; ``--postprocess hip`` = the VAE decoder's last kernel writes the uint8 frames the file writers take, so no
+fp32 video exists on either side) on files, or
 ``--inputs file.pt`` passes tensors directly: ref (3,1,H,W) in [-1,1], pose (3,T,H,W), context (1,Lt,4096),
 uncond_context (1,Lt,4096), clip (1,257,1280); without either synthetic inputs are drawn.  ``--save-dir`` writes
 ``0_output_000000.webp`` (lossless animated WebP; ``--format`` for APNG / GIF / .npy / frames, or ``.mp4`` = the reference's
@@ -174,6 +175,7 @@ def encode_conditioning(prompt: str, negative_prompt: str, ref: torch.Tensor, te
 
 
 PREPROCESS_ROUTES = ("torch", "hip")
+POSTPROCESS_ROUTES = ("torch", "hip")
 
 
 def request_from_files(ref_image: str, pose_video: str, cfg, conditioning: str = None, device="cuda", seed=0, text_dim=4096,
@@ -229,7 +231,13 @@ def build_engine(cfg, load=None, device="cuda"):
 
 
 def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frames=None, engine=None, tile_frames=None, tile_overlap=None,
-        vae_chunk_frames=None):
+        vae_chunk_frames=None, postprocess="torch"):
+    """``postprocess``: "torch" (default) returns the video as fp32 (B, 3, T, H, W) in [0, 1]; "hip" returns it as the file writers' pixels,
+    uint8 (B, T, H, W, 3) on the device, written by the VAE decoder's last kernel (engine.decode_first_stage_u8; needs a GPU)."""
+    if postprocess not in POSTPROCESS_ROUTES:
+        raise ValueError(f"postprocess must be one of {POSTPROCESS_ROUTES}, got {postprocess!r}")
+    if postprocess == "hip" and not torch.cuda.is_available():
+        raise lib.ScailHipError("postprocess='hip' writes the uint8 frames with the library's kernels and needs a GPU; there is no host fallback")
     engine = engine or build_engine(cfg, load, device)
     H, W = cfg.get("args", {}).get("sampling_image_size", [512, 896])
     net = engine.network
@@ -246,7 +254,7 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
             raise ValueError(f"a pose clip longer than one window needs 4n + 1 frames (the causal VAE's frame groups), got {n_pix}")
         Tt, overlap = tile_args(tile_frames, tile_overlap, net.num_frames)
         tiles = plan_tiles((n_pix - 1) // 4 + 1, Tt, overlap)
-        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames)
+        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames, postprocess)
     pose_lat = engine.encode_first_stage(req["pose"].unsqueeze(0), None, force_encode=True)   # already half resolution (:350-351)
     ref_concat = ref_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)      # B C T H W -> B T C H W
     pose_latent = pose_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)
@@ -257,22 +265,27 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     uc = dict(crossattn=req["uncond_context"], **shared)
     torch.manual_seed(seed)
     z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps)
-    return _finish(engine, z, t0, vae_chunk_frames)
+    return _finish(engine, z, t0, vae_chunk_frames, postprocess)
 
 
-def _finish(engine, z, t0, vae_chunk_frames=None):
-    """sampled latent (B T C H W) -> (video in [0, 1], latent (B C T H W), seconds); (None, None, seconds) off sequence-parallel rank 0"""
+def _finish(engine, z, t0, vae_chunk_frames=None, postprocess="torch"):
+    """sampled latent (B T C H W) -> (video in [0, 1], latent (B C T H W), seconds); (None, None, seconds) off sequence-parallel rank 0.
+    ``postprocess`` "hip": the video is uint8 (B, T, H, W, 3) instead, the same pixels the writers make of the fp32 one."""
     if engine.sp is not None and engine.sp.size > 1 and engine.sp.rank != 0:
         torch.cuda.synchronize()
         return None, None, time.perf_counter() - t0                         # only SP rank 0 holds the gathered latent (:484)
     z = z.permute(0, 2, 1, 3, 4).contiguous()                               # B T C H W -> B C T H W (:484-485)
+    if postprocess == "hip":
+        video = engine.decode_first_stage_u8(z.float(), chunk_frames=vae_chunk_frames)
+        torch.cuda.synchronize()
+        return video, z, time.perf_counter() - t0
     x = engine.decode_first_stage(z.float(), chunk_frames=vae_chunk_frames)
     video = torch.clamp((x + 1.0) / 2.0, 0.0, 1.0)                          # (:494)
     torch.cuda.synchronize()
     return video, z, time.perf_counter() - t0
 
 
-def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames=None):
+def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames=None, postprocess="torch"):
     """A pose clip longer than one window (an extension, see the module docstring): RFSamplerLong with the configured sampler's
     parameters over ``tiles``; every window's pose frames [4 start, 4 (start + Tt - 1)] are VAE-encoded on their own (the causal VAE treats
     a window's first frame as a clip's first frame, which is how ``smpl_tiled[:, k]`` is used); noise and decode for the whole latent."""
@@ -297,7 +310,7 @@ def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_ch
         z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, tile_indices=tiles)
     finally:
         engine.sampler = plain
-    return _finish(engine, z, t0, vae_chunk_frames)
+    return _finish(engine, z, t0, vae_chunk_frames, postprocess)
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -340,7 +353,17 @@ def build_parser() -> argparse.ArgumentParser:
                     help="where the reference image and the driving video are resized, cropped and halved: torch = on the host, the whole clip "
                          "at once as fp32; hip = on the GPU with the library's kernels, the clip crossing as uint8 a chunk of frames at a time "
                          "(bounded host and device memory for long clips)")
+    ap.add_argument("--postprocess", choices=POSTPROCESS_ROUTES, default="torch",
+                    help="where the decoded clip becomes the writers' 8-bit pixels: torch = the decoder returns fp32, clamp and scaling run as "
+                         "torch ops and the writer quantises on the host; hip = the decoder's last kernel writes uint8 (T, H, W, 3) frames, "
+                         "which cross to the host once (no fp32 video on either side; --out then holds the uint8 tensor)")
     return ap
+
+
+def _save(video_io, video, save_dir, fps, key, ext):
+    """the clip of ``run`` to files: fp32 (B, 3, T, H, W) goes to the writer as (B, T, 3, H, W), uint8 (B, T, H, W, 3) as it is"""
+    samples = video.cpu() if video.dtype == torch.uint8 else video.permute(0, 2, 1, 3, 4).contiguous().cpu()      # B C T H W -> B T C H W (:493)
+    return video_io.save_multi_video_grid([samples], save_dir, fps=fps, key=key, ext=ext)
 
 
 def main(argv=None):
@@ -354,7 +377,7 @@ def main(argv=None):
             tile_args(a.tile_frames, a.tile_overlap, cfg["model"]["network_config"].get("params", {}).get("num_frames", 81))
         except ValueError as e:
             ap.error(str(e))
-    tk = dict(tile_frames=a.tile_frames, tile_overlap=a.tile_overlap, vae_chunk_frames=a.vae_chunk_frames)
+    tk = dict(tile_frames=a.tile_frames, tile_overlap=a.tile_overlap, vae_chunk_frames=a.vae_chunk_frames, postprocess=a.postprocess)
     if a.gemm_precision is not None:
         cfg = copy.deepcopy(cfg)
         cfg["model"]["network_config"].setdefault("params", {})["gemm_precision"] = a.gemm_precision
@@ -378,9 +401,8 @@ def main(argv=None):
             os.makedirs(save_dir, exist_ok=True)
             with open(os.path.join(save_dir, "text.txt"), "w") as f:                   # sample_video.py:413-414
                 f.write(text)
-            samples = video.permute(0, 2, 1, 3, 4).contiguous().cpu()
-            paths = video_io.save_multi_video_grid([samples], save_dir, fps=cfg.get("args", {}).get("sampling_fps", 16),
-                                                   key=f"{os.path.basename(os.path.normpath(input_dir))}_output", ext=a.format)
+            paths = _save(video_io, video, save_dir, cfg.get("args", {}).get("sampling_fps", 16),
+                          f"{os.path.basename(os.path.normpath(input_dir))}_output", a.format)
             print(f"  latent {tuple(z.shape)} -> video {tuple(video.shape)} in {dt:.2f} s; wrote {', '.join(paths)}")
         return
     inputs = torch.load(a.inputs) if a.inputs else None
@@ -403,9 +425,7 @@ def main(argv=None):
         torch.save({"video": video.cpu(), "latent": z.cpu()}, a.out)
     if a.save_dir:
         from . import video_io
-        samples = video.permute(0, 2, 1, 3, 4).contiguous().cpu()                      # B C T H W -> B T C H W (:493)
-        paths = video_io.save_multi_video_grid([samples], a.save_dir, fps=cfg.get("args", {}).get("sampling_fps", 16),
-                                               key="0_output", ext=a.format)
+        paths = _save(video_io, video, a.save_dir, cfg.get("args", {}).get("sampling_fps", 16), "0_output", a.format)
         print("wrote", ", ".join(paths))
 
 

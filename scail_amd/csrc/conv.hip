@@ -1060,6 +1060,58 @@ __global__ void from_channels_last_frames_kernel(const u16* __restrict__ x, int6
     }
 }
 
+// channels-last bf16 (N, ldx), channels 0..2 = R, G, B -> the uint8 pixels a file writer takes (scail_frames_u8): the request's whole output
+// tail -- widen, (x + 1) / 2, clamp to [0, 1], 255 *, truncate -- as one pass.  The arithmetic is the default route's operation by operation
+// in fp32, each rounded on its own (torch.clamp((x + 1) / 2, 0, 1), then numpy's (255.0 * .).astype(uint8)); fmaxf returns its other argument
+// for a NaN, which makes a NaN pixel 0.  WanVAE.decode's clamp(-1, 1) in front needs no instruction: (x + 1) / 2 is monotone and maps what that
+// clamp cuts off onto what the clamp to [0, 1] cuts off, so y is the same for every input.
+__device__ __forceinline__ uint32_t frames_u8_quant(float v) {
+    const float y = fminf(fmaxf((v + 1.0f) / 2.0f, 0.0f), 1.0f);
+    return (uint32_t)(int)(255.0f * y);
+}
+
+// The output is nseg contiguous runs ("segments") of seg_vox voxels = 3 seg_vox bytes: the whole window when it is dense, a frame when only the
+// rows are dense, else a row; segment s starts at out + (s / segs_per_frame) * frame_bytes + (s % segs_per_frame) * seg_stride.  A workgroup
+// takes FU8_VOX consecutive voxels of one segment: every thread reads FU8_VPT voxels with one 16-byte load each (a wave reads 1 KiB of
+// consecutive rows at ldx = 8) and puts their 3 bytes into LDS, at the offset the byte has in global memory modulo 16; after the barrier the
+// image leaves as whole 16-byte slots, one dwordx4 store per lane, and only the up to two ragged slots at the ends of the run leave as bytes.
+constexpr int FU8_VPT = 4, FU8_VOX = 256 * FU8_VPT;
+__global__ __launch_bounds__(256) void frames_u8_kernel(const u16* __restrict__ x, int64_t ldx, uint8_t* __restrict__ out, int64_t seg_vox,
+                                                        int64_t segs_per_frame, int64_t seg_stride, int64_t frame_bytes, int64_t blocks_per_seg) {
+    __shared__ __attribute__((aligned(16))) uint8_t img[3 * FU8_VOX + 16];
+    const int64_t s = blockIdx.x / blocks_per_seg, v0 = (blockIdx.x % blocks_per_seg) * FU8_VOX;
+    const int nvox = (int)(seg_vox - v0 < FU8_VOX ? seg_vox - v0 : FU8_VOX);
+    uint8_t* dst = out + (s / segs_per_frame) * frame_bytes + (s % segs_per_frame) * seg_stride + 3 * v0;
+    const int a = (int)(reinterpret_cast<uintptr_t>(dst) & 15);
+    const u16* src = x + (s * seg_vox + v0) * ldx;
+    uint4 r[FU8_VPT];
+#pragma unroll
+    for (int k = 0; k < FU8_VPT; ++k) {
+        const int i = k * 256 + threadIdx.x;
+        r[k] = i < nvox ? *reinterpret_cast<const uint4*>(src + (int64_t)i * ldx) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (int k = 0; k < FU8_VPT; ++k) {
+        const int i = k * 256 + threadIdx.x;
+        if (i < nvox) {
+            uint8_t* p = img + a + 3 * i;
+            p[0] = (uint8_t)frames_u8_quant(bf_lo(r[k].x));
+            p[1] = (uint8_t)frames_u8_quant(bf_hi(r[k].x));
+            p[2] = (uint8_t)frames_u8_quant(bf_lo(r[k].y));
+        }
+    }
+    __syncthreads();
+    const int end = a + 3 * nvox;                       // the run is img[a, end); img[j] belongs at dst - a + j, where 16-byte slots are aligned
+    for (int j = threadIdx.x * 16; j < end; j += 256 * 16) {
+        if (j >= a && j + 16 <= end) {
+            *reinterpret_cast<uint4*>(dst - a + j) = *reinterpret_cast<const uint4*>(img + j);
+        } else {
+            const int lo = j > a ? j : a, hi = j + 16 < end ? j + 16 : end;
+            for (int b = lo; b < hi; ++b) dst[b - a] = img[b];
+        }
+    }
+}
+
 // ================================================================================================
 // C ABI
 // ================================================================================================
@@ -1535,4 +1587,28 @@ extern "C" int scail_from_channels_last_frames(const scail_bf16* x, int64_t ldx,
     if (v4) hipLaunchKernelGGL(from_channels_last_frames_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, y, a, b, (int)C, plane, off, N, lo, hi);
     else hipLaunchKernelGGL(from_channels_last_frames_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, y, a, b, (int)C, plane, off, N, lo, hi);
     return scail_check_launch("from_channels_last_frames");
+}
+
+extern "C" int scail_frames_u8(const scail_bf16* x, int64_t ldx, uint8_t* out, int64_t row_bytes, int64_t frame_bytes, int64_t n_frames,
+                               int64_t H, int64_t W, void* stream) {
+    using std::to_string;
+    SCAIL_REQUIRE(n_frames >= 0 && H >= 0 && W >= 0 && n_frames < (1 << 20) && H < (1 << 20) && W < (1 << 20),
+                  "frames_u8: sizes must be 0 .. 2^20 - 1, got n_frames = " + to_string(n_frames) + ", H = " + to_string(H) + ", W = " + to_string(W));
+    SCAIL_REQUIRE(ldx >= 8 && ldx % 8 == 0 && ldx < (1 << 20), "frames_u8: the row stride must be a multiple of 8 and at least 8 channels (16-byte rows), got ldx = " + to_string(ldx));
+    SCAIL_REQUIRE(row_bytes >= 3 * W, "frames_u8: a row of " + to_string(W) + " pixels needs " + to_string(3 * W) + " bytes, got row_bytes = " + to_string(row_bytes));
+    SCAIL_REQUIRE(H == 0 || (row_bytes < (1ll << 40) && frame_bytes >= H * row_bytes),
+                  "frames_u8: a frame of " + to_string(H) + " rows needs " + to_string(H * row_bytes) + " bytes, got frame_bytes = " + to_string(frame_bytes));
+    if (n_frames * H * W == 0) return 0;
+    SCAIL_REQUIRE(x != nullptr && out != nullptr, std::string("frames_u8: null pointer: ") + (x == nullptr ? "x" : "out"));
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0, "frames_u8: x needs 16-byte aligned rows, got an address that ends in " + to_string(reinterpret_cast<uintptr_t>(x) & 15));
+    // the longest contiguous runs of the output: the window, its frames, or its rows
+    const bool rows_dense = row_bytes == 3 * W, frames_dense = rows_dense && frame_bytes == H * row_bytes;
+    const int64_t seg_vox = frames_dense ? n_frames * H * W : rows_dense ? H * W : W;
+    const int64_t segs_per_frame = frames_dense || rows_dense ? 1 : H, nseg = frames_dense ? 1 : n_frames * segs_per_frame;
+    const int64_t blocks_per_seg = (seg_vox + FU8_VOX - 1) / FU8_VOX;
+    SCAIL_REQUIRE(nseg * blocks_per_seg < (1ll << 31), "frames_u8: too many voxels for one launch");
+    // (a dense window is ONE segment: its frame stride is never used, and a frame-level segment's row stride neither)
+    hipLaunchKernelGGL(frames_u8_kernel, dim3((unsigned)(nseg * blocks_per_seg)), dim3(256), 0, (hipStream_t)stream, x, ldx, out, seg_vox,
+                       segs_per_frame, row_bytes, frames_dense ? 0 : frame_bytes, blocks_per_seg);
+    return scail_check_launch("frames_u8");
 }

@@ -87,6 +87,14 @@ struct Arena {
         if (rc_ != 0) return rc_;       \
     }
 #define VAE_CHK(a_) if ((a_).err) return 1;
+// SCAIL_REQUIRE in a body that several entry points share: the message names the entry point that was called (`who_`)
+#define VAE_REQUIRE(who_, cond, msg)                                                 \
+    do {                                                                             \
+        if (!(cond)) {                                                               \
+            scail_set_error(std::string(who_) + ": " + (msg) + " [" #cond "]");      \
+            return 1;                                                                \
+        }                                                                            \
+    } while (0)
 
 int copy_frame(Arena& a, scail_bf16* dst, const scail_bf16* src, int64_t elems) {
     if (hipMemcpyAsync(dst, src, elems * 2, hipMemcpyDeviceToDevice, (hipStream_t)a.stream) != hipSuccess) {
@@ -345,9 +353,16 @@ StreamPlan stream_plan(const scail_vae& h, int64_t chunk, int64_t hl, int64_t wl
     return p;
 }
 
+// Where a decode leaves the clip: planar fp32 [3][T][H][W], not clamped (f32), or the writers' uint8 [T][H][W][3] (u8: scail_frames_u8).  One of the two.
+struct VideoOut {
+    float* f32 = nullptr;
+    uint8_t* u8 = nullptr;
+};
+
 // The decoder chain over the latent frames [t0, t0 + n) of a clip of Tl: the whole clip (t0 = 0, n = Tl: scail_vae_decode) or one chunk of a
-// streamed decode, whose causal convolutions take their temporal context from the carry areas (a.head, a.later; causal_begin).
-int decode_frames(scail_vae* h, Arena& a, const float* latent, float* video, int64_t Tl, int64_t t0, int64_t n, int64_t hl, int64_t wl) {
+// streamed decode, whose causal convolutions take their temporal context from the carry areas (a.head, a.later; causal_begin).  The last launch
+// writes the chunk's frame window of `video`; everything before it is the same for both forms of output.
+int decode_frames(scail_vae* h, Arena& a, const float* latent, const VideoOut& video, int64_t Tl, int64_t t0, int64_t n, int64_t hl, int64_t wl) {
     const scail_vae_weights& w = h->w;
     void* stream = a.stream;
     const int64_t T = 1 + 4 * (Tl - 1), H = 8 * hl, W = 8 * wl;
@@ -386,8 +401,59 @@ int decode_frames(scail_vae* h, Arena& a, const float* latent, float* video, int
     const int64_t f0 = t0 == 0 ? 0 : 4 * t0 - 3;       // the clip's first latent frame stands for one video frame, every other one for four
     SCAIL_REQUIRE(x.T == (t0 == 0 ? 1 + 4 * (n - 1) : 4 * n) && x.H == H && x.W == W, "scail_vae_decode: stage table does not expand (4, 8, 8)");
     a.put(x);
-    if (whole) return scail_from_channels_last(x.p, x.C, video, nullptr, nullptr, 3, x.vox(), -3.0e38f, 3.0e38f, stream);
-    return scail_from_channels_last_frames(x.p, x.C, video, nullptr, nullptr, 3, T * H * W, f0 * H * W, x.vox(), -3.0e38f, 3.0e38f, stream);
+    if (video.u8 != nullptr) return scail_frames_u8(x.p, x.C, video.u8 + f0 * H * W * 3, 3 * W, 3 * W * H, x.T, H, W, stream);
+    if (whole) return scail_from_channels_last(x.p, x.C, video.f32, nullptr, nullptr, 3, x.vox(), -3.0e38f, 3.0e38f, stream);
+    return scail_from_channels_last_frames(x.p, x.C, video.f32, nullptr, nullptr, 3, T * H * W, f0 * H * W, x.vox(), -3.0e38f, 3.0e38f, stream);
+}
+
+// scail_vae_decode / scail_vae_decode_u8 (`who`)
+int decode_whole(const char* who, scail_vae* h, const float* latent, const VideoOut& video, int64_t Tl, int64_t hl, int64_t wl, void* workspace,
+                 int64_t workspace_bytes, void* stream) {
+    VAE_REQUIRE(who, h != nullptr && (video.f32 != nullptr || video.u8 != nullptr) && latent != nullptr, "null argument");
+    VAE_REQUIRE(who, Tl > 0 && hl > 0 && wl > 0, "bad latent shape");
+    const scail_vae_weights& w = h->w;
+    const int64_t T = 1 + 4 * (Tl - 1), H = 8 * hl, W = 8 * wl;
+    Arena a;
+    a.base = static_cast<char*>(workspace);
+    a.slot_bytes = slot_bytes_for(w, T, H, W);
+    a.stream = stream;
+    a.trace = h->trace; a.trace_user = h->trace_user;
+    VAE_REQUIRE(who, workspace != nullptr && workspace_bytes >= NSLOT * a.slot_bytes && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+                  "workspace too small or not 256-byte aligned (scail_vae_workspace_bytes)");
+    return decode_frames(h, a, latent, video, Tl, 0, Tl, hl, wl);
+}
+
+// scail_vae_decode_stream / scail_vae_decode_stream_u8 (`who`)
+int decode_stream(const char* who, scail_vae* h, const float* latent, const VideoOut& video, int64_t Tl, int64_t hl, int64_t wl, int64_t chunk, void* workspace,
+                  int64_t workspace_bytes, void* stream) {
+    VAE_REQUIRE(who, h != nullptr && (video.f32 != nullptr || video.u8 != nullptr) && latent != nullptr, "null argument");
+    VAE_REQUIRE(who, Tl > 0 && hl > 0 && wl > 0, "bad latent shape");
+    VAE_REQUIRE(who, chunk >= 2 && chunk <= (1 << 20), std::string("chunk must be at least 2 latent frames (every stage needs two frames of a chunk), got ") + std::to_string(chunk));
+    const StreamPlan plan = stream_plan(*h, chunk, hl, wl);
+    VAE_REQUIRE(who, workspace != nullptr && workspace_bytes >= plan.total() && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
+                  std::string("workspace too small or not 256-byte aligned (scail_vae_decode_stream_workspace_bytes): need ") +
+                      std::to_string(plan.total()) + " bytes, got " + std::to_string(workspace_bytes));
+    Arena a;
+    a.base = static_cast<char*>(workspace);
+    a.slot_bytes = plan.big;
+    a.n_small = 2; a.small_bytes = plan.small;
+    a.stream = stream;
+    a.trace = h->trace; a.trace_user = h->trace_user;
+    if (Tl <= chunk + 1) return decode_frames(h, a, latent, video, Tl, 0, Tl, hl, wl);       // one chunk: the launches of scail_vae_decode
+    a.head = 2;
+    a.carry = a.base + (NSLOT - 2) * plan.big + 2 * plan.small;
+    a.carry_bytes = plan.carry;
+    for (int64_t t0 = 0; t0 < Tl;) {
+        int64_t n = Tl - t0 < chunk ? Tl - t0 : chunk;
+        if (Tl - t0 - n == 1) ++n;                 // a remainder of one frame joins the last chunk: no stage ever sees fewer than two frames
+        a.later = t0 > 0;
+        a.carry_off = 0;
+        for (bool& u : a.used) u = false;
+        VAE_TRY(decode_frames(h, a, latent, video, Tl, t0, n, hl, wl));
+        VAE_REQUIRE(who, a.carry_off == plan.carry, "scail_vae_decode_stream: the chunk's causal convolutions do not match the carry plan");
+        t0 += n;
+    }
+    return 0;
 }
 
 }  // namespace
@@ -476,18 +542,16 @@ extern "C" int scail_vae_encode(scail_vae* h, const float* video, float* latent,
 
 extern "C" int scail_vae_decode(scail_vae* h, const float* latent, float* video, int64_t Tl, int64_t hl, int64_t wl,
                                 void* workspace, int64_t workspace_bytes, void* stream) {
-    SCAIL_REQUIRE(h != nullptr && video != nullptr && latent != nullptr, "null argument");
-    SCAIL_REQUIRE(Tl > 0 && hl > 0 && wl > 0, "bad latent shape");
-    const scail_vae_weights& w = h->w;
-    const int64_t T = 1 + 4 * (Tl - 1), H = 8 * hl, W = 8 * wl;
-    Arena a;
-    a.base = static_cast<char*>(workspace);
-    a.slot_bytes = slot_bytes_for(w, T, H, W);
-    a.stream = stream;
-    a.trace = h->trace; a.trace_user = h->trace_user;
-    SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= NSLOT * a.slot_bytes && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
-                  "workspace too small or not 256-byte aligned (scail_vae_workspace_bytes)");
-    return decode_frames(h, a, latent, video, Tl, 0, Tl, hl, wl);
+    VideoOut out;
+    out.f32 = video;
+    return decode_whole(__func__, h, latent, out, Tl, hl, wl, workspace, workspace_bytes, stream);
+}
+
+extern "C" int scail_vae_decode_u8(scail_vae* h, const float* latent, uint8_t* frames, int64_t Tl, int64_t hl, int64_t wl,
+                                   void* workspace, int64_t workspace_bytes, void* stream) {
+    VideoOut out;
+    out.u8 = frames;
+    return decode_whole(__func__, h, latent, out, Tl, hl, wl, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t scail_vae_decode_stream_workspace_bytes(const scail_vae* h, int64_t chunk, int64_t hl, int64_t wl) {
@@ -497,32 +561,14 @@ extern "C" int64_t scail_vae_decode_stream_workspace_bytes(const scail_vae* h, i
 
 extern "C" int scail_vae_decode_stream(scail_vae* h, const float* latent, float* video, int64_t Tl, int64_t hl, int64_t wl,
                                        int64_t chunk, void* workspace, int64_t workspace_bytes, void* stream) {
-    SCAIL_REQUIRE(h != nullptr && video != nullptr && latent != nullptr, "null argument");
-    SCAIL_REQUIRE(Tl > 0 && hl > 0 && wl > 0, "bad latent shape");
-    SCAIL_REQUIRE(chunk >= 2 && chunk <= (1 << 20), std::string("chunk must be at least 2 latent frames (every stage needs two frames of a chunk), got ") + std::to_string(chunk));
-    const StreamPlan plan = stream_plan(*h, chunk, hl, wl);
-    SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= plan.total() && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
-                  std::string("workspace too small or not 256-byte aligned (scail_vae_decode_stream_workspace_bytes): need ") +
-                      std::to_string(plan.total()) + " bytes, got " + std::to_string(workspace_bytes));
-    Arena a;
-    a.base = static_cast<char*>(workspace);
-    a.slot_bytes = plan.big;
-    a.n_small = 2; a.small_bytes = plan.small;
-    a.stream = stream;
-    a.trace = h->trace; a.trace_user = h->trace_user;
-    if (Tl <= chunk + 1) return decode_frames(h, a, latent, video, Tl, 0, Tl, hl, wl);       // one chunk: the launches of scail_vae_decode
-    a.head = 2;
-    a.carry = a.base + (NSLOT - 2) * plan.big + 2 * plan.small;
-    a.carry_bytes = plan.carry;
-    for (int64_t t0 = 0; t0 < Tl;) {
-        int64_t n = Tl - t0 < chunk ? Tl - t0 : chunk;
-        if (Tl - t0 - n == 1) ++n;                 // a remainder of one frame joins the last chunk: no stage ever sees fewer than two frames
-        a.later = t0 > 0;
-        a.carry_off = 0;
-        for (bool& u : a.used) u = false;
-        VAE_TRY(decode_frames(h, a, latent, video, Tl, t0, n, hl, wl));
-        SCAIL_REQUIRE(a.carry_off == plan.carry, "scail_vae_decode_stream: the chunk's causal convolutions do not match the carry plan");
-        t0 += n;
-    }
-    return 0;
+    VideoOut out;
+    out.f32 = video;
+    return decode_stream(__func__, h, latent, out, Tl, hl, wl, chunk, workspace, workspace_bytes, stream);
+}
+
+extern "C" int scail_vae_decode_stream_u8(scail_vae* h, const float* latent, uint8_t* frames, int64_t Tl, int64_t hl, int64_t wl,
+                                          int64_t chunk, void* workspace, int64_t workspace_bytes, void* stream) {
+    VideoOut out;
+    out.u8 = frames;
+    return decode_stream(__func__, h, latent, out, Tl, hl, wl, chunk, workspace, workspace_bytes, stream);
 }

@@ -173,3 +173,22 @@ class CVae:
         L.call("scail_vae_decode", self._h, z.data_ptr(), out.data_ptr(), Tl, h, w, ws.data_ptr(), ws.numel(),
                torch.cuda.current_stream().cuda_stream)
         return out
+
+    def decode_u8(self, z: torch.Tensor, chunk_frames=None) -> torch.Tensor:
+        """z fp32 (zc, Tl, h, w) -> the clip as the writers' pixels, uint8 (1 + 4 (Tl - 1), 8h, 8w, 3): ``decode`` with scail_frames_u8 as the last
+        launch (of each chunk) -- trunc(255 * clamp((x + 1) / 2, 0, 1)) of every value ``decode`` returns, and no fp32 video anywhere.
+        ``chunk_frames`` and the workspace: as in ``decode``."""
+        _, Tl, h, w = z.shape
+        T, H, W = 1 + 4 * (Tl - 1), 8 * h, 8 * w
+        if chunk_frames is not None:
+            chunk = int(chunk_frames)
+            ws = self._stream_workspace(chunk, h, w)
+            out = torch.empty(T, H, W, 3, device=z.device, dtype=torch.uint8)
+            L.call("scail_vae_decode_stream_u8", self._h, z.data_ptr(), out.data_ptr(), Tl, h, w, chunk, ws.data_ptr(), ws.numel(),
+                   torch.cuda.current_stream().cuda_stream)
+            return out
+        ws = self._workspace(T, H, W)
+        out = torch.empty(T, H, W, 3, device=z.device, dtype=torch.uint8)
+        L.call("scail_vae_decode_u8", self._h, z.data_ptr(), out.data_ptr(), Tl, h, w, ws.data_ptr(), ws.numel(),
+               torch.cuda.current_stream().cuda_stream)
+        return out

@@ -105,6 +105,13 @@ class SATVideoDiffusionEngine(nn.Module):
         return self.first_stage_model.decode(1.0 / self.scale_factor * z, chunk_frames=chunk_frames)
 
     @torch.no_grad()
+    def decode_first_stage_u8(self, z, chunk_frames=None):
+        """``decode_first_stage`` ending in the writers' pixels (an extension): uint8 (B, T, H, W, 3) on the device, WanVAE_.decode_u8."""
+        if self.first_stage_model is None:
+            raise RuntimeError("first stage (VAE) not built; pass build_first_stage: true in the model config")
+        return self.first_stage_model.decode_u8(1.0 / self.scale_factor * z, chunk_frames=chunk_frames)
+
+    @torch.no_grad()
     def encode_first_stage(self, x, batch=None, force_encode=False):
         """diffusion_video.py:311-331."""
         if not force_encode and self.latent_input:

@@ -59,6 +59,7 @@ SIGNATURES = {
     "scail_from_channels_last": [_p, _i64, _p, _p, _p, _i64, _i64, _f, _f, _p],
     "scail_to_channels_last_frames": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _p],
     "scail_from_channels_last_frames": [_p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _f, _f, _p],
+    "scail_frames_u8": [_p, _i64, _p, _i64, _i64, _i64, _i64, _i64, _p],
     "scail_attn_small": [_p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _f, _p, _p, _p, _i64, _p],
     "scail_mul_bf16": [_p, _p, _p, _i64, _p],
     "scail_row_affine": [_p, _p, _p, _p, _i64, _i64, _i64, _p],
@@ -106,6 +107,8 @@ SIGNATURES = {
     "scail_vae_decode": [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p],
     "scail_vae_decode_stream_workspace_bytes": [_p, _i64, _i64, _i64],
     "scail_vae_decode_stream": [_p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p],
+    "scail_vae_decode_u8": [_p, _p, _p, _i64, _i64, _i64, _p, _i64, _p],
+    "scail_vae_decode_stream_u8": [_p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p],
 }
 # return types other than the int status: every *_bytes query answers an int64_t, the destroy functions nothing
 RESTYPES = {"scail_dit_destroy": None, "scail_vae_destroy": None, **{n: _i64 for n in SIGNATURES if n.endswith("_bytes")}}
@@ -128,7 +131,8 @@ RESIZE_MAX_SCALE = 16
 ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- scail_vae_decode_stream, its workspace query, scail_to / from_channels_last_frames --
                          # and no existing call changed: still 8; load() fails on a library that lacks them; likewise the request
                          # preprocessing, scail_resize_crop_aa / scail_pose_half, and the convolution queries scail_conv3d_norm_fused_for /
-                         # scail_conv3d_kernel_name_for, and the GEMM query scail_gemm_kernel_name_for)
+                         # scail_conv3d_kernel_name_for, the GEMM query scail_gemm_kernel_name_for, and the uint8 output route,
+                         # scail_frames_u8 / scail_vae_decode_u8 / scail_vae_decode_stream_u8)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);

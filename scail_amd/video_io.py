@@ -311,11 +311,33 @@ def save_video_as_grid(video_batch: torch.Tensor, save_path: str, fps: float = 5
     return out
 
 
+def _save_multi_u8(video_batches: Sequence[torch.Tensor], save_dir: str, fps: float, key: str, ext: str) -> List[str]:
+    """save_multi_video_grid for uint8 (B, T, H, W, C) clips: one clip's frames are views of it; several clips are joined along W once per
+    batch entry ("h (n w) c") and the frames are views of that."""
+    shape = tuple(video_batches[0].shape)
+    if len(shape) != 5 or any(tuple(v.shape) != shape for v in video_batches):
+        raise ValueError(f"save_multi_video_grid: uint8 clips must all be (B, T, H, W, C) of one shape, got {[tuple(v.shape) for v in video_batches]}")
+    clips = [v.cpu().contiguous().numpy() for v in video_batches]
+    out = []
+    for i in range(shape[0]):
+        wide = clips[0][i] if len(clips) == 1 else np.concatenate([c[i] for c in clips], axis=2)       # T H (n W) C
+        p = os.path.join(save_dir, f"{key}_{i:06d}{ext}")
+        _write_frames(list(wide), p, fps)
+        out.append(p)
+    return out
+
+
 def save_multi_video_grid(video_batches: Sequence[torch.Tensor], save_dir: str, fps: float = 5, key: str = "0_output",
                           ext: str = ".webp") -> List[str]:
     """Several (B, T, C, H, W) clips side by side, frame layout "n c h w -> h (n w) c"
-    (reference save_multi_video_grid_and_mp4, :181-198): save_dir/<key>_000000<ext>."""
+    (reference save_multi_video_grid_and_mp4, :181-198): save_dir/<key>_000000<ext>.
+    Clips may instead be given as the pixels themselves, uint8 (B, T, H, W, C) (scail_frames_u8's output, ``cli.run(postprocess="hip")``): the
+    files are those of the float clips they were quantised from; no float conversion, and the frames handed to the writer are views."""
     os.makedirs(save_dir, exist_ok=True)
+    if all(v.dtype == torch.uint8 for v in video_batches):
+        return _save_multi_u8(video_batches, save_dir, fps, key, ext)
+    if any(v.dtype == torch.uint8 for v in video_batches):
+        raise ValueError("save_multi_video_grid: clips are either all float (B, T, C, H, W) or all uint8 (B, T, H, W, C)")
     multi = torch.stack([v.float().cpu() for v in video_batches], dim=2)           # B T N C H W
     out = []
     for i, mv in enumerate(multi):

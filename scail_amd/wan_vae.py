@@ -325,6 +325,20 @@ class WanVAE_(nn.Module):
         x = ops.conv3d_cl(x, W["decoder.head.2"], x.shape[:3])
         return ops.from_channels_last(x, 3).unsqueeze(0)
 
+    @torch.no_grad()
+    def decode_u8(self, z: torch.Tensor, scale=None, chunk_frames=None) -> torch.Tensor:
+        """z (1|-, zc, T, h, w) -> the clip as the file writers' pixels, uint8 (1, 1+4(T-1), 8h, 8w, 3) on the device: for every value v that
+        ``decode`` returns, trunc(255 * clamp((v + 1) / 2, 0, 1)) -- what sample_video.py:494 and the writers (:188 / :212) make of it -- written
+        by the decoder's last kernel, so no fp32 video exists.  C executor only; ``chunk_frames`` as in ``decode``."""
+        if z.dim() == 5:
+            assert z.shape[0] == 1
+            z = z[0]
+        if not self.use_c_exec:
+            raise NotImplementedError("decode_u8: the uint8 output route exists in the C executor only (use_c_exec); the layer-by-layer path "
+                                      "returns the fp32 video")
+        self.prepare()
+        return self._c().decode_u8(z.float().to(next(self.parameters()).device).contiguous(), chunk_frames=chunk_frames).unsqueeze(0)
+
 
 class WanVAE:
     """Reference-compatible wrapper (wan_vae.py:619-666)."""
@@ -349,3 +363,8 @@ class WanVAE:
     def decode(self, zs, chunk_frames=None):
         """zs: iterable of [z, T, h, w] -> float video clamped to [-1, 1] (wan_vae.py:659-666); ``chunk_frames``: WanVAE_.decode."""
         return torch.cat([self.model.decode(u.unsqueeze(0), chunk_frames=chunk_frames).float().clamp_(-1, 1) for u in zs], dim=0)
+
+    def decode_u8(self, zs, chunk_frames=None):
+        """zs: iterable of [z, T, h, w] -> uint8 (B, T, H, W, 3), the quantised ``decode`` (the clamp to [-1, 1] changes no pixel: WanVAE_.decode_u8)."""
+        clips = [self.model.decode_u8(u.unsqueeze(0), chunk_frames=chunk_frames) for u in zs]
+        return clips[0] if len(clips) == 1 else torch.cat(clips, dim=0)         # (one clip is returned as it is: torch.cat would copy it)
