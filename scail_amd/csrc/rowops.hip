@@ -3,7 +3,9 @@
 // timestep embedding, tiny linears, AdaLN tables, patchify / unpatchify, CFG+Euler.
 // One 256-thread workgroup per row for the norm kernels; every bf16 access is a 16-byte vector.
 #include "common.h"
+#include <algorithm>
 #include <atomic>
+#include <cstring>
 
 #define ROW_THREADS 256
 #define ROW_MAXV 3  // D <= 256 * 8 * 3 = 6144 kept in registers
@@ -228,7 +230,7 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_wave_kernel(
     const float* __restrict__ w, const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
     int64_t rows, int64_t rows_per_batch, int head_dim, float eps, float out_scale, int slab_w, int64_t slab_stride) {
     constexpr int D = 512 * CPL;
-    extern __shared__ __attribute__((aligned(16))) float prm[];       // the norm weight times out_scale: [D]
+    extern __shared__ __attribute__((aligned(16))) float prm[];       // the norm weight as given: [D] (out_scale multiplies each result element below)
     for (int i4 = threadIdx.x; i4 < D / 4; i4 += 256) *reinterpret_cast<float4*>(prm + i4 * 4) = *reinterpret_cast<const float4*>(w + i4 * 4);
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -610,25 +612,94 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 static std::atomic<int> g_row_wave{1};   // option state: atomic (set by one thread, read by every launching thread)
 int scail_row_wave_enable(int on) { g_row_wave = on != 0; return 0; }
 
-// returns -1 when the wave kernels do not cover this D (the caller launches the block kernel), else the launch status
+// ------------------------------------------------------------------------------------------------
+// Which kernel a LayerNorm / RMSNorm (+ RoPE) call runs.  row_choose is the ONE statement of it: ln_launch and rmsnorm_rope_launch launch
+// what it says, and the host-side query scail_row_kernel_name_for is a projection of the same answer.  Nothing else reads option "row_wave".
+// ------------------------------------------------------------------------------------------------
+struct RowChoice {
+    bool wave = false;           // one wave per row (ln_wave_kernel / rmsnorm_rope_wave_kernel) instead of one workgroup per row
+    int cpl = 0;                 // wave form: 16-byte chunks per lane, D = 512 * cpl
+    bool hd128 = false;          // RMSNorm + RoPE wave form: head_dim == 128, the lane's (cos, sin) pairs loaded once per row
+    int64_t wgs_per_batch = 0;   // LayerNorm wave form: workgroups dealt to one batch element
+    int64_t grid = 0;            // workgroups; -1: the wave form's grid was asked for and the device's CU count is not available
+};
+
+// form: SCAIL_ROW_*; rows = n_batch * rows_out (the RMSNorm forms have no batch split: only the product counts).  want_grid == false
+// answers the kernel alone, which needs no device; the grid of a wave form is sized by the device's compute units.
+static RowChoice row_choose(int form, int64_t n_batch, int64_t rows_out, int64_t D, int64_t head_dim, bool want_grid) {
+    RowChoice c;
+    const int64_t rows = n_batch * rows_out;
+    c.grid = rows;                                     // the block kernels: one workgroup per row
+    const bool ln = form == SCAIL_ROW_LN_MODULATE || form == SCAIL_ROW_LN_AFFINE;
+    // LayerNorm: the wave form wherever it covers D.  RMSNorm: with RoPE the wave form wins (0.455 -> 0.41 ms at config 2: the (cos, sin) pairs
+    // once per row instead of per chunk); without, the block kernel is already at the pass's plateau (0.367 against 0.383 ms;
+    // profiles/r04_row_pass_probe.log)
+    if (!g_row_wave || D % 512 != 0 || rows <= 0 || !(ln || form == SCAIL_ROW_RMSNORM_ROPE)) return c;
+    const int cpl = (int)(D / 512);
+    if (cpl != 3 && cpl != 4 && cpl != 8 && cpl != 10 && cpl != 12) return c;       // the instantiations
+    c.wave = true;
+    c.cpl = cpl;
+    c.hd128 = !ln && head_dim == 128;
+    c.grid = 0;
+    if (!want_grid) return c;
+    const int cus = scail_device_cus();
+    if (cus <= 0) { c.grid = -1; return c; }
+    if (ln) {
+        // persistent workgroups: about three per compute unit (157 VGPRs, 40 KB of LDS), dealt evenly to the batch elements
+        c.wgs_per_batch = std::max<int64_t>(1, std::min<int64_t>((rows_out + 3) / 4, (3 * cus + n_batch - 1) / n_batch));
+        c.grid = n_batch * c.wgs_per_batch;
+    } else {
+        c.grid = std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 3 * (int64_t)cus));
+    }
+    return c;
+}
+
+// The choice in words: the kernel's template name with the arguments of the instantiation
+static std::string row_choice_name(int form, const RowChoice& c) {
+    const bool ln = form == SCAIL_ROW_LN_MODULATE || form == SCAIL_ROW_LN_AFFINE;
+    const std::string mode = form == SCAIL_ROW_LN_MODULATE ? "0" : "1";
+    if (!c.wave) return ln ? "ln_kernel<" + mode + ">" : "rmsnorm_rope_kernel";
+    if (ln) return "ln_wave_kernel<" + mode + ", " + std::to_string(c.cpl) + ">";
+    return "rmsnorm_rope_wave_kernel<" + std::to_string(c.cpl) + (c.hd128 ? ", true>" : ", false>");
+}
+
+extern "C" int scail_row_kernel_name_for(int form, int64_t n_batch, int64_t rows_out, int64_t D, int64_t head_dim, char* buf, int64_t len,
+                                         int64_t* workgroups) {
+    SCAIL_REQUIRE(buf != nullptr, "null argument");
+    SCAIL_REQUIRE(form >= SCAIL_ROW_LN_MODULATE && form <= SCAIL_ROW_COPY, "unknown form");
+    SCAIL_REQUIRE(D > 0 && D % 8 == 0 && D <= ROW_THREADS * 8 * ROW_MAXV, "D must be a multiple of 8 and <= 6144");
+    SCAIL_REQUIRE(n_batch >= 0 && rows_out >= 0, "negative row count");
+    SCAIL_REQUIRE(form < SCAIL_ROW_RMSNORM || (head_dim > 0 && head_dim % 8 == 0 && D % head_dim == 0), "head_dim must be a multiple of 8 dividing D");
+    const RowChoice c = row_choose(form, n_batch, rows_out, D, head_dim, workgroups != nullptr);
+    if (c.grid < 0) return 2;                           // (scail_device_cus left the message)
+    const std::string name = row_choice_name(form, c);
+    SCAIL_REQUIRE((int64_t)name.size() < len, "buffer too small");
+    std::memcpy(buf, name.c_str(), name.size() + 1);
+    if (workgroups != nullptr) *workgroups = c.grid;
+    return 0;
+}
+
 template <int MODE>
-static int ln_wave_launch(const scail_bf16* x, int64_t ldx, scail_bf16* y, int64_t ldy, const float* p0, const float* p1, int64_t mod_stride,
-                          int64_t rows_out, int64_t src_rows_per_batch, int64_t src_row_offset, int64_t rows, int64_t D, float eps, void* stream) {
-    if (!g_row_wave || D % 512 != 0 || rows_out <= 0 || rows % rows_out != 0) return -1;
+static int ln_launch(const scail_bf16* x, int64_t ldx, scail_bf16* y, int64_t ldy, const float* p0, const float* p1, int64_t mod_stride,
+                     int64_t n_batch, int64_t rows_out, int64_t src_rows_per_batch, int64_t src_row_offset, int64_t D, float eps, void* stream) {
+    const RowChoice c = row_choose(MODE == 0 ? SCAIL_ROW_LN_MODULATE : SCAIL_ROW_LN_AFFINE, n_batch, rows_out, D, 0, true);
+    if (c.grid < 0) return 2;
+    if (!c.wave) {
+        hipLaunchKernelGGL(ln_kernel<MODE>, dim3((unsigned)c.grid), dim3(ROW_THREADS), 0, (hipStream_t)stream, x, ldx, y, ldy, p0, p1, mod_stride,
+                           rows_out, src_rows_per_batch, src_row_offset, (int)D, eps);
+        return scail_check_launch(MODE == 0 ? "ln_modulate" : "layernorm_affine");
+    }
 #define LN_WAVE(CPL_)                                                                                                                  \
     case CPL_:                                                                                                                         \
-        return scail_launch_lds<ln_wave_kernel<MODE, CPL_>>("ln_wave", 2 * 512 * CPL_ * 4, dim3((unsigned)(n_batch * wpb)), dim3(256), 2 * 512 * CPL_ * 4, stream, \
-                                                            x, ldx, y, ldy, p0, p1, mod_stride, rows_out, src_rows_per_batch, src_row_offset, (int)wpb, eps);
-    // persistent workgroups: about three per compute unit (157 VGPRs, 40 KB of LDS), dealt evenly to the batch elements
-    const int64_t n_batch = rows / rows_out;
-    const int cus = scail_device_cus();
-    if (cus <= 0) return 2;
-    const int64_t wpb = std::max<int64_t>(1, std::min<int64_t>((rows_out + 3) / 4, (3 * cus + n_batch - 1) / n_batch));
-    switch (D / 512) {
+        return scail_launch_lds<ln_wave_kernel<MODE, CPL_>>("ln_wave", 2 * 512 * CPL_ * 4, dim3((unsigned)c.grid), dim3(256), 2 * 512 * CPL_ * 4, stream, \
+                                                            x, ldx, y, ldy, p0, p1, mod_stride, rows_out, src_rows_per_batch, src_row_offset, (int)c.wgs_per_batch, eps);
+    switch (c.cpl) {
         LN_WAVE(3) LN_WAVE(4) LN_WAVE(8) LN_WAVE(10) LN_WAVE(12)
-        default: return -1;
+        default: break;
     }
 #undef LN_WAVE
+    scail_set_error("layernorm: no wave kernel for the choice " + row_choice_name(MODE == 0 ? SCAIL_ROW_LN_MODULATE : SCAIL_ROW_LN_AFFINE, c));
+    return 2;
 }
 
 extern "C" int scail_ln_modulate(const scail_bf16* x, int64_t ldx, scail_bf16* y, int64_t ldy,
@@ -640,12 +711,7 @@ extern "C" int scail_ln_modulate(const scail_bf16* x, int64_t ldx, scail_bf16* y
     SCAIL_REQUIRE(aligned16(x) && aligned16(y) && aligned16(shift) && aligned16(scale), "pointers must be 16-byte aligned");
     const int64_t rows = n_batch * rows_out;
     if (rows == 0) return 0;
-    if (int rc = ln_wave_launch<0>(x, ldx, y, ldy, shift, scale, mod_stride, rows_out, src_rows_per_batch, src_row_offset, rows, D, eps, stream); rc >= 0)
-        return rc;
-    hipLaunchKernelGGL(ln_kernel<0>, dim3((unsigned)rows), dim3(ROW_THREADS), 0, (hipStream_t)stream, x, ldx,
-                       y, ldy, shift, scale, mod_stride, rows_out, src_rows_per_batch, src_row_offset,
-                       (int)D, eps);
-    return scail_check_launch("ln_modulate");
+    return ln_launch<0>(x, ldx, y, ldy, shift, scale, mod_stride, n_batch, rows_out, src_rows_per_batch, src_row_offset, D, eps, stream);
 }
 
 extern "C" int scail_layernorm_affine(const scail_bf16* x, int64_t ldx, scail_bf16* y, int64_t ldy,
@@ -655,10 +721,7 @@ extern "C" int scail_layernorm_affine(const scail_bf16* x, int64_t ldx, scail_bf
     SCAIL_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "strides must keep 16-byte alignment");
     SCAIL_REQUIRE(aligned16(x) && aligned16(y) && aligned16(w) && aligned16(b), "pointers must be 16-byte aligned");
     if (rows == 0) return 0;
-    if (int rc = ln_wave_launch<1>(x, ldx, y, ldy, w, b, 0, rows, rows, 0, rows, D, eps, stream); rc >= 0) return rc;
-    hipLaunchKernelGGL(ln_kernel<1>, dim3((unsigned)rows), dim3(ROW_THREADS), 0, (hipStream_t)stream, x, ldx,
-                       y, ldy, w, b, (int64_t)0, rows, rows, (int64_t)0, (int)D, eps);
-    return scail_check_launch("layernorm_affine");
+    return ln_launch<1>(x, ldx, y, ldy, w, b, 0, 1, rows, rows, 0, D, eps, stream);
 }
 
 extern "C" int scail_rmsnorm_rope(const scail_bf16* x, int64_t ldx, scail_bf16* y, int64_t ldy,
@@ -681,30 +744,30 @@ static int rmsnorm_rope_launch(const scail_bf16* x, int64_t ldx, scail_bf16* y, 
     SCAIL_REQUIRE(slab_w == 0 || (slab_w % 8 == 0 && D % slab_w == 0 && ldy >= slab_w && slab_stride % 8 == 0 && slab_stride >= (rows - 1) * ldy + slab_w),
                   "slab width must be a multiple of 8 dividing D, slab row stride >= slab width, slab stride a multiple of 8 that holds rows of that stride");
     if (rows == 0) return 0;
-    // with RoPE the wave form wins (0.455 -> 0.41 ms at config 2: the (cos, sin) pairs once per row instead of per chunk); without, the block
-    // kernel is already at the pass's plateau (0.367 against 0.383 ms; profiles/r04_row_pass_probe.log)
-    if (g_row_wave && w != nullptr && cos_tab != nullptr && D % 512 == 0) {
-        const int cus = scail_device_cus();
-        if (cus <= 0) return 2;
-        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 3 * (int64_t)cus));
+    const int form = w == nullptr ? SCAIL_ROW_COPY : cos_tab != nullptr ? SCAIL_ROW_RMSNORM_ROPE : SCAIL_ROW_RMSNORM;
+    const RowChoice c = row_choose(form, 1, rows, D, head_dim, true);
+    if (c.grid < 0) return 2;
+    if (c.wave) {
 #define RR_WAVE(CPL_)                                                                                                                \
     case CPL_: {                                                                                                                     \
         constexpr int lds_ = 512 * CPL_ * 4;                                                                                         \
-        if (head_dim == 128)                                                                                                         \
-            hipLaunchKernelGGL((rmsnorm_rope_wave_kernel<CPL_, true>), dim3(grid), dim3(256), lds_, (hipStream_t)stream, x, ldx, y,  \
+        if (c.hd128)                                                                                                                 \
+            hipLaunchKernelGGL((rmsnorm_rope_wave_kernel<CPL_, true>), dim3((unsigned)c.grid), dim3(256), lds_, (hipStream_t)stream, x, ldx, y,  \
                                ldy, w, cos_tab, sin_tab, rows, rows_per_batch, (int)head_dim, eps, out_scale, (int)slab_w, slab_stride); \
         else                                                                                                                         \
-            hipLaunchKernelGGL((rmsnorm_rope_wave_kernel<CPL_, false>), dim3(grid), dim3(256), lds_, (hipStream_t)stream, x, ldx, y, \
+            hipLaunchKernelGGL((rmsnorm_rope_wave_kernel<CPL_, false>), dim3((unsigned)c.grid), dim3(256), lds_, (hipStream_t)stream, x, ldx, y, \
                                ldy, w, cos_tab, sin_tab, rows, rows_per_batch, (int)head_dim, eps, out_scale, (int)slab_w, slab_stride); \
         return scail_check_launch("rmsnorm_rope");                                                                                   \
     }
-        switch (D / 512) {
+        switch (c.cpl) {
             RR_WAVE(3) RR_WAVE(4) RR_WAVE(8) RR_WAVE(10) RR_WAVE(12)
             default: break;
         }
 #undef RR_WAVE
+        scail_set_error("rmsnorm_rope: no wave kernel for the choice " + row_choice_name(form, c));
+        return 2;
     }
-    hipLaunchKernelGGL(rmsnorm_rope_kernel, dim3((unsigned)rows), dim3(ROW_THREADS), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(rmsnorm_rope_kernel, dim3((unsigned)c.grid), dim3(ROW_THREADS), 0, (hipStream_t)stream,
                        x, ldx, y, ldy, w, cos_tab, sin_tab, rows_per_batch, (int)D, (int)head_dim, eps, out_scale, (int)slab_w, slab_stride);
     return scail_check_launch("rmsnorm_rope");
 }

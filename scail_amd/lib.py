@@ -23,6 +23,7 @@ SIGNATURES = {
     "scail_rmsnorm_rope": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _f, _p],
     "scail_rmsnorm_rope_scaled": [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _f, _f, _p],
     "scail_rmsnorm_rope_slabs": [_p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _f, _f, _p],
+    "scail_row_kernel_name_for": [_i, _i64, _i64, _i64, _i64, _p, _i64, _p],
     "scail_slabs_to_rows": [_p, _i64, _i64, _p, _i64, _i64, _i64, _p],
     "scail_transpose_v": [_p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p],
     "scail_flash_attn_bf16": [_p, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64,
@@ -122,6 +123,8 @@ ABLATIONS = LIB_PATH.endswith("_abl.so")
 
 EPI_BIAS, EPI_GELU_TANH, EPI_GELU_ERF, EPI_RESID = 0, 1, 2, 3
 ACT_NONE, ACT_SILU, ACT_GELU_TANH = 0, 1, 2
+# include/scail_hip.h SCAIL_ROW_*: the call scail_row_kernel_name_for is asked about
+ROW_LN_MODULATE, ROW_LN_AFFINE, ROW_RMSNORM, ROW_RMSNORM_ROPE, ROW_COPY = 0, 1, 2, 3, 4
 # include/scail_dit.h SCAIL_DIT_FP8_*: the per-token GEMMs of a block that scail_dit_enable_fp8 switches to fp8
 FP8_GEMMS = {"qkv": 1, "o": 2, "cq": 4, "co": 8, "w1": 16, "w2": 32}
 FP8_ALL = 63
@@ -131,8 +134,9 @@ RESIZE_MAX_SCALE = 16
 ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- scail_vae_decode_stream, its workspace query, scail_to / from_channels_last_frames --
                          # and no existing call changed: still 8; load() fails on a library that lacks them; likewise the request
                          # preprocessing, scail_resize_crop_aa / scail_pose_half, and the convolution queries scail_conv3d_norm_fused_for /
-                         # scail_conv3d_kernel_name_for, the GEMM query scail_gemm_kernel_name_for, and the uint8 output route,
-                         # scail_frames_u8 / scail_vae_decode_u8 / scail_vae_decode_stream_u8)
+                         # scail_conv3d_kernel_name_for, the GEMM query scail_gemm_kernel_name_for, the uint8 output route,
+                         # scail_frames_u8 / scail_vae_decode_u8 / scail_vae_decode_stream_u8, and the row-kernel query
+                         # scail_row_kernel_name_for)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);
