@@ -246,7 +246,8 @@ int scail_dit_profile_read(scail_dit* h, int category, double* ms_total, int64_t
  * scail_dit_enable_fp8 quantizes the selected per-layer matrices from the handle's bf16 weights into the caller's device buffer
  * buf (>= scail_dit_fp8_weight_bytes(h, which) bytes, 256-byte aligned; it must outlive the fp8 use), enqueued on `stream`; call it
  * outside stream capture.  A selected shape outside scail_gemm_fp8's limits (N, K multiples of 128) fails it up front, naming the shape.
- * which == 0 or buf == NULL: back to bf16.  While fp8 is enabled the workspace queries (scail_dit_workspace_bytes, _block_, _sample_)
+ * which == 0 or buf == NULL: back to bf16.  Which of the quantised matrices run in fp8 can be narrowed per layer
+ * (scail_dit_fp8_select_layers below).  While fp8 is enabled the workspace queries (scail_dit_workspace_bytes, _block_, _sample_)
  * include the e4m3 copy of a GEMM input, and scail_dit_step_sp / scail_dit_block_sp return an error (sequence-parallel ranks: bf16 only).
  * scail_dit_fp8_weight_bytes: -1 for a null handle or an unknown bit.
  */
@@ -259,6 +260,40 @@ int scail_dit_profile_read(scail_dit* h, int category, double* ms_total, int64_t
 #define SCAIL_DIT_FP8_ALL 63u
 int64_t scail_dit_fp8_weight_bytes(const scail_dit* h, uint32_t which);
 int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int64_t bytes, void* stream);
+
+/*
+ * Per-layer fp8 selection and the on-device GEMM error probe (both opt-in, both on top of scail_dit_enable_fp8).
+ * With per-token and per-channel scales one outlier channel of a GEMM input flushes the rest of that row to zero; the damage is local
+ * to a few (layer, GEMM) pairs.  The probe finds them on the request's own activations, the selection keeps only them in bf16.
+ *
+ * scail_dit_fp8_select_layers: masks[num_layers] (host array, copied), masks[i] = the SCAIL_DIT_FP8_* bits in force in layer i.  Every
+ *   masks[i] must be a subset of the mask given to scail_dit_enable_fp8 (only a quantised matrix can be selected): a bit outside it is an
+ *   error that names the layer and the bit.  Nothing is re-quantised and the weight buffer is not touched; the executor decides per
+ *   (layer, GEMM) which of the two kernels runs.  masks == NULL: uniform again (the enabled mask in every layer).  scail_dit_enable_fp8
+ *   resets the selection (and turns the probe off).  The workspace queries keep using the enabled (union) mask.  SCAIL_DIT_CFG_PAIR and the
+ *   last-layer row pruning stay exact under any selection: they only need every GEMM to compute a row from that row alone.
+ *
+ * scail_dit_fp8_probe: table = device fp64 [num_layers][6][4], zeroed by the caller; scratch = scail_dit_fp8_probe_bytes(h, B, Ltok)
+ *   bytes of device memory, 256-byte aligned (two bf16 buffers of B * Ltok rows x the widest quantised N); both must outlive the probe.
+ *   table == NULL turns the probe off.  While it is on, every single-rank call (scail_dit_step, _chars, scail_dit_block, scail_dit_sample*)
+ *   does, for each GEMM whose weight is quantised -- in force or not --, on exactly the rows the real GEMM runs on:
+ *     1. Y16 = bf16(x W^T + b) with scail_gemm_bf16, plain bias epilogue, into scratch;
+ *     2. Y8 = the same with scail_quant_fp8_rows + scail_gemm_fp8, plain bias epilogue, into scratch;
+ *     3. scail_rel_err_rows(Y16, Y8) into table[layer][g] (g = the bit index of SCAIL_DIT_FP8_*):
+ *        [0] += sum |Y8 - Y16|^2, [1] += sum |Y16|^2, [2] = max over rows of the row's ratio, [3] += rows;
+ *     4. the layer's real GEMM in bf16.
+ *   So the network's result is the bf16 network's bit for bit and every probed activation is clean (no fp8 error upstream of it).
+ *   sqrt([0] / [1]) is the relative error of that fp8 GEMM, sqrt([2]) its worst token's.  What is measured is the output of the
+ *   bias-only GEMM: not what GELU makes of it, not the hidden state after the gated residual.  Cost: two extra GEMMs, one quantisation and
+ *   one pass over both results per probed GEMM -- meant for ONE evaluation per request, after which the caller reads the table, selects
+ *   layers and turns the probe off.  Nothing synchronises; the caller reads the table after the stream has finished.  A call with more
+ *   rows (B * Ltok) than the scratch covers is refused before anything is enqueued.  Needs fp8 enabled; the sequence-parallel calls
+ *   refuse such a handle as before.  Not meant for stream capture (scail_rel_err_rows keeps its partial sums in library memory).
+ * scail_dit_fp8_probe_bytes: -1 for a null handle or a bad shape; 0 while no GEMM is quantised.
+ */
+int scail_dit_fp8_select_layers(scail_dit* h, const uint32_t* masks);
+int64_t scail_dit_fp8_probe_bytes(const scail_dit* h, int64_t B, int64_t Ltok);
+int scail_dit_fp8_probe(scail_dit* h, double* table, void* scratch, int64_t scratch_bytes);
 
 /*
  * The whole Euler sampling loop of RFSampler (sampling.py:920-982) with VanillaCFG (guiders.py:41-57) for one request:

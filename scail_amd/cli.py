@@ -230,14 +230,50 @@ def build_engine(cfg, load=None, device="cuda"):
     return engine
 
 
+def fp8_max_error_arg(value, gemm_precision):
+    """``--fp8-max-error`` checked against the network's GEMM precision: a number >= 0 (inf allowed), and only with fp8 GEMMs."""
+    if value is None:
+        return None
+    value = float(value)
+    if not value >= 0.0:
+        raise ValueError(f"--fp8-max-error must be a number >= 0, got {value}")
+    if gemm_precision != "fp8":
+        raise ValueError("--fp8-max-error needs --gemm-precision fp8 (or gemm_precision: fp8 in the network's yaml): it chooses which fp8 GEMMs to keep")
+    return value
+
+
+def format_fp8_table(cal, max_rel_err):
+    """The probe's result as text: one row per layer, one column per GEMM, then the (layer, GEMM) pairs left in bf16."""
+    names = list(lib.FP8_GEMMS)
+    rel, masks = cal["rel_err"], cal["masks"]
+    out = [f"fp8 probe: relative error of each fp8 GEMM against its bf16 twin (first evaluation), threshold {max_rel_err:g}",
+           "layer " + " ".join(f"{n:>8}" for n in names)]
+    for i in range(rel.shape[0]):
+        out.append(f"{i:5d} " + " ".join(f"{float(rel[i, g]):8.2e}" for g in range(len(names))))
+    left = [f"({i}, {n})" for i in range(rel.shape[0]) for g, n in enumerate(names) if (cal["enabled"] >> g) & 1 and not (masks[i] >> g) & 1]
+    out.append("left in bf16: " + (", ".join(left) if left else "none"))
+    return "\n".join(out)
+
+
+def _calibrate(engine, c, uc, shape, steps, fp8_max_error):
+    """--fp8-max-error: once per request, before sampling (its noise comes from a generator of its own)"""
+    if fp8_max_error is None:
+        return
+    cal = engine.calibrate_fp8(c, uc, shape, fp8_max_error, num_steps=steps)
+    print(format_fp8_table(cal, fp8_max_error))
+
+
 def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frames=None, engine=None, tile_frames=None, tile_overlap=None,
-        vae_chunk_frames=None, postprocess="torch"):
-    """``postprocess``: "torch" (default) returns the video as fp32 (B, 3, T, H, W) in [0, 1]; "hip" returns it as the file writers' pixels,
+        vae_chunk_frames=None, postprocess="torch", fp8_max_error=None):
+    """``fp8_max_error`` (fp8 networks only): probe the request's first evaluation and keep in bf16 every (layer, GEMM) whose fp8 result is
+    further than this from bf16 (engine.calibrate_fp8).
+    ``postprocess``: "torch" (default) returns the video as fp32 (B, 3, T, H, W) in [0, 1]; "hip" returns it as the file writers' pixels,
     uint8 (B, T, H, W, 3) on the device, written by the VAE decoder's last kernel (engine.decode_first_stage_u8; needs a GPU)."""
     if postprocess not in POSTPROCESS_ROUTES:
         raise ValueError(f"postprocess must be one of {POSTPROCESS_ROUTES}, got {postprocess!r}")
     if postprocess == "hip" and not torch.cuda.is_available():
         raise lib.ScailHipError("postprocess='hip' writes the uint8 frames with the library's kernels and needs a GPU; there is no host fallback")
+    fp8_max_error = fp8_max_error_arg(fp8_max_error, cfg["model"]["network_config"].get("params", {}).get("gemm_precision", "bf16"))
     engine = engine or build_engine(cfg, load, device)
     H, W = cfg.get("args", {}).get("sampling_image_size", [512, 896])
     net = engine.network
@@ -254,7 +290,7 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
             raise ValueError(f"a pose clip longer than one window needs 4n + 1 frames (the causal VAE's frame groups), got {n_pix}")
         Tt, overlap = tile_args(tile_frames, tile_overlap, net.num_frames)
         tiles = plan_tiles((n_pix - 1) // 4 + 1, Tt, overlap)
-        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames, postprocess)
+        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames, postprocess, fp8_max_error)
     pose_lat = engine.encode_first_stage(req["pose"].unsqueeze(0), None, force_encode=True)   # already half resolution (:350-351)
     ref_concat = ref_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)      # B C T H W -> B T C H W
     pose_latent = pose_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)
@@ -263,6 +299,7 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
                   concat_smpl_render=pose_latent, image_clip_features=req["clip"].to(torch.bfloat16))
     c = dict(crossattn=req["context"], **shared)
     uc = dict(crossattn=req["uncond_context"], **shared)
+    _calibrate(engine, c, uc, (T, C, h, w), steps, fp8_max_error)
     torch.manual_seed(seed)
     z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps)
     return _finish(engine, z, t0, vae_chunk_frames, postprocess)
@@ -285,7 +322,7 @@ def _finish(engine, z, t0, vae_chunk_frames=None, postprocess="torch"):
     return video, z, time.perf_counter() - t0
 
 
-def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames=None, postprocess="torch"):
+def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames=None, postprocess="torch", fp8_max_error=None):
     """A pose clip longer than one window (an extension, see the module docstring): RFSamplerLong with the configured sampler's
     parameters over ``tiles``; every window's pose frames [4 start, 4 (start + Tt - 1)] are VAE-encoded on their own (the causal VAE treats
     a window's first frame as a clip's first frame, which is how ``smpl_tiled[:, k]`` is used); noise and decode for the whole latent."""
@@ -306,6 +343,7 @@ def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_ch
     params["device"] = device
     plain, engine.sampler = engine.sampler, S.RFSamplerLong(**params)
     try:
+        _calibrate(engine, c, uc, (T, C, h, w), steps, fp8_max_error)       # the first window
         torch.manual_seed(seed)
         z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, tile_indices=tiles)
     finally:
@@ -338,6 +376,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--gemm-precision", choices=("bf16", "fp8"), default=None,
                     help="precision of the six per-token GEMMs of every block (default: the config's, bf16); fp8 = e4m3 with per-token / "
                          "per-channel scales, single GPU")
+    ap.add_argument("--fp8-max-error", type=float, default=None,
+                    help="with fp8 GEMMs: before sampling, run the request's first network evaluation through the executor's error probe "
+                         "and keep in bf16 every (layer, GEMM) whose fp8 result is further than this (relative error against its bf16 "
+                         "twin) from bf16; prints the table.  No measured table of a real checkpoint exists yet: choose the value from "
+                         "the printed table of your own weights")
     ap.add_argument("--tile-frames", type=int, default=None,
                     help="pixel frames per temporal window, 4n + 1 (default: the network's num_frames); a pose clip with more frames is sampled "
                          "in overlapping windows (RFSamplerLong), an extension of the reference CLI; such a clip needs 4n + 1 frames")
@@ -381,6 +424,10 @@ def main(argv=None):
     if a.gemm_precision is not None:
         cfg = copy.deepcopy(cfg)
         cfg["model"]["network_config"].setdefault("params", {})["gemm_precision"] = a.gemm_precision
+    try:                                                                # an argument error before any model is built
+        tk["fp8_max_error"] = fp8_max_error_arg(a.fp8_max_error, cfg["model"]["network_config"].get("params", {}).get("gemm_precision", "bf16"))
+    except ValueError as e:
+        ap.error(str(e))
     lines = [(r, i) for i, r in enumerate(a.request)] + (list(read_from_file(a.input_file)) if a.input_file else [])
     if lines:
         import os

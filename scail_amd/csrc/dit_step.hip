@@ -36,6 +36,12 @@ struct scail_dit {
     uint32_t fp8 = 0;
     struct Fp8W { const uint8_t* q; const float* s; };
     std::vector<std::array<Fp8W, 6>> fp8w;
+    // scail_dit_fp8_select_layers: per layer, the subset of `fp8` in force (empty: `fp8` in every layer)
+    std::vector<uint32_t> fp8_sel;
+    // scail_dit_fp8_probe: the caller's fp64 table [layers][6][4] (null: off) and the two bf16 result buffers of probe_rows x fp8_n() each
+    double* probe_table = nullptr;
+    scail_bf16 *probe_y16 = nullptr, *probe_y8 = nullptr;
+    int64_t probe_rows = 0;
 };
 
 namespace {
@@ -175,6 +181,35 @@ static int64_t fp8_k(const scail_dit* h) {
         }
     return kmax;
 }
+// the widest output of a quantised GEMM (the probe's result buffers)
+static int64_t fp8_n(const scail_dit* h) {
+    int64_t nmax = 0;
+    for (int g = 0; g < G_COUNT; ++g)
+        if (h->fp8 & (1u << g)) {
+            int64_t N, K;
+            gemm_shape(h->cfg, g, &N, &K);
+            nmax = std::max(nmax, N);
+        }
+    return nmax;
+}
+// whether GEMM g of layer i runs in fp8: quantised by scail_dit_enable_fp8 and not deselected by scail_dit_fp8_select_layers
+static bool fp8_in_force(const scail_dit* h, int64_t i, int g) {
+    return ((h->fp8_sel.empty() ? h->fp8 : h->fp8_sel[i]) & (1u << g)) != 0;
+}
+static void probe_off(scail_dit* h) {
+    h->probe_table = nullptr;
+    h->probe_y16 = h->probe_y8 = nullptr;
+    h->probe_rows = 0;
+}
+// a call that runs GEMMs on `rows` rows while the probe is on: refused, before anything is enqueued, when the probe's buffers are smaller
+static int probe_check(const scail_dit* h, int64_t rows) {
+    if (h->probe_table != nullptr && rows > h->probe_rows) {
+        scail_set_error("scail_dit_fp8_probe: this call runs GEMMs on " + std::to_string(rows) + " rows, the probe's scratch covers " +
+                        std::to_string(h->probe_rows) + " (scail_dit_fp8_probe_bytes)");
+        return 1;
+    }
+    return 0;
+}
 
 // ---- workspaces: every layout is stated once; the *_workspace_bytes query and the call that checks it read the same struct ----
 struct BlockBufs {
@@ -245,12 +280,21 @@ static SampleWs sample_ws(int64_t step, int64_t Tv, int64_t H, int64_t W, int64_
     return {step, step + pair, step + 2 * pair, step + 2 * pair + align256(Tden * F * 4)};
 }
 
-// GEMM g of layer i: scail_gemm_bf16, or (SCAIL_DIT_FP8_* bit g enabled) the rows of x quantized to e4m3 into the block's scratch and
-// scail_gemm_fp8 on the layer's e4m3 weight; the same epilogue either way
+// GEMM g of layer i: scail_gemm_bf16, or (SCAIL_DIT_FP8_* bit g in force in layer i) the rows of x quantized to e4m3 into the block's
+// scratch and scail_gemm_fp8 on the layer's e4m3 weight; the same epilogue either way.  While the probe is on, a GEMM whose weight is
+// quantised (in force or not) first runs twice on these very rows with the plain bias epilogue -- bf16 and fp8, into the probe's two
+// buffers --, their distance goes to table[i][g], and the real GEMM then runs in bf16.
 static int dit_gemm(scail_dit* h, int64_t i, int g, const BlockBufs& bf, const scail_bf16* x, int64_t lda, const float* bias, scail_bf16* y,
                     int64_t ldc, int64_t M, int64_t N, int64_t K, int epi, const scail_bf16* resid, int64_t ldr, const float* gate, int64_t gs,
                     int64_t rpb, void* stream) {
-    if (h->fp8 & (1u << g)) {
+    const bool quantised = (h->fp8 & (1u << g)) != 0;
+    if (quantised && h->probe_table != nullptr) {
+        const scail_dit::Fp8W& f = h->fp8w[i][g];
+        DIT_TRY(scail_gemm_bf16(x, lda, gemm_weight(h->layers[i], g), bias, h->probe_y16, N, M, N, K, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
+        DIT_TRY(scail_quant_fp8_rows(x, lda, bf.xq, K, bf.sx, M, K, stream));
+        DIT_TRY(scail_gemm_fp8(bf.xq, K, bf.sx, f.q, f.s, bias, h->probe_y8, N, M, N, K, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
+        DIT_TRY(scail_rel_err_rows(h->probe_y16, N, h->probe_y8, N, h->probe_table + (i * G_COUNT + g) * 4, M, N, stream));
+    } else if (quantised && fp8_in_force(h, i, g)) {
         const scail_dit::Fp8W& f = h->fp8w[i][g];
         DIT_TRY(scail_quant_fp8_rows(x, lda, bf.xq, K, bf.sx, M, K, stream));
         return scail_gemm_fp8(bf.xq, K, bf.sx, f.q, f.s, bias, y, ldc, M, N, K, epi, resid, ldr, gate, gs, rpb, stream);
@@ -544,6 +588,7 @@ extern "C" int scail_dit_block(scail_dit* h, int64_t layer, scail_bf16* hidden, 
     const BlockWs s = block_ws(h, B, Ltok);
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= s.end && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                   "workspace too small or not 256-byte aligned (scail_dit_block_workspace_bytes)");
+    DIT_TRY(probe_check(h, B * Ltok));
     return dit_block(h, layer, hidden, mod, cond, rope_cos, rope_sin, B, Ltok, s.bufs(workspace), 0, Ltok, false, stream);
 }
 
@@ -598,6 +643,9 @@ extern "C" int64_t scail_dit_fp8_weight_bytes(const scail_dit* h, uint32_t which
 extern "C" int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int64_t bytes, void* stream) {
     SCAIL_REQUIRE(h != nullptr, "null handle");
     SCAIL_REQUIRE((which & ~(uint32_t)SCAIL_DIT_FP8_ALL) == 0, "unknown SCAIL_DIT_FP8_* bit");
+    // a new set of quantised matrices: the per-layer selection and the probe (whose buffers were sized for the old set) start over
+    h->fp8_sel.clear();
+    probe_off(h);
     if (which == 0 || buf == nullptr) {     // back to bf16
         h->fp8 = 0;
         h->fp8w.clear();
@@ -633,6 +681,48 @@ extern "C" int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int
             h->fp8w[i][g] = {q, sc};
         }
     h->fp8 = which;
+    return 0;
+}
+
+extern "C" int scail_dit_fp8_select_layers(scail_dit* h, const uint32_t* masks) {
+    SCAIL_REQUIRE(h != nullptr, "null handle");
+    if (masks == nullptr) {                 // uniform again: the enabled mask in every layer
+        h->fp8_sel.clear();
+        return 0;
+    }
+    for (int64_t i = 0; i < h->cfg.num_layers; ++i) {
+        const uint32_t extra = masks[i] & ~h->fp8;
+        if (extra == 0) continue;
+        const uint32_t bit = extra & (~extra + 1u);      // the lowest offending bit
+        int g = 0;
+        while (g < G_COUNT && (1u << g) != bit) ++g;
+        scail_set_error("scail_dit_fp8_select_layers: layer " + std::to_string(i) + " selects bit " + std::to_string(bit) +
+                        (g < G_COUNT ? " (" + std::string(k_gemm_names[g]) + ")" : std::string(" (no SCAIL_DIT_FP8_* bit)")) +
+                        ", which is outside the mask " + std::to_string(h->fp8) + " given to scail_dit_enable_fp8: only a quantised matrix can be selected");
+        return 1;
+    }
+    h->fp8_sel.assign(masks, masks + h->cfg.num_layers);
+    return 0;
+}
+
+// the probe's scratch: two bf16 result buffers of rows x fp8_n(), each 256-byte aligned
+extern "C" int64_t scail_dit_fp8_probe_bytes(const scail_dit* h, int64_t B, int64_t Ltok) {
+    if (h == nullptr || B <= 0 || Ltok <= 0 || B * Ltok >= (1ll << 31)) return -1;
+    return 2 * align256(B * Ltok * fp8_n(h) * 2);
+}
+extern "C" int scail_dit_fp8_probe(scail_dit* h, double* table, void* scratch, int64_t scratch_bytes) {
+    SCAIL_REQUIRE(h != nullptr, "null handle");
+    probe_off(h);
+    if (table == nullptr) return 0;
+    SCAIL_REQUIRE(h->fp8 != 0, "no GEMM is quantised: call scail_dit_enable_fp8 first (the probe compares the quantised matrices with their bf16 twins)");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(table) & 7) == 0, "table must be 8-byte aligned");
+    SCAIL_REQUIRE(scratch != nullptr && (reinterpret_cast<uintptr_t>(scratch) & 255) == 0, "scratch must be a 256-byte aligned device buffer");
+    const int64_t half = scratch_bytes / 2 / 256 * 256, rows = half / (fp8_n(h) * 2);
+    SCAIL_REQUIRE(rows >= 1, "scratch too small for a single row (scail_dit_fp8_probe_bytes)");
+    h->probe_table = table;
+    h->probe_y16 = static_cast<scail_bf16*>(scratch);
+    h->probe_y8 = reinterpret_cast<scail_bf16*>(static_cast<char*>(scratch) + half);
+    h->probe_rows = rows;
     return 0;
 }
 
@@ -739,6 +829,7 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
     SCAIL_REQUIRE(c.time_embed_dim == c.hidden_size, "final-layer table add needs time_embed_dim == hidden_size");
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= s.total, "workspace too small (scail_dit_workspace_bytes)");
     SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
+    if (sp == nullptr) DIT_TRY(probe_check(h, B * tok_lens(n_char, T, H, W).Ltok));
 
     const int64_t D = c.hidden_size, nl = c.num_layers;
     const float eps = c.layernorm_epsilon;
@@ -865,6 +956,7 @@ extern "C" int scail_dit_sample_chars(scail_dit* h, float* x, const float* times
     SCAIL_REQUIRE(step_bytes >= 0, "bad latent shape");
     const SampleWs ws = sample_ws(step_bytes, T, H, W);
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= ws.total, "workspace too small (scail_dit_sample_workspace_bytes)");
+    DIT_TRY(probe_check(h, 2 * tok_lens(n_char, T, H, W).Ltok));
     char* base = static_cast<char*>(workspace);
     float *xin = reinterpret_cast<float*>(base + ws.xin), *v = reinterpret_cast<float*>(base + ws.v);
     const int64_t n = T * 16 * H * W;
@@ -936,6 +1028,7 @@ extern "C" int scail_dit_sample_tiled(scail_dit* h, float* x, const float* times
         return fail("workspace too small: " + std::to_string(workspace_bytes) + " bytes, needs " + std::to_string(ws.total) +
                     " (scail_dit_sample_tiled_workspace_bytes)");
     SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
+    DIT_TRY(probe_check(h, 2 * tok_lens(1, Tt, H, W).Ltok));
 
     char* base = static_cast<char*>(workspace);
     float *xin = reinterpret_cast<float*>(base + ws.xin), *v = reinterpret_cast<float*>(base + ws.v), *den = reinterpret_cast<float*>(base + ws.den);

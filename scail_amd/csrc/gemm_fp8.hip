@@ -1,5 +1,6 @@
 // FP8 (OCP e4m3fn) path of the per-token GEMMs (include/scail_hip.h "fp8 per-token GEMMs"):
 //   scail_quant_fp8_rows  bf16 [R, C] -> e4m3 [R, C] + one fp32 scale per row (activations per token, weights per output channel)
+//   scail_rel_err_rows    sum of squared differences / sum of squares of two bf16 matrices into a device fp64 accumulator (the fp8 probe)
 //   scail_gemm_fp8        y = epi(acc[m, n] * sx[m] * sw[n] + bias[n]), acc = the e4m3 product on the block-scaled MFMA
 //                         v_mfma_scale_f32_32x32x64_f8f6f4 (twice the bf16 matrix rate per clock), bf16 out.
 // The E8M0 block scales of the MFMA are held at the unit value (127): the per-row fp32 scales are applied in the epilogue, so every
@@ -63,6 +64,106 @@ extern "C" int scail_quant_fp8_rows(const scail_bf16* x, int64_t ldx, uint8_t* q
     hipLaunchKernelGGL(scail_quant_fp8_rows_kernel, dim3((unsigned)rows), dim3(QF8_THREADS), 0, (hipStream_t)stream,
                        reinterpret_cast<const u16*>(x), ldx, q, ldq, s, (int)cols);
     return scail_check_launch("scail_quant_fp8_rows");
+}
+
+// ---- relative error of two bf16 matrices (the executor's fp8 probe, include/scail_hip.h scail_rel_err_rows) -------------------------
+// Stage 1: workgroup k walks the rows [k rpb, (k + 1) rpb) in ascending order, 256 threads and 16-byte loads per row as above.  A lane
+// adds its elements in ascending column order, d = b - a, err = err + d d, pow = pow + a a in fp32 with every operation rounded on its own
+// (contraction off); the lanes of a wave are combined by the xor butterfly 32, 16, .., 1 and the four waves as (w0 + w1) + (w2 + w3): the
+// same bits in every thread.  Thread 0 widens the row's two sums to fp64, adds them to the workgroup's and keeps the largest row ratio.
+// Stage 2 (one workgroup, after stage 1 in stream order): thread 0 adds the workgroups' partial sums in ascending order and updates acc.
+// No floating-point atomics and no inter-workgroup hand-off inside a launch: rpb and the grid depend on `rows` alone, so the same inputs
+// give the same bits.  The partial sums live in static device memory (one copy per device): calls on one device must be stream-ordered
+// among themselves, as the executor's are.
+#define RE_THREADS 256
+#define RE_MAX_WGS 1024
+static __device__ double g_rel_err_part[RE_MAX_WGS][2];
+static __device__ float g_rel_err_max[RE_MAX_WGS];
+
+// max that keeps a NaN (a row with a non-finite element must not look clean)
+__device__ __forceinline__ float re_max(float m, float r) { return (r > m || r != r) ? r : m; }
+
+__global__ __launch_bounds__(RE_THREADS) void scail_rel_err_rows_kernel(const u16* __restrict__ a, int64_t lda, const u16* __restrict__ b,
+                                                                        int64_t ldb, int64_t rows, int64_t rpb, int cols) {
+#pragma clang fp contract(off)
+    __shared__ float red[2][RE_THREADS / 64];
+    const int64_t r0 = (int64_t)blockIdx.x * rpb, r1 = r0 + rpb < rows ? r0 + rpb : rows;
+    double se = 0.0, sp = 0.0;
+    float mx = 0.f;
+    for (int64_t r = r0; r < r1; ++r) {
+        const u16* ar = a + r * lda;
+        const u16* br = b + r * ldb;
+        float err = 0.f, pw = 0.f;
+        for (int c = threadIdx.x * 8; c < cols; c += RE_THREADS * 8) {
+            float fa[8], fb[8];
+            unpack8(*reinterpret_cast<const uint4*>(ar + c), fa);
+            unpack8(*reinterpret_cast<const uint4*>(br + c), fb);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float d = fb[e] - fa[e];
+                err = err + d * d;
+                pw = pw + fa[e] * fa[e];
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            err = err + __shfl_xor(err, o, 64);
+            pw = pw + __shfl_xor(pw, o, 64);
+        }
+        __syncthreads();     // the previous row's reads of red are done
+        if ((threadIdx.x & 63) == 0) {
+            red[0][threadIdx.x >> 6] = err;
+            red[1][threadIdx.x >> 6] = pw;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const float err_r = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+            const float pow_r = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+            const float ratio = pow_r == 0.f ? (err_r == 0.f ? 0.f : __builtin_inff()) : __fdiv_rn(err_r, pow_r);
+            se = se + (double)err_r;
+            sp = sp + (double)pow_r;
+            mx = re_max(mx, ratio);
+        }
+    }
+    if (threadIdx.x == 0) {
+        g_rel_err_part[blockIdx.x][0] = se;
+        g_rel_err_part[blockIdx.x][1] = sp;
+        g_rel_err_max[blockIdx.x] = mx;
+    }
+}
+
+__global__ __launch_bounds__(64) void scail_rel_err_finish_kernel(double* __restrict__ acc, int wgs, double rows) {
+    if (threadIdx.x != 0) return;
+    double se = 0.0, sp = 0.0;
+    float mx = 0.f;
+    for (int k = 0; k < wgs; ++k) {
+        se = se + g_rel_err_part[k][0];
+        sp = sp + g_rel_err_part[k][1];
+        mx = re_max(mx, g_rel_err_max[k]);
+    }
+    acc[0] = acc[0] + se;
+    acc[1] = acc[1] + sp;
+    const double m = (double)mx;
+    acc[2] = (m > acc[2] || m != m) ? m : acc[2];
+    acc[3] = acc[3] + rows;
+}
+
+extern "C" int scail_rel_err_rows(const scail_bf16* a, int64_t lda, const scail_bf16* b, int64_t ldb, double* acc, int64_t rows,
+                                  int64_t cols, void* stream) {
+    SCAIL_REQUIRE(a != nullptr && b != nullptr && acc != nullptr, "null pointer");
+    SCAIL_REQUIRE(rows >= 0 && cols > 0 && cols % 8 == 0 && cols < (1ll << 30), "cols must be a positive multiple of 8");
+    SCAIL_REQUIRE(lda >= cols && ldb >= cols && lda % 8 == 0 && ldb % 8 == 0, "lda / ldb must be >= cols and multiples of 8");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(a) & 15) == 0 && (reinterpret_cast<uintptr_t>(b) & 15) == 0 &&
+                      (reinterpret_cast<uintptr_t>(acc) & 7) == 0,
+                  "pointer alignment (a, b 16 B; acc 8 B)");
+    SCAIL_REQUIRE(rows < (1ll << 31), "too many rows");
+    if (rows == 0) return 0;
+    const int64_t rpb = (rows + RE_MAX_WGS - 1) / RE_MAX_WGS, wgs = (rows + rpb - 1) / rpb;
+    hipLaunchKernelGGL(scail_rel_err_rows_kernel, dim3((unsigned)wgs), dim3(RE_THREADS), 0, (hipStream_t)stream,
+                       reinterpret_cast<const u16*>(a), lda, reinterpret_cast<const u16*>(b), ldb, rows, rpb, (int)cols);
+    if (int rc = scail_check_launch("scail_rel_err_rows")) return rc;
+    hipLaunchKernelGGL(scail_rel_err_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, acc, (int)wgs, (double)rows);
+    return scail_check_launch("scail_rel_err_rows (finish)");
 }
 
 // ---- GEMM --------------------------------------------------------------------------------------------------------------------

@@ -79,13 +79,18 @@ class CStep:
         self._h = h
         self._ws = None
         self._fp8_buf = None
+        self._probe = None                               # (table, scratch) while the fp8 probe is on
+        self.num_layers = net.num_layers
         if getattr(net, "fp8_mask", 0):
             self.enable_fp8(net.fp8_mask, W["patch_w"].device)
+            if getattr(net, "fp8_layer_masks", None) is not None:
+                self.select_fp8_layers(net.fp8_layer_masks)
 
     def enable_fp8(self, which: int, device) -> None:
         """scail_dit_enable_fp8: quantize the selected per-token GEMM weights (lib.FP8_GEMMS bits) into a buffer this object owns;
         which = 0 returns to bf16."""
         lib = L.load()
+        self._probe = None                               # the executor turns the probe off and forgets the per-layer selection
         if not which:
             L.call("scail_dit_enable_fp8", self._h, 0, None, 0, torch.cuda.current_stream(device).cuda_stream)
             self._fp8_buf = None
@@ -96,6 +101,36 @@ class CStep:
         buf = torch.empty(nbytes, device=device, dtype=torch.uint8)
         L.call("scail_dit_enable_fp8", self._h, which, buf.data_ptr(), nbytes, torch.cuda.current_stream(device).cuda_stream)
         self._fp8_buf = buf
+
+    def select_fp8_layers(self, masks) -> None:
+        """scail_dit_fp8_select_layers: ``masks`` = one lib.FP8_GEMMS mask per layer, each a subset of the enabled mask (the GEMMs that
+        stay fp8 in that layer); None = the enabled mask in every layer again."""
+        if masks is None:
+            L.call("scail_dit_fp8_select_layers", self._h, None)
+            return
+        masks = [int(m) for m in masks]
+        if len(masks) != self.num_layers:
+            raise L.ScailHipError(f"select_fp8_layers: need one mask per layer ({self.num_layers}), got {len(masks)}")
+        if any(m < 0 or m > 0xffffffff for m in masks):
+            raise L.ScailHipError(f"select_fp8_layers: masks must be unsigned 32-bit values, got {masks}")
+        L.call("scail_dit_fp8_select_layers", self._h, (C.c_uint32 * len(masks))(*masks))
+
+    def fp8_probe_on(self, B: int, Ltok: int, device) -> torch.Tensor:
+        """scail_dit_fp8_probe: calls of up to B * Ltok token rows now also measure every quantised GEMM against its bf16 twin (and run
+        the network in bf16).  Returns the zeroed device table (layers, 6, 4) fp64 the executor accumulates into."""
+        need = L.load().scail_dit_fp8_probe_bytes(self._h, B, Ltok)
+        if need < 0:
+            raise L.ScailHipError(f"scail_dit_fp8_probe_bytes: bad shape (B {B}, Ltok {Ltok})")
+        table = torch.zeros(self.num_layers, 6, 4, device=device, dtype=torch.float64)
+        scratch = torch.empty(max(need, 256), device=device, dtype=torch.uint8)
+        L.call("scail_dit_fp8_probe", self._h, table.data_ptr(), scratch.data_ptr(), scratch.numel())
+        self._probe = (table, scratch)
+        return table
+
+    def fp8_probe_off(self) -> None:
+        """Back to the selected kernels (the table the caller holds stays valid; the scratch is released in stream order)."""
+        L.call("scail_dit_fp8_probe", self._h, None, None, 0)
+        self._probe = None
 
     def close(self):
         if self._h is not None:

@@ -88,6 +88,69 @@ def _fp8_options(gemm_precision, fp8_gemms):
     return "fp8", mask
 
 
+def _fp8_layer_options(fp8_layers, num_layers, mask):
+    """Per-layer SCAIL_DIT_FP8_* masks from the constructor option ``fp8_layers`` (None: no per-layer selection): one entry per layer,
+    each the mask itself (0 = that layer stays bf16) or an iterable / string of names from lib.FP8_GEMMS, and a subset of ``mask``
+    (only a GEMM that fp8_gemms quantises can be selected)."""
+    if fp8_layers is None:
+        return None
+    if not mask:
+        raise ValueError("fp8_layers needs gemm_precision='fp8'")
+    if isinstance(fp8_layers, (str, bytes)) or not hasattr(fp8_layers, "__len__"):
+        raise ValueError(f"fp8_layers must be a sequence with one entry per layer, got {fp8_layers!r}")
+    if len(fp8_layers) != num_layers:
+        raise ValueError(f"fp8_layers needs one entry per layer ({num_layers}), got {len(fp8_layers)}")
+    out = []
+    for i, e in enumerate(fp8_layers):
+        if isinstance(e, int) and not isinstance(e, bool):
+            m = e
+        else:
+            if isinstance(e, (bool, float)) or e is None:
+                raise ValueError(f"fp8_layers[{i}]: expected a mask or GEMM names, got {e!r}")
+            if isinstance(e, str):
+                e = [g for g in e.replace(",", " ").split() if g]
+            unknown = [g for g in e if g not in L.FP8_GEMMS]
+            if unknown:
+                raise ValueError(f"fp8_layers[{i}]: unknown GEMM(s) {unknown}; choose from {sorted(L.FP8_GEMMS)}")
+            m = sum(L.FP8_GEMMS[g] for g in set(e))
+        if not 0 <= m <= L.FP8_ALL:
+            raise ValueError(f"fp8_layers[{i}]: mask must be 0..{L.FP8_ALL}, got {m}")
+        if m & ~mask:
+            names = [n for n, b in L.FP8_GEMMS.items() if m & ~mask & b]
+            raise ValueError(f"fp8_layers[{i}] selects {names}, which fp8_gemms (mask {mask}) does not quantise")
+        out.append(m)
+    return out
+
+
+def fp8_rel_err(table):
+    """(layers, 6, 4) probe table (include/scail_dit.h scail_dit_fp8_probe) -> ((layers, 6) sqrt(num / den), (layers, 6) sqrt(worst row
+    ratio)) as fp64 CPU tensors.  den == 0: 0 when num == 0 too (nothing there, nothing lost), +inf otherwise."""
+    t = torch.as_tensor(table, dtype=torch.float64).cpu()
+    if t.dim() != 3 or t.shape[1:] != (6, 4):
+        raise ValueError(f"probe table must be (layers, 6, 4), got {tuple(t.shape)}")
+    num, den = t[..., 0], t[..., 1]
+    q = torch.where(den == 0, torch.where(num == 0, torch.zeros_like(num), torch.full_like(num, float("inf"))), num / den)
+    return torch.sqrt(q), torch.sqrt(t[..., 2])
+
+
+def choose_fp8_layers(rel_err, max_rel_err, enabled_mask):
+    """Per-layer fp8 masks from a probe result: GEMM g of layer i stays fp8 iff bit g of ``enabled_mask`` is set and its relative error
+    is finite and <= ``max_rel_err``.  ``rel_err``: (layers, 6) values sqrt(num / den) -- or the raw (layers, 6, 4) table, read with
+    fp8_rel_err (num == den == 0 counts as 0).  NaN and inf never pass.  Pure: no device, no network."""
+    r = torch.as_tensor(rel_err, dtype=torch.float64).cpu()
+    if r.dim() == 3:
+        r = fp8_rel_err(r)[0]
+    if r.dim() != 2 or r.shape[1] != 6:
+        raise ValueError(f"rel_err must be (layers, 6) or (layers, 6, 4), got {tuple(r.shape)}")
+    max_rel_err = float(max_rel_err)
+    if not max_rel_err >= 0.0:
+        raise ValueError(f"max_rel_err must be a number >= 0, got {max_rel_err}")
+    if isinstance(enabled_mask, bool) or not isinstance(enabled_mask, int) or not 0 <= enabled_mask <= L.FP8_ALL:
+        raise ValueError(f"enabled_mask must be 0..{L.FP8_ALL}, got {enabled_mask!r}")
+    keep = torch.isfinite(r) & (r <= max_rel_err)
+    return [sum(1 << g for g in range(6) if (enabled_mask >> g) & 1 and bool(keep[i, g])) for i in range(r.shape[0])]
+
+
 class DiffusionTransformer(nn.Module):
     """Reference-compatible network object; see module docstring."""
 
@@ -99,7 +162,7 @@ class DiffusionTransformer(nn.Module):
                  parallel_output=True, height_interpolation=1.0, width_interpolation=1.0, time_interpolation=1.0,
                  use_SwiGLU=False, use_RMSNorm=False, cfg_embed_dim=None, ofs_embed_dim=None,
                  layernorm_epsilon=1e-6, inner_hidden_size=None, use_i2v_clip=False, dtype="bf16",
-                 device=None, init_seed=1234, gemm_precision="bf16", fp8_gemms=None, **kwargs):
+                 device=None, init_seed=1234, gemm_precision="bf16", fp8_gemms=None, fp8_layers=None, **kwargs):
         super().__init__()
         # ---- options of the reference class this engine does not implement: fail loudly ----
         unsupported = []
@@ -152,6 +215,9 @@ class DiffusionTransformer(nn.Module):
                 raise NotImplementedError(f"{nm} must be a multiple of {mult}")
         # opt-in fp8 (e4m3) per-token GEMMs (include/scail_dit.h scail_dit_enable_fp8); a yaml sets them through network_config.params
         self.gemm_precision, self.fp8_mask = _fp8_options(gemm_precision, fp8_gemms)
+        # fp8_layers: which of those GEMMs stay fp8 in each layer (scail_dit_fp8_select_layers); None = all of them in every layer
+        self.fp8_layer_masks = _fp8_layer_options(fp8_layers, num_layers, self.fp8_mask)
+        self.fp8_probe_table = None        # the raw (layers, 6, 4) table of the last fp8_probe()
         if self.fp8_mask:
             D, FF = self.hidden_size, self.inner_hidden_size
             for name, (n, k) in (("qkv", (3 * D, D)), ("o", (D, D)), ("cq", (D, D)), ("co", (D, D)), ("w1", (FF, D)), ("w2", (D, FF))):
@@ -476,6 +542,39 @@ class DiffusionTransformer(nn.Module):
             from .cstep import CStep
             self._cstep = CStep(self, self.prepare())
         return self._cstep
+
+    def select_fp8_layers(self, masks):
+        """Set (or, with None, drop) the per-layer fp8 selection: ``masks`` as the constructor option ``fp8_layers``."""
+        self.fp8_layer_masks = _fp8_layer_options(masks, self.num_layers, self.fp8_mask)
+        if self._cstep is not None:
+            self._cstep.select_fp8_layers(self.fp8_layer_masks)
+
+    @torch.no_grad()
+    def fp8_probe(self, x, timesteps=None, context=None, y=None, **kwargs):
+        """One forward (arguments of ``forward_f32``) with the executor's fp8 probe on: every GEMM that fp8_gemms quantises is evaluated in
+        bf16 and in fp8 on the same, clean, bf16 activations and the difference of the two bias-only results is summed on the device
+        (include/scail_dit.h scail_dit_fp8_probe).  Returns (rel_err, worst): (layers, 6) fp64 CPU tensors, columns in lib.FP8_GEMMS order,
+        rel_err = sqrt(sum |y8 - y16|^2 / sum |y16|^2) and worst = the same for the worst token row; GEMMs that are not quantised read 0.
+        The raw table stays in ``fp8_probe_table``.  The forward itself runs in bf16 and its result is dropped; one host synchronisation."""
+        if not self.fp8_mask:
+            raise ValueError("fp8_probe needs gemm_precision='fp8' (it compares the quantised GEMMs with their bf16 twins)")
+        if not self.executor_ok() or (self.sp is not None and self.sp.size > 1):
+            raise NotImplementedError("fp8_probe runs in the C executor on a single rank only (not with SCAIL_C_STEP=0, _tap, kernel_timer, "
+                                      "sequence-parallel ranks)")
+        ref = kwargs.get("ref_concat", None)
+        if ref is None:
+            raise AssertionError("must specify ref_concat")
+        B, T, _, H, Wd = x.shape
+        n_char = ref.shape[1]
+        Ltok = (n_char + T) * (H // 2) * (Wd // 2) + n_char * T * (H // 4) * (Wd // 4)
+        ex = self._executor()
+        table = ex.fp8_probe_on(B, Ltok, x.device)
+        try:
+            self.forward_f32(x, timesteps, context, y, **kwargs)
+        finally:
+            ex.fp8_probe_off()
+        self.fp8_probe_table = table.cpu()
+        return fp8_rel_err(self.fp8_probe_table)
 
     def _check_chars(self, n_char, T, pose_frames):
         if pose_frames != n_char * T:

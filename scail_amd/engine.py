@@ -96,6 +96,34 @@ class SATVideoDiffusionEngine(nn.Module):
         return samples
 
     @torch.no_grad()
+    def calibrate_fp8(self, cond: Dict, uc: Optional[Dict], shape, max_rel_err: float, num_steps: Optional[int] = None, seed: int = 0):
+        """Per-layer fp8 selection for one request (an extension; scail_amd.dit.DiffusionTransformer.fp8_probe / choose_fp8_layers): the
+        sampler's first network evaluation -- first sigma, the CFG batch [uncond; cond], ``cond`` / ``uc`` as for ``sample`` -- runs once
+        through the executor's probe, and every (layer, GEMM) whose fp8 result is further than ``max_rel_err`` (relative, Frobenius) from
+        its bf16 twin stays in bf16 from then on.  shape = (T, C, H, W); the noise comes from a generator of its own (``seed``), so the
+        request's random stream is not consumed.  With ``smpl_tiled`` in ``cond`` (temporal tiles) the first window is probed.
+        Returns dict(rel_err (layers, 6), worst (layers, 6), masks [layers], enabled = the quantised mask); columns in lib.FP8_GEMMS order."""
+        from .dit import choose_fp8_layers
+        net = self.network
+        if self.sp is not None and self.sp.size > 1:
+            raise NotImplementedError("calibrate_fp8: the fp8 GEMMs run on a single rank only")
+        if not getattr(net, "fp8_mask", 0):
+            raise ValueError("calibrate_fp8 needs a network built with gemm_precision='fp8'")
+        uc = cond if uc is None else uc
+        g = torch.Generator().manual_seed(seed)
+        x = torch.randn(1, *shape, generator=g).to(torch.float32).to(self.device)
+        shared = {k: v for k, v in cond.items() if k not in ("crossattn", "smpl_tiled")}
+        if "smpl_tiled" in cond:                                           # RFSamplerLong: the first temporal window and its pose tile
+            shared["concat_smpl_render"] = cond["smpl_tiled"][:, 0]
+            x = x[:, :cond["smpl_tiled"].shape[2]].contiguous()
+        t = (self.sampler.sigmas(num_steps)[0] * 1000.0).repeat(2).to(self.device)        # c_noise = 1000 sigma (RFScaling)
+        ctx = torch.cat((uc["crossattn"], cond["crossattn"]), 0)
+        rel, worst = net.fp8_probe(torch.cat([x, x], 0), t, ctx, None, cond_key=("sample_hip", id(cond)), cfg_pair=True, **shared)
+        masks = choose_fp8_layers(rel, max_rel_err, net.fp8_mask)
+        net.select_fp8_layers(masks)
+        return dict(rel_err=rel, worst=worst, masks=masks, enabled=net.fp8_mask)
+
+    @torch.no_grad()
     def decode_first_stage(self, z, chunk_frames=None):
         """diffusion_video.py:298-309.  ``chunk_frames`` (an extension): the VAE's streamed decode, WanVAE_.decode."""
         if self.first_stage_model is None:

@@ -70,6 +70,7 @@ SIGNATURES = {
     "scail_bf16_to_f32": [_p, _p, _i64, _p],
     "scail_quant_fp8_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _p],
     "scail_gemm_fp8": [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _i64, _p, _i64, _i64, _p],
+    "scail_rel_err_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _p],
     "scail_resize_crop_aa": [_p, _i, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
     "scail_pose_half": [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p],
     # include/scail_dit.h (structs are passed by pointer; scail_amd/cstep.py builds them)
@@ -99,6 +100,10 @@ SIGNATURES = {
     "scail_dit_sample_tiled": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _p],
     "scail_dit_fp8_weight_bytes": [_p, C.c_uint32],
     "scail_dit_enable_fp8": [_p, C.c_uint32, _p, _i64, _p],
+    # per-layer fp8 selection (host uint32 masks [num_layers]) and the on-device GEMM error probe (device fp64 table [layers][6][4])
+    "scail_dit_fp8_select_layers": [_p, _p],
+    "scail_dit_fp8_probe_bytes": [_p, _i64, _i64],
+    "scail_dit_fp8_probe": [_p, _p, _p, _i64],
     # include/scail_vae.h (scail_amd/cvae.py builds the structs)
     "scail_vae_create": [_p, _p],
     "scail_vae_destroy": [_p],
@@ -136,7 +141,8 @@ ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- sc
                          # preprocessing, scail_resize_crop_aa / scail_pose_half, and the convolution queries scail_conv3d_norm_fused_for /
                          # scail_conv3d_kernel_name_for, the GEMM query scail_gemm_kernel_name_for, the uint8 output route,
                          # scail_frames_u8 / scail_vae_decode_u8 / scail_vae_decode_stream_u8, and the row-kernel query
-                         # scail_row_kernel_name_for)
+                         # scail_row_kernel_name_for, and the fp8 probe and per-layer selection, scail_rel_err_rows /
+                         # scail_dit_fp8_select_layers / scail_dit_fp8_probe / scail_dit_fp8_probe_bytes)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);

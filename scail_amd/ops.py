@@ -97,6 +97,21 @@ def quant_fp8_rows(x, out=None, scale=None):
     return out, scale
 
 
+def rel_err_rows(a, b, acc=None):
+    """Distance of the bf16 matrix b from a, added to the fp64 accumulator ``acc`` (4,) (include/scail_hip.h scail_rel_err_rows; a new,
+    zeroed one when None): acc[0] += sum (b - a)^2, acc[1] += sum a^2, acc[2] = max(acc[2], worst row's ratio), acc[3] += rows."""
+    _chk(a, bf16, "rel_err_rows.a"); _chk(b, bf16, "rel_err_rows.b")
+    R, Cc, lda = _rowmajor2d(a, "rel_err_rows.a")
+    Rb, Cb, ldb = _rowmajor2d(b, "rel_err_rows.b")
+    assert (Rb, Cb) == (R, Cc), (R, Cc, Rb, Cb)
+    if acc is None:
+        acc = torch.zeros(4, device=a.device, dtype=torch.float64)
+    _chk(acc, torch.float64, "rel_err_rows.acc")
+    assert acc.numel() == 4 and acc.is_contiguous()
+    L.call("scail_rel_err_rows", a.data_ptr(), lda, b.data_ptr(), ldb, acc.data_ptr(), R, Cc, _stream())
+    return acc
+
+
 def gemm_fp8(xq, sx, wq, sw, bias=None, out=None, epilogue=L.EPI_BIAS, resid=None, gate=None, rows_per_batch=0):
     """y = epilogue((xq @ wq.T) * sx[:, None] * sw[None, :] + bias) (include/scail_hip.h scail_gemm_fp8).  xq (M, K) / wq (N, K) e4m3 codes
     (uint8, from quant_fp8_rows), sx (M,) / sw (N,) fp32; bias, out, resid, gate as for gemm()."""

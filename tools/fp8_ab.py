@@ -4,8 +4,11 @@
     scail_gemm_bf16 (gemm4) and scail_gemm_fp8, the fraction of the 5 PF dense MX-fp8 peak, the ratio fp8 / gemm4;
   * the quantization pass in GB/s (bf16 read + e4m3 write + scales);
   * the config-2 step (14B, 512x896x81f, B = 2, CFG pair, scail_dit_step): bf16 against fp8 with every per-token GEMM in fp8, or the
-    --mask of SCAIL_DIT_FP8_* bits.
-Usage: python tools/fp8_ab.py [--reps 10] [--layers 40] [--no-step] [--no-gemm] [--mask 63]
+    --mask of SCAIL_DIT_FP8_* bits;
+  * --probe: the executor's GEMM error probe (scail_dit_fp8_probe) on the same config-2 evaluation: the (layers, 6) table of relative
+    errors of every fp8 GEMM against its bf16 twin on clean bf16 activations, the worst token row per GEMM, and what the probed
+    evaluation costs next to a plain one.
+Usage: python tools/fp8_ab.py [--reps 10] [--layers 40] [--no-step] [--no-gemm] [--mask 63] [--probe]
 Prints one line per measurement and a JSON summary line last."""
 from __future__ import annotations
 
@@ -134,6 +137,44 @@ def step_leg(reps, layers, mask, dev):
     return r
 
 
+def probe_leg(layers, mask, dev):
+    from scail_amd import cli
+    from scail_amd.dit import DiffusionTransformer
+    from scail_amd.sampler import make_flow_timesteps
+    T, H, W, Lt, Lc = 21, 64, 112, 512, 257
+    net = DiffusionTransformer(transformer_args=dict(model_parallel_size=1), num_frames=81, latent_width=300, latent_height=300,
+                               share_adaln=True, use_i2v_clip=True, device=dev, init_seed=1234, num_layers=layers, gemm_precision="fp8",
+                               fp8_gemms=mask, **P14B)
+    g = torch.Generator().manual_seed(1234)
+    x = torch.randn(1, T, 16, H, W, generator=g).to(dev)
+    ref = torch.randn(1, 1, 16, H, W, generator=g).to(dev).to(torch.bfloat16)
+    pose = torch.randn(1, T, 16, H // 2, W // 2, generator=g).to(dev).to(torch.bfloat16)
+    ctx = torch.randn(2, Lt, P14B["text_dim"], generator=g).to(dev).to(torch.bfloat16)
+    clip = torch.randn(1, Lc, 1280, generator=g).to(dev).to(torch.bfloat16)
+    t = (make_flow_timesteps(0, 50, shift_scale=5, mode="normal")[0] * 1000.0).repeat(2).to(dev)     # the sampler's first evaluation
+    xin = torch.cat([x, x], 0)
+    kw = dict(concat_images=torch.zeros(1, device=dev), ref_concat=ref, concat_smpl_render=pose, image_clip_features=clip, cfg_pair=True)
+    net.forward_f32(xin, t, ctx, None, **kw)                      # warm-up: conditioning, tile tables, workspace
+    torch.cuda.synchronize()
+    plain_ms = _time(lambda: net.forward_f32(xin, t, ctx, None, **kw))
+    res = {}
+    probe_ms = _time(lambda: res.update(zip(("rel_err", "worst"), net.fp8_probe(xin, t, ctx, None, **kw))))
+    rel, worst = res["rel_err"], res["worst"]
+    print(cli.format_fp8_table(dict(rel_err=rel, masks=[mask] * layers, enabled=mask), float("inf")))
+    print("worst token row of each GEMM (same layout):")
+    for i in range(layers):
+        print(f"{i:5d} " + " ".join(f"{float(worst[i, k]):8.2e}" for k in range(6)))
+    on = [k for k in range(6) if (mask >> k) & 1]
+    r = {"layers": layers, "mask": mask, "plain_fp8_step_ms": plain_ms, "probed_step_ms": probe_ms,
+         "rel_err_min": float(rel[:, on].min()), "rel_err_max": float(rel[:, on].max()), "worst_row_max": float(worst[:, on].max()),
+         "rows_per_gemm": net.fp8_probe_table[:, :, 3].tolist()}
+    print(f"probe at config-2 size ({layers} layers, mask {mask}, random-init weights): relative error {r['rel_err_min']:.4f} .. {r['rel_err_max']:.4f}, "
+          f"worst token row {r['worst_row_max']:.4f}; probed evaluation {probe_ms:.1f} ms (with the host read of the table) against "
+          f"{plain_ms:.1f} ms for a plain fp8 step", flush=True)
+    net._cstep.close()
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
@@ -142,6 +183,7 @@ def main():
     ap.add_argument("--mask", type=int, default=L.FP8_ALL)
     ap.add_argument("--no-gemm", action="store_true")
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--probe", action="store_true", help="also print the GEMM error probe's table at config-2 size")
     a = ap.parse_args()
     dev = "cuda"
     L.load()
@@ -150,6 +192,8 @@ def main():
         out["gemm"] = gemm_leg(a.reps, dev)
     if not a.no_step:
         out["step"] = step_leg(a.step_reps, a.layers, a.mask, dev)
+    if a.probe:
+        out["probe"] = probe_leg(a.layers, a.mask, dev)
     print(json.dumps(out))
 
 
