@@ -119,7 +119,7 @@ int scail_dit_step(scail_dit* h, const float* x, const float* timesteps, const s
  *              (L = 71 232) runs the 8-wave kernel
  *   all-gather (keys: the gathered [ranks * Ltok, 2D] rows)    ranks * Ltok = full L < 104 858, and Ltok < 69 906 per rank
  *   ulysses    (q, k rows of [ranks * Ltok, 3D / ranks])       Ltok < 69 906 per rank, i.e. full L < ranks * 69 906
- * (scail_flash_attn_kernel_for answers for a given launch.)
+ * (scail_flash_attn_kernel_name_for answers for a given launch, by kernel name; scail_flash_attn_kernel_for for one (batch, head) pair of it.)
  */
 int64_t scail_dit_chars_workspace_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W, int64_t n_char);
 int scail_dit_step_chars(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,

@@ -21,7 +21,9 @@
 // in); a row's two lanes (g = 0, 1) keep the same m and separate partial l that are added once at
 // the end.  LDS rows are padded (K: 272 B, V^T: 144 B) so every ds_read_b128 service group touches
 // 16 distinct 16-byte slots.
+#include <algorithm>
 #include <atomic>
+#include <cstring>
 #include "common.h"
 
 #define HD 128
@@ -875,6 +877,8 @@ static const double k_attn4_q3_cost = 0.79;
 struct Attn4Launch {
     int rows;                   // 256 | 192
     int64_t item0, n_items;     // items [item0, item0 + n_items) of the pair-major (pair, query tile) list of THIS tile height
+    int xcd_mode;               // workgroup-id decode (Attn4Args::xcd_mode); attn4_plan leaves it and the grid to attn_choose
+    int64_t grid;               // workgroups: n_items, or 8 * ceil(n_items / 8) in xcd_mode 2
 };
 // Returns the number of launches (1 or 2), or 0 + scail_last_error when the device's CU count is unavailable.
 // Constants of the plan (measured, profiles/r05_attn_sp_shape_probe.log): k_attn4_q3_cost = 0.79 (a 192-row tile against a 256-row one),
@@ -930,11 +934,113 @@ static bool attn4_eligible(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t Lq,
     return (Lk % 64 == 0 || ragged_ok) && (prescaled || raw_ok) && Lk >= 512 && accumulate == 0 && Lq * q_rs < lim && Lk * k_rs < lim &&
            Lq * o_rs < lim && 128 * (Lk + 63) < lim;
 }
-// The kernel decodes its 1-D workgroup id with reciprocal multiplications that are exact while id * divisor < 2^31
-// (asmgen/attn4.py magic31): query blocks^2 * heads * batch and heads^2 * batch must stay below that; larger grids run the 8-wave kernel.
-static bool attn4_grid_ok(int64_t n_batch, int64_t heads, int64_t Lq) {
+// What the self-attention and the cross-attention choice share: option "attn4", and the generated kernels' 1-D workgroup-id decode -- reciprocal
+// multiplications that are exact while id * divisor < 2^31 (asmgen/attn4.py magic31): query blocks^2 * heads * batch and heads^2 * batch must stay
+// below that; larger grids run the hipcc kernels.
+static bool attn4_allowed(int64_t n_batch, int64_t heads, int64_t Lq) {
     const int64_t nqb = (Lq + 191) / 192, lim = 1ll << 31;       // the finer of the two query tilings
-    return heads < (1 << 15) && n_batch < (1 << 15) && nqb * heads * n_batch < lim / nqb && heads * n_batch < lim / heads;
+    return g_attn4_mode && heads < (1 << 15) && n_batch < (1 << 15) && nqb * heads * n_batch < lim / nqb && heads * n_batch < lim / heads;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Which kernels, and which launches of them, a self-attention call runs.  attn_choose is the ONE statement of it: scail_flash_attn_bf16 launches
+// what it says, and the host-only queries (scail_flash_attn_kernel_for, scail_flash_attn_kernel_name_for) are projections of the same answer;
+// scail_flash_attn_rows_for is attn4_plan alone, the plan whether or not a call would run the generated kernel.  Nothing outside attn_choose
+// and its helpers above (attn4_plan, attn4_eligible, attn4_allowed -- the last shared with cross_choose) reads options "attn4", "attn4_rows",
+// "attn4_cus", "attn4_xcd", the thread's rows hint, g_attn4_name or the measurement build's attn_variant.
+// ------------------------------------------------------------------------------------------------
+enum AttnFamily { ATTN_GEN,          // generated: scail_attn4_m16f (+ _q3), or the variant the measurement build's "attn4_kernel" knob names
+                  ATTN_W8,           // the product's 8-wave kernel
+                  ATTN_VARIANT };    // measurement build: a schedule of the 8-wave family forced with "attn_variant"
+// a hipcc kernel of the 8-wave family as the launch needs it: scail_launch_lds of the instantiation (which opts it in to `lds` bytes of
+// dynamic LDS on each device's first launch), the instantiation in words, threads, query rows per workgroup
+struct AttnKernel {
+    int (*launch)(const char* what, int lds_max, dim3 grid, dim3 block, size_t lds, void* stream, const AttnParams& p);
+    const char* name;
+    int lds, threads, qblk;
+};
+#define ATTN_KERNEL(LDS_, THREADS_, QBLK_, ...) {&scail_launch_lds<__VA_ARGS__, AttnParams>, #__VA_ARGS__, LDS_, THREADS_, QBLK_}
+// the 8-wave software-pipelined kernel: 4 / 4 VALU per MFMA gap, staging stores placed one per gap
+static const AttnKernel k_attn_w8 = ATTN_KERNEL(ATT_PP_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_swp_kernel<4, 4, 0, 1>);
+#ifdef SCAIL_ABLATIONS
+// A/B schedules of the 8-wave kernel family (all parity-tested except the timing ablations; measurements in DESIGN.md section 4.2): the
+// FIRST row with (attn_variant & mask) == value is the kernel.  Bit 20 (workgroup lifetimes, AttnParams::probe) is in no mask.
+static int g_attn_variant = 8 | (2 << 12);
+static const struct { int mask, value; AttnKernel k; } k_attn_variants[] = {
+    // bit 3: the software-pipelined kernel, bits 12-15 its interleave density
+    {8 | (15 << 12), 8 | (1 << 12), ATTN_KERNEL(ATT_PP_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_swp_kernel<5, 5>)},
+    {8 | (15 << 12), 8 | (2 << 12), k_attn_w8},                                                                          // the default
+    {8 | (15 << 12), 8 | (3 << 12), ATTN_KERNEL(ATT_PP_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_swp_kernel<6, 4>)},
+    {8 | (15 << 12), 8 | (4 << 12), ATTN_KERNEL(ATT_PP_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_swp_kernel<3, 3>)},
+    {8 | (15 << 12), 8 | (5 << 12), ATTN_KERNEL(ATT_PP_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_swp_kernel<4, 4, 1>)},   // timing ablation
+    {8 | (15 << 12), 8 | (6 << 12), ATTN_KERNEL(ATT_PP_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_swp_kernel<4, 4>)},      // 4 / 4 without the store placement
+    {8, 8, ATTN_KERNEL(ATT_PP_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_swp_kernel<9, 3>)},
+    {256, 256, ATTN_KERNEL(ATT_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_kernel<258, 8>)},                                // LDS-DMA staging
+    {64, 64, ATTN_KERNEL(ATT_LDS_BYTES, 256, 128, flash_attn_kernel<2, 4>)},                                             // 4-wave workgroups, two per CU
+    {0xFFFFF, 18, ATTN_KERNEL(ATT_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_kernel<18, 8>)},                              // timing ablations
+    {0xFFFFF, 34, ATTN_KERNEL(ATT_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_kernel<34, 8>)},
+    {0xFFFFF, 50, ATTN_KERNEL(ATT_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_kernel<50, 8>)},
+    {3, 0, ATTN_KERNEL(ATT_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_kernel<0, 8>)},
+    {3, 1, ATTN_KERNEL(ATT_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_kernel<1, 8>)},
+    {3, 2, ATTN_KERNEL(ATT_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_kernel<2, 8>)},
+    {3, 3, ATTN_KERNEL(ATT_LDS_BYTES, ATT_THREADS, QBLK, flash_attn_kernel<3, 8>)},
+};
+#endif
+struct AttnChoice {
+    AttnFamily family = ATTN_W8;
+    AttnKernel hip = k_attn_w8;  // ATTN_W8 / ATTN_VARIANT: the launch
+    int variant = 0;             // ATTN_VARIANT: the attn_variant code
+    const char* name = nullptr;  // ATTN_GEN: the base symbol (g_attn4_name's characters); a 192-row launch runs name + "_q3"
+    bool fold = true;            // ATTN_GEN: a 16x16x32 "fold" kernel (scores in log2 units, the scale multiplied into the Q fragments once)
+    int n_launch = 0;            // ATTN_GEN with a plan: 1 or 2 launches; -1: the plan needs the device's CU count and there is none
+    Attn4Launch launch[2] = {};
+};
+
+// want_plan == false answers the family and the kernel alone, which needs no device; the plan of the shipped generated kernel is sized by the
+// device's compute units (attn4_plan) unless option "attn4_rows" or the thread's hint forces a height.
+static AttnChoice attn_choose(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk, int accumulate,
+                              bool prescaled, bool want_plan) {
+    AttnChoice c;
+    if (attn4_allowed(n_batch, heads, Lq) && attn4_eligible(q_rs, k_rs, o_rs, Lq, Lk, accumulate, prescaled)) {
+        c.family = ATTN_GEN;
+        c.name = g_attn4_name.c_str();
+        c.fold = attn4_variant_is("m16f") || attn4_variant_is("m16g");      // (the 32x32x16 variants of the measurement build are not)
+        if (!want_plan) return c;
+        // launch plan (tile heights): the 192-row form exists for the shipped kernel only
+        if (g_attn4_name == k_attn4_default) {
+            c.n_launch = attn4_plan(n_batch, heads, Lq, c.launch);
+            if (c.n_launch == 0) { c.n_launch = -1; return c; }
+        } else {
+            c.n_launch = 1;
+            c.launch[0] = {256, 0, (Lq + 255) / 256 * heads * n_batch};
+        }
+        // XCD-aware ids (measured, profiles/r05_attn_sp_shape_probe.log): fewer than 8 pairs -> plain decode (all XCDs stream the one
+        // pair in step; 5 pairs: 4 % faster than a run per XCD); whole launches of 8 k pairs -> pairs dealt round-robin (mode 1);
+        // anything else -> 8 equal runs of the item list (mode 2, the grid padded to 8 runs)
+        const int64_t pairs = heads * n_batch;
+        for (int li = 0; li < c.n_launch; ++li) {
+            Attn4Launch& pl = c.launch[li];
+            pl.xcd_mode = (!g_attn4_xcd || pairs < 8) ? 0 : ((pairs % 8 == 0 && c.n_launch == 1) ? 1 : 2);
+            pl.grid = pl.xcd_mode == 2 ? 8 * ((pl.n_items + 7) / 8) : pl.n_items;
+        }
+        return c;
+    }
+#ifdef SCAIL_ABLATIONS
+    if (g_attn_variant != (8 | (2 << 12))) {
+        c.family = ATTN_VARIANT;
+        c.variant = g_attn_variant;
+        for (const auto& v : k_attn_variants)
+            if ((c.variant & v.mask) == v.value) { c.hip = v.k; break; }      // (the table's last four rows cover every code)
+    }
+#endif
+    return c;
+}
+
+// The choice in words: a hipcc kernel's template with the arguments of the instantiation, "attn_variant <code>: " in front where the measurement
+// build forced it; a generated kernel's symbol -- of launch `li` of the plan (the launch resolves its kernel by it), or the base symbol (li < 0)
+static std::string attn_choice_name(const AttnChoice& c, int li) {
+    if (c.family == ATTN_GEN) return li >= 0 && c.launch[li].rows == 192 ? std::string(c.name) + "_q3" : std::string(c.name);
+    return c.family == ATTN_VARIANT ? "attn_variant " + std::to_string(c.variant) + ": " + c.hip.name : c.hip.name;
 }
 
 extern "C" int scail_flash_attn_rows_for(int64_t n_batch, int64_t heads, int64_t Lq) {
@@ -945,7 +1051,33 @@ extern "C" int scail_flash_attn_rows_for(int64_t n_batch, int64_t heads, int64_t
 }
 
 extern "C" int scail_flash_attn_kernel_for(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t Lq, int64_t Lk, int accumulate, int prescaled) {
-    return (g_attn4_mode && attn4_eligible(q_rs, k_rs, o_rs, Lq, Lk, accumulate, prescaled != 0)) ? 4 : 8;
+    return attn_choose(q_rs, k_rs, o_rs, 1, 1, Lq, Lk, accumulate, prescaled != 0, false).family == ATTN_GEN ? 4 : 8;
+}
+
+extern "C" int scail_flash_attn_kernel_name_for(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk,
+                                                int accumulate, int prescaled, char* buf, int64_t len, int64_t* plan) {
+    SCAIL_REQUIRE(buf != nullptr, "null argument");
+    SCAIL_REQUIRE(n_batch >= 1 && heads >= 1 && Lq >= 1 && Lk >= 1, "need at least one pair, one query and one key");
+    const AttnChoice c = attn_choose(q_rs, k_rs, o_rs, n_batch, heads, Lq, Lk, accumulate, prescaled != 0, plan != nullptr);
+    if (c.n_launch < 0) return 2;                       // (scail_device_cus left the message)
+    std::string name = attn_choice_name(c, c.n_launch > 0 ? 0 : -1);
+    if (c.n_launch == 2) name += " + " + attn_choice_name(c, 1);
+    SCAIL_REQUIRE((int64_t)name.size() < len, "buffer too small");
+    std::memcpy(buf, name.c_str(), name.size() + 1);
+    if (plan == nullptr) return 0;
+    std::fill(plan, plan + 9, (int64_t)0);
+    if (c.family != ATTN_GEN) {                         // a hipcc kernel: one launch, a workgroup per (query block, head, batch element)
+        const int64_t v[5] = {1, c.hip.qblk, 0, (Lq + c.hip.qblk - 1) / c.hip.qblk * heads * n_batch, 0};
+        std::copy(v, v + 5, plan);
+        return 0;
+    }
+    plan[0] = c.n_launch;
+    for (int li = 0; li < c.n_launch; ++li) {
+        const Attn4Launch& pl = c.launch[li];
+        const int64_t v[4] = {pl.rows, pl.item0, pl.n_items, pl.xcd_mode};
+        std::copy(v, v + 4, plan + 1 + 4 * li);
+    }
+    return 0;
 }
 
 int scail_gemm4_enable(int on);   // gemm.hip
@@ -980,9 +1112,9 @@ extern "C" int scail_set_option(const char* name, int value) {
     }
     if (k == "gemm4") return scail_gemm4_enable(value);                     // 0: the kernels of csrc/gemm.hip for every shape
     if (k == "conv4") return scail_conv4_enable(value);                     // 0: the kernels of csrc/conv.hip for every convolution
-    if (k == "row_wave") return scail_row_wave_enable(value);
-    if (k == "conv_direct") return scail_conv_direct_enable(value);
-    if (k == "conv4_cont") return scail_conv4_cont_enable(value);           // 1: tile-continuation variants of the generated 96-channel kernels         // 0: the gather kernel for the HBM-bound convolutions too               // 0: block-per-row LayerNorm / RMSNorm kernels for every width
+    if (k == "row_wave") return scail_row_wave_enable(value);               // 0: block-per-row LayerNorm / RMSNorm kernels for every width
+    if (k == "conv_direct") return scail_conv_direct_enable(value);         // 0: the gather kernel for the HBM-bound convolutions too
+    if (k == "conv4_cont") return scail_conv4_cont_enable(value);           // 1: tile-continuation variants of the generated 96-channel kernels
     if (k == "conv_s2") return scail_conv_s2_enable(value);                 // 0: the gather kernel for Resample's stride-2 convolution; 1 / 2: conv_s2_kernel with one / two frames per workgroup
     if (k == "conv4_resnorm") return scail_conv4_resnorm_enable(value);     // 0: scail_conv3d_cl_resid_norm = the two separate calls for every shape
     if (k == "attn4_thr") {                                                 // lazy-rescale threshold of attn4: P <= 2^value
@@ -1001,7 +1133,6 @@ int scail_gemm4_knob(const char* knob, int value);
 int scail_gemm_group_m(int v);
 int scail_conv_tune(int v);
 int scail_conv4_kernel(const char* suffix);
-static int g_attn_variant = 8 | (2 << 12);
 extern "C" int scail_tune_set(const char* knob, int value) {
     if (std::string(knob) == "attn_variant") {
         if (value & (512 | 1024 | 2048)) {
@@ -1011,9 +1142,8 @@ extern "C" int scail_tune_set(const char* knob, int value) {
         g_attn_variant = value;
         return 0;
     }
-    if (std::string(knob) == "attn4") { g_attn4_mode = value != 0; return 0; }              // 0: 8-wave kernels only
-    if (std::string(knob) == "attn4_thr") { g_attn4_thr_log2 = (float)value; return 0; }    // lazy-rescale threshold (log2 units)
-    if (std::string(knob) == "attn4_xcd") { g_attn4_xcd = value != 0; return 0; }
+    if (std::string(knob) == "attn4" || std::string(knob) == "attn4_xcd") return scail_set_option(knob, value);   // (the product's options)
+    if (std::string(knob) == "attn4_thr") { g_attn4_thr_log2 = (float)value; return 0; }    // lazy-rescale threshold (log2 units), any value: the option checks its range
     if (std::string(knob).rfind("attn4_kernel", 0) == 0) {
         // A/B of the generated schedules: knob = "attn4_kernel" (default kernel) or "attn4_kernel:<suffix>" -> kernel
         // scail_attn4_<suffix> of the embedded code object (the variants exist only in the ablation build, SCAIL_ABLATIONS=1)
@@ -1035,6 +1165,24 @@ extern "C" int scail_tune_set(const char* knob, int value) {
 
 #endif  // SCAIL_ABLATIONS
 
+// The fields of the generated kernels' argument block that scail_attn4_m16f (one launch of the plan) and scail_attn4_x2 (set 1 of its two)
+// share: operands and strides, the launch's items, the reciprocals of the workgroup-id decode.  sl2, thr and restarts are the caller's.
+static void attn4_fill(Attn4Args& a, const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_ss, int64_t k_bs, int64_t k_rs,
+                       const void* vt, int64_t vt_ss, int64_t vt_bs, void* o, int64_t o_bs, int64_t o_rs, int64_t heads, int64_t Lq, int64_t Lk,
+                       int64_t n_seg, const Attn4Launch& pl) {
+    a.q = q; a.k = k; a.vt = vt; a.o = o;
+    a.q_bs = q_bs; a.q_rs = q_rs; a.k_ss = k_ss; a.k_bs = k_bs; a.k_rs = k_rs; a.vt_ss = vt_ss; a.vt_bs = vt_bs;
+    a.o_bs = o_bs; a.o_rs = o_rs;
+    a.heads = (int32_t)heads; a.Lq = (int32_t)Lq; a.Lk = (int32_t)Lk; a.Lkp = (int32_t)((Lk + 63) / 64 * 64); a.n_seg = (int32_t)n_seg;
+    a.nqb = (int32_t)((Lq + pl.rows - 1) / pl.rows);
+    a.magic_nqb = (uint32_t)(((1ull << 31) + a.nqb - 1) / a.nqb);
+    a.magic_heads = (uint32_t)(((1ull << 31) + heads - 1) / heads);
+    a.xcd_mode = pl.xcd_mode;
+    a.n_items = (int32_t)pl.n_items;
+    a.item0 = (int32_t)pl.item0;
+    a.items_per_xcd = (a.n_items + 7) / 8;
+}
+
 extern "C" int scail_flash_attn_bf16(const scail_bf16* q, int64_t q_bs, int64_t q_rs,
                                      const scail_bf16* k, int64_t k_ss, int64_t k_bs, int64_t k_rs,
                                      const scail_bf16* vt, int64_t vt_ss, int64_t vt_bs,
@@ -1055,72 +1203,23 @@ extern "C" int scail_flash_attn_bf16(const scail_bf16* q, int64_t q_bs, int64_t 
     SCAIL_REQUIRE(vt_bs == 0 || vt_bs == heads * HD * Lkp, "vt batch stride must be 0 or heads*128*ceil64(Lk)");
     SCAIL_REQUIRE(Lq < (1ll << 31) && Lkp * n_seg < (1ll << 31), "sequence too long");
     if (Lq == 0 || n_batch == 0) return 0;
-    static ScailDeviceOnce attr_set;
-    if (attr_set.need()) {
-        const void* fns[] = {reinterpret_cast<const void*>(&flash_attn_swp_kernel<4, 4, 0, 1>),
-#ifdef SCAIL_ABLATIONS
-                             reinterpret_cast<const void*>(&flash_attn_swp_kernel<5, 5>), reinterpret_cast<const void*>(&flash_attn_swp_kernel<4, 4>),
-                             reinterpret_cast<const void*>(&flash_attn_swp_kernel<6, 4>), reinterpret_cast<const void*>(&flash_attn_swp_kernel<3, 3>),
-                             reinterpret_cast<const void*>(&flash_attn_swp_kernel<9, 3>), reinterpret_cast<const void*>(&flash_attn_swp_kernel<4, 4, 1>),
-#endif
-        };
-        for (const void* f : fns) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_PP_LDS_BYTES);
-            if (e != hipSuccess) {
-                scail_set_error(std::string("flash_attn: hipFuncSetAttribute failed: ") + hipGetErrorString(e));
-                return 2;
-            }
-        }
-#ifdef SCAIL_ABLATIONS
-        const void* lock[] = {reinterpret_cast<const void*>(&flash_attn_kernel<258, 8>), reinterpret_cast<const void*>(&flash_attn_kernel<2, 4>),
-                              reinterpret_cast<const void*>(&flash_attn_kernel<0, 8>), reinterpret_cast<const void*>(&flash_attn_kernel<1, 8>),
-                              reinterpret_cast<const void*>(&flash_attn_kernel<2, 8>), reinterpret_cast<const void*>(&flash_attn_kernel<3, 8>),
-                              reinterpret_cast<const void*>(&flash_attn_kernel<18, 8>), reinterpret_cast<const void*>(&flash_attn_kernel<34, 8>),
-                              reinterpret_cast<const void*>(&flash_attn_kernel<50, 8>)};
-        for (const void* f : lock) (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, ATT_LDS_BYTES);
-#endif
-        attr_set.done();
-    }
-    if (g_attn4_mode && attn4_eligible(q_rs, k_rs, o_rs, Lq, Lk, accumulate, prescaled) && attn4_grid_ok(n_batch, heads, Lq)) {
+    const AttnChoice c = attn_choose(q_rs, k_rs, o_rs, n_batch, heads, Lq, Lk, accumulate, prescaled, true);
+    if (c.family == ATTN_GEN) {
         // scail_attn4_m16f (or the variant chosen with the measurement build's "attn4_kernel" knob).  The 16x16x32 "fold" kernels
         // work on scores in log2 units: sl2 = 0 says q carries scale * log2(e) already, any other value is multiplied into the Q
         // fragments once in the prologue; their lazy-rescale threshold is in log2 units.  The 32x32x16 variants of the
         // measurement build take sl2 per score and the threshold in raw-score units.
-        hipFunction_t fn;
-        const bool fold = attn4_variant_is("m16f") || attn4_variant_is("m16g");
-        // launch plan (tile heights): the 192-row form exists for the shipped kernel only
-        Attn4Launch plan[2];
-        int n_launch = 1;
-        if (g_attn4_name == k_attn4_default) {
-            n_launch = attn4_plan(n_batch, heads, Lq, plan);
-            if (n_launch == 0) return 2;
-        } else {
-            plan[0] = {256, 0, (Lq + 255) / 256 * heads * n_batch};
-        }
-        const int64_t pairs = heads * n_batch;
-        for (int li = 0; li < n_launch; ++li) {
-            const Attn4Launch& pl = plan[li];
-            if (int rc = scail_module_function("attn4", k_attn4_hsaco, pl.rows == 192 ? g_attn4_name + "_q3" : g_attn4_name, &fn)) return rc;
+        if (c.n_launch < 0) return 2;
+        const float thr_log2 = g_attn4_thr_log2;
+        for (int li = 0; li < c.n_launch; ++li) {
+            hipFunction_t fn;
+            if (int rc = scail_module_function("attn4", k_attn4_hsaco, attn_choice_name(c, li), &fn)) return rc;
             Attn4Args a;
-            a.q = q; a.k = k; a.vt = vt; a.o = o;
-            a.q_bs = q_bs; a.q_rs = q_rs; a.k_ss = k_ss; a.k_bs = k_bs; a.k_rs = k_rs; a.vt_ss = vt_ss; a.vt_bs = vt_bs;
-            a.o_bs = o_bs; a.o_rs = o_rs;
-            a.heads = (int32_t)heads; a.Lq = (int32_t)Lq; a.Lk = (int32_t)Lk; a.Lkp = (int32_t)Lkp; a.n_seg = (int32_t)n_seg;
-            a.sl2 = fold ? (prescaled ? 0.0f : sl2) : sl2;
-            const float thr_log2 = g_attn4_thr_log2;
-            a.thr = fold ? thr_log2 : thr_log2 / sl2;
-            a.nqb = (int32_t)((Lq + pl.rows - 1) / pl.rows);
-            a.magic_nqb = (uint32_t)(((1ull << 31) + a.nqb - 1) / a.nqb);
-            a.magic_heads = (uint32_t)(((1ull << 31) + heads - 1) / heads);
-            a.n_items = (int32_t)pl.n_items;
-            a.item0 = (int32_t)pl.item0;
+            attn4_fill(a, q, q_bs, q_rs, k, k_ss, k_bs, k_rs, vt, vt_ss, vt_bs, o, o_bs, o_rs, heads, Lq, Lk, n_seg, c.launch[li]);
+            a.sl2 = c.fold ? (prescaled ? 0.0f : sl2) : sl2;
+            a.thr = c.fold ? thr_log2 : thr_log2 / sl2;
             a.restarts = g_attn4_restart_ctr;
-            a.items_per_xcd = (a.n_items + 7) / 8;
-            // XCD-aware ids (measured, profiles/r05_attn_sp_shape_probe.log): fewer than 8 pairs -> plain decode (all XCDs stream the one
-            // pair in step; 5 pairs: 4 % faster than a run per XCD); whole launches of 8 k pairs -> pairs dealt round-robin (mode 1);
-            // anything else -> 8 equal runs of the item list (mode 2)
-            a.xcd_mode = (!g_attn4_xcd || pairs < 8) ? 0 : ((pairs % 8 == 0 && n_launch == 1) ? 1 : 2);
-            if (int rc = scail_module_launch("attn4", fn, (unsigned)(a.xcd_mode == 2 ? 8 * a.items_per_xcd : a.n_items), 256, a, stream)) return rc;
+            if (int rc = scail_module_launch("attn4", fn, (unsigned)c.launch[li].grid, 256, a, stream)) return rc;
         }
         return 0;
     }
@@ -1132,63 +1231,9 @@ extern "C" int scail_flash_attn_bf16(const scail_bf16* q, int64_t q_bs, int64_t 
     p.heads = (int)heads; p.Lq = (int)Lq; p.Lk = (int)Lk; p.Lkp = (int)Lkp; p.n_seg = (int)n_seg;
     p.sl2 = sl2;
     p.accumulate = accumulate;
-    p.probe = 0;
-    dim3 grid((unsigned)((Lq + QBLK - 1) / QBLK), (unsigned)heads, (unsigned)n_batch);
-#ifdef SCAIL_ABLATIONS
-    // A/B schedules of the 8-wave kernel family (all parity-tested; measurements in DESIGN.md section 4.2)
-    p.probe = (g_attn_variant >> 20) & 1;
-    if (g_attn_variant != (8 | (2 << 12))) {
-        if (g_attn_variant & 8) {
-            const int sub = (g_attn_variant >> 12) & 15;     // A/B of the interleave density
-            static bool swp_attr = false;
-            if (!swp_attr) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_swp_kernel<5, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, ATT_PP_LDS_BYTES);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_swp_kernel<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, ATT_PP_LDS_BYTES);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_swp_kernel<6, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, ATT_PP_LDS_BYTES);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_swp_kernel<3, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, ATT_PP_LDS_BYTES);
-    #ifdef SCAIL_ABLATIONS
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_swp_kernel<4, 4, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, ATT_PP_LDS_BYTES);
-    #endif
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_swp_kernel<4, 4, 0, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, ATT_PP_LDS_BYTES);
-                swp_attr = true;
-            }
-            if (sub == 1) hipLaunchKernelGGL((flash_attn_swp_kernel<5, 5>), grid, dim3(ATT_THREADS), ATT_PP_LDS_BYTES, (hipStream_t)stream, p);
-            else if (sub == 2) hipLaunchKernelGGL((flash_attn_swp_kernel<4, 4, 0, 1>), grid, dim3(ATT_THREADS), ATT_PP_LDS_BYTES, (hipStream_t)stream, p);   // default
-            else if (sub == 3) hipLaunchKernelGGL((flash_attn_swp_kernel<6, 4>), grid, dim3(ATT_THREADS), ATT_PP_LDS_BYTES, (hipStream_t)stream, p);
-            else if (sub == 4) hipLaunchKernelGGL((flash_attn_swp_kernel<3, 3>), grid, dim3(ATT_THREADS), ATT_PP_LDS_BYTES, (hipStream_t)stream, p);
-    #ifdef SCAIL_ABLATIONS
-            else if (sub == 5) hipLaunchKernelGGL((flash_attn_swp_kernel<4, 4, 1>), grid, dim3(ATT_THREADS), ATT_PP_LDS_BYTES, (hipStream_t)stream, p);
-    #endif
-            else if (sub == 6) hipLaunchKernelGGL((flash_attn_swp_kernel<4, 4>), grid, dim3(ATT_THREADS), ATT_PP_LDS_BYTES, (hipStream_t)stream, p);   // 4/4 without the store placement
-            else hipLaunchKernelGGL((flash_attn_swp_kernel<9, 3>), grid, dim3(ATT_THREADS), ATT_PP_LDS_BYTES, (hipStream_t)stream, p);
-            return scail_check_launch("flash_attn");
-        }
-        if (g_attn_variant & 256) {  // LDS-DMA staging
-            hipLaunchKernelGGL((flash_attn_kernel<258, 8>), grid, dim3(ATT_THREADS), ATT_LDS_BYTES, (hipStream_t)stream, p);
-            return scail_check_launch("flash_attn");
-        }
-        if (g_attn_variant & 64) {   // 4-wave workgroups, two per CU
-            dim3 grid4((unsigned)((Lq + 127) / 128), (unsigned)heads, (unsigned)n_batch);
-            hipLaunchKernelGGL((flash_attn_kernel<2, 4>), grid4, dim3(256), ATT_LDS_BYTES, (hipStream_t)stream, p);
-            return scail_check_launch("flash_attn");
-        }
-    #ifdef SCAIL_ABLATIONS
-        if ((g_attn_variant & 0xFFFFF) == 18) { hipLaunchKernelGGL((flash_attn_kernel<18, 8>), grid, dim3(ATT_THREADS), ATT_LDS_BYTES, (hipStream_t)stream, p); return scail_check_launch("flash_attn"); }
-        if ((g_attn_variant & 0xFFFFF) == 34) { hipLaunchKernelGGL((flash_attn_kernel<34, 8>), grid, dim3(ATT_THREADS), ATT_LDS_BYTES, (hipStream_t)stream, p); return scail_check_launch("flash_attn"); }
-        if ((g_attn_variant & 0xFFFFF) == 50) { hipLaunchKernelGGL((flash_attn_kernel<50, 8>), grid, dim3(ATT_THREADS), ATT_LDS_BYTES, (hipStream_t)stream, p); return scail_check_launch("flash_attn"); }
-    #endif
-        switch (g_attn_variant & 3) {
-            case 0: hipLaunchKernelGGL((flash_attn_kernel<0, 8>), grid, dim3(ATT_THREADS), ATT_LDS_BYTES, (hipStream_t)stream, p); break;
-            case 1: hipLaunchKernelGGL((flash_attn_kernel<1, 8>), grid, dim3(ATT_THREADS), ATT_LDS_BYTES, (hipStream_t)stream, p); break;
-            case 2: hipLaunchKernelGGL((flash_attn_kernel<2, 8>), grid, dim3(ATT_THREADS), ATT_LDS_BYTES, (hipStream_t)stream, p); break;
-            default: hipLaunchKernelGGL((flash_attn_kernel<3, 8>), grid, dim3(ATT_THREADS), ATT_LDS_BYTES, (hipStream_t)stream, p); break;
-        }
-        return scail_check_launch("flash_attn");
-    }
-#endif
-    // the 8-wave software-pipelined kernel: 4 / 4 VALU per MFMA gap, staging stores placed one per gap
-    hipLaunchKernelGGL((flash_attn_swp_kernel<4, 4, 0, 1>), grid, dim3(ATT_THREADS), ATT_PP_LDS_BYTES, (hipStream_t)stream, p);
-    return scail_check_launch("flash_attn");
+    p.probe = (c.variant >> 20) & 1;
+    const dim3 grid((unsigned)((Lq + c.hip.qblk - 1) / c.hip.qblk), (unsigned)heads, (unsigned)n_batch);
+    return c.hip.launch("flash_attn", c.hip.lds, grid, dim3(c.hip.threads), c.hip.lds, stream, p);
 }
 
 // ---- cross attention over two key sets on the generated 4-wave pipeline (scail_attn4_x2) ----
@@ -1199,17 +1244,57 @@ struct Attn4X2Args {
     int32_t Lk2, Lkp2, n_wgs, pad;
 };
 static_assert(sizeof(Attn4X2Args) == 216, "Attn4X2Args must match asmgen/attn4.py X2_KERNARG_SIZE");
-// one K row stride for both sets (the set switch keeps the K DMA lane offsets), at least one whole key tile per set (a ragged tile's
-// missing rows are fetched from 64 rows earlier), 32-bit byte offsets inside a (batch, head) slice, exact reciprocal id decode
-static bool cross4_eligible(int64_t q_rs, int64_t k1_rs, int64_t k2_rs, int64_t o_rs, int64_t Lq, int64_t Lk1, int64_t Lk2, int64_t n_batch, int64_t heads) {
+
+// ------------------------------------------------------------------------------------------------
+// Which kernel a two-set cross attention runs.  cross_choose is the ONE statement of it: scail_cross_attn2_bf16 launches what it says, and the
+// host-only queries (scail_cross_attn2_kernel_for, scail_cross_attn2_kernel_name_for) are projections of the same answer.  Nothing else
+// reads option "cross4" or k_cross4_min_tiles; option "attn4" and the id decode's grid limit come in through attn4_allowed.
+// ------------------------------------------------------------------------------------------------
+struct CrossChoice {
+    bool generated = false;      // scail_attn4_x2 instead of cross_attn2_kernel
+    const char* name = "cross_attn2_kernel";
+    int64_t n_items = 0;         // generated: (pair, 256-row query block) items the persistent workgroups walk over
+    int64_t grid = 0;            // workgroups; -1: the generated kernel's grid was asked for and the device's CU count is not available
+};
+
+// scail_attn4_x2 needs: one K row stride for both sets (the set switch keeps the K DMA lane offsets), at least one whole key tile per set (a
+// ragged tile's missing rows are fetched from 64 rows earlier), 32-bit byte offsets inside a (batch, head) slice, exact reciprocal id decode.
+// want_grid == false answers the kernel alone, which needs no device: the generated kernel runs one persistent workgroup per compute unit.
+static CrossChoice cross_choose(int64_t q_rs, int64_t k1_rs, int64_t k2_rs, int64_t o_rs, int64_t Lq, int64_t Lk1, int64_t Lk2, int64_t n_batch,
+                                int64_t heads, bool want_grid) {
+    CrossChoice c;
+    c.grid = (Lq + 127) / 128 * heads * n_batch;          // cross_attn2_kernel: a workgroup per (128-row query block, head, batch element)
     const int64_t lim = (1ll << 30);
-    const bool want = g_cross4 == 1 || (g_cross4 == 2 && (Lk1 + 63) / 64 + (Lk2 + 63) / 64 >= k_cross4_min_tiles);
-    return want && g_attn4_mode && k1_rs == k2_rs && Lk1 >= 64 && Lk2 >= 64 && Lq * q_rs < lim && Lq * o_rs < lim && Lk1 * k1_rs < lim &&
-           Lk2 * k2_rs < lim && 128 * (Lk1 + 63) < lim && 128 * (Lk2 + 63) < lim && attn4_grid_ok(n_batch, heads, Lq);
+    const int mode = g_cross4;
+    const bool want = mode == 1 || (mode == 2 && (Lk1 + 63) / 64 + (Lk2 + 63) / 64 >= k_cross4_min_tiles);
+    if (!(want && k1_rs == k2_rs && Lk1 >= 64 && Lk2 >= 64 && Lq * q_rs < lim && Lq * o_rs < lim && Lk1 * k1_rs < lim && Lk2 * k2_rs < lim &&
+          128 * (Lk1 + 63) < lim && 128 * (Lk2 + 63) < lim && attn4_allowed(n_batch, heads, Lq)))
+        return c;
+    c.generated = true;
+    c.name = "scail_attn4_x2";
+    c.n_items = (Lq + 255) / 256 * heads * n_batch;
+    c.grid = 0;
+    if (!want_grid) return c;
+    const int cus = scail_device_cus();
+    c.grid = cus <= 0 ? -1 : std::min<int64_t>(c.n_items, cus);
+    return c;
 }
+
 extern "C" int scail_cross_attn2_kernel_for(int64_t q_rs, int64_t k1_rs, int64_t k2_rs, int64_t o_rs, int64_t Lq, int64_t Lk1, int64_t Lk2,
                                             int64_t n_batch, int64_t heads) {
-    return cross4_eligible(q_rs, k1_rs, k2_rs, o_rs, Lq, Lk1, Lk2, n_batch, heads) ? 4 : 2;
+    return cross_choose(q_rs, k1_rs, k2_rs, o_rs, Lq, Lk1, Lk2, n_batch, heads, false).generated ? 4 : 2;
+}
+
+extern "C" int scail_cross_attn2_kernel_name_for(int64_t q_rs, int64_t k1_rs, int64_t k2_rs, int64_t o_rs, int64_t Lq, int64_t Lk1, int64_t Lk2,
+                                                 int64_t n_batch, int64_t heads, char* buf, int64_t len, int64_t* workgroups) {
+    SCAIL_REQUIRE(buf != nullptr, "null argument");
+    SCAIL_REQUIRE(n_batch >= 1 && heads >= 1 && Lq >= 1 && Lk1 >= 1 && Lk2 >= 1, "need at least one pair, one query and one key per set");
+    const CrossChoice c = cross_choose(q_rs, k1_rs, k2_rs, o_rs, Lq, Lk1, Lk2, n_batch, heads, workgroups != nullptr);
+    if (c.grid < 0) return 2;                           // (scail_device_cus left the message)
+    SCAIL_REQUIRE((int64_t)std::strlen(c.name) < len, "buffer too small");
+    std::strcpy(buf, c.name);
+    if (workgroups != nullptr) *workgroups = c.grid;
+    return 0;
 }
 
 extern "C" int scail_cross_attn2_bf16(const scail_bf16* q, int64_t q_bs, int64_t q_rs,
@@ -1228,31 +1313,20 @@ extern "C" int scail_cross_attn2_bf16(const scail_bf16* q, int64_t q_bs, int64_t
     if (n_batch == 0 || Lq == 0) return 0;
     const bool prescaled = scale == SCAIL_ATTN_Q_PRESCALED;        // q already carries scale * log2(e)
     SCAIL_REQUIRE(prescaled || (scale > 0.0f && scale < 3.0e38f), "cross_attn2: scale must be a positive finite number or SCAIL_ATTN_Q_PRESCALED");
-    if (cross4_eligible(q_rs, k1_rs, k2_rs, o_rs, Lq, Lk1, Lk2, n_batch, heads)) {
+    const CrossChoice c = cross_choose(q_rs, k1_rs, k2_rs, o_rs, Lq, Lk1, Lk2, n_batch, heads, true);
+    if (c.generated) {
         // scail_attn4_x2 (csrc/attn4.s, asmgen/attn4.py Cfg.x2): the 4-wave pipeline of the self-attention kernel, persistent workgroups (one
         // per CU) walking over the (pair, 256-row query block) items, the key pipeline run once per key set and item
         hipFunction_t fn;
-        if (int rc = scail_module_function("attn4", k_attn4_hsaco, "scail_attn4_x2", &fn)) return rc;
-        const int cus = scail_device_cus();
-        if (cus <= 0) return 2;
+        if (int rc = scail_module_function("attn4", k_attn4_hsaco, c.name, &fn)) return rc;
+        if (c.grid < 0) return 2;
         Attn4X2Args a;
-        Attn4Args& b = a.base;
-        const int64_t Lkp1 = (Lk1 + 63) / 64 * 64, Lkp2 = (Lk2 + 63) / 64 * 64;
-        b.q = q; b.k = k1; b.vt = vt1; b.o = o;
-        b.q_bs = q_bs; b.q_rs = q_rs; b.k_ss = 0; b.k_bs = k1_bs; b.k_rs = k1_rs; b.vt_ss = 0; b.vt_bs = vt1_bs; b.o_bs = o_bs; b.o_rs = o_rs;
-        b.heads = (int32_t)heads; b.Lq = (int32_t)Lq; b.Lk = (int32_t)Lk1; b.Lkp = (int32_t)Lkp1; b.n_seg = 1;
-        b.sl2 = prescaled ? 0.0f : scale * 1.4426950408889634f;
-        b.thr = g_attn4_thr_log2;
-        b.nqb = (int32_t)((Lq + 255) / 256);
-        b.magic_nqb = (uint32_t)(((1ull << 31) + b.nqb - 1) / b.nqb);
-        b.magic_heads = (uint32_t)(((1ull << 31) + heads - 1) / heads);
-        b.xcd_mode = 0;
-        b.n_items = (int32_t)(b.nqb * heads * n_batch);
-        b.items_per_xcd = (b.n_items + 7) / 8;
-        b.item0 = 0;
-        b.restarts = nullptr;            // the cross attention is not counted (scail_flash_attn_count_restarts is about the self-attention)
-        a.k2 = k2; a.vt2 = vt2; a.k2_bs = k2_bs; a.vt2_bs = vt2_bs; a.Lk2 = (int32_t)Lk2; a.Lkp2 = (int32_t)Lkp2;
-        a.n_wgs = (int32_t)std::min<int64_t>(b.n_items, cus);
+        attn4_fill(a.base, q, q_bs, q_rs, k1, 0, k1_bs, k1_rs, vt1, 0, vt1_bs, o, o_bs, o_rs, heads, Lq, Lk1, 1, Attn4Launch{256, 0, c.n_items, 0, c.grid});
+        a.base.sl2 = prescaled ? 0.0f : scale * 1.4426950408889634f;
+        a.base.thr = g_attn4_thr_log2;
+        a.base.restarts = nullptr;       // the cross attention is not counted (scail_flash_attn_count_restarts is about the self-attention)
+        a.k2 = k2; a.vt2 = vt2; a.k2_bs = k2_bs; a.vt2_bs = vt2_bs; a.Lk2 = (int32_t)Lk2; a.Lkp2 = (int32_t)((Lk2 + 63) / 64 * 64);
+        a.n_wgs = (int32_t)c.grid;
         a.pad = 0;
         return scail_module_launch("cross_attn2 (attn4_x2)", fn, (unsigned)a.n_wgs, 256, a, stream);
     }
@@ -1263,6 +1337,6 @@ extern "C" int scail_cross_attn2_bf16(const scail_bf16* q, int64_t q_bs, int64_t
     p.o = o; p.o_bs = o_bs; p.o_rs = o_rs;
     p.heads = (int)heads; p.Lq = (int)Lq;
     p.sl2 = prescaled ? 1.0f : scale * 1.44269504088896340736f;
-    dim3 grid((unsigned)((Lq + 127) / 128), (unsigned)heads, (unsigned)n_batch);
+    const dim3 grid((unsigned)((Lq + 127) / 128), (unsigned)heads, (unsigned)n_batch);
     return scail_launch_lds<cross_attn2_kernel>("cross_attn2", X2_LDS_BYTES, grid, dim3(X2_THREADS), X2_LDS_BYTES, stream, p);
 }

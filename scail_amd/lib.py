@@ -29,10 +29,12 @@ SIGNATURES = {
     "scail_flash_attn_bf16": [_p, _i64, _i64, _p, _i64, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64,
                               _i64, _i64, _i64, _i64, _i64, _f, _i, _p],
     "scail_flash_attn_kernel_for": [_i64, _i64, _i64, _i64, _i64, _i, _i],
+    "scail_flash_attn_kernel_name_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _p, _i64, _p],
     "scail_flash_attn_rows_for": [_i64, _i64, _i64],
     "scail_flash_attn_count_restarts": [_p],
     "scail_comm_standin": [_p, _p, _i64, C.c_int32, _i64, _p],
     "scail_cross_attn2_kernel_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64],
+    "scail_cross_attn2_kernel_name_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p],
     "scail_gemm_kernel_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i],
     "scail_gemm_kernel_name_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _p, _i64],
     "scail_conv3d_kernel_for": [_p, _i64, _i64, _i],
@@ -141,7 +143,8 @@ ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- sc
                          # preprocessing, scail_resize_crop_aa / scail_pose_half, and the convolution queries scail_conv3d_norm_fused_for /
                          # scail_conv3d_kernel_name_for, the GEMM query scail_gemm_kernel_name_for, the uint8 output route,
                          # scail_frames_u8 / scail_vae_decode_u8 / scail_vae_decode_stream_u8, and the row-kernel query
-                         # scail_row_kernel_name_for, and the fp8 probe and per-layer selection, scail_rel_err_rows /
+                         # scail_row_kernel_name_for, the attention queries scail_flash_attn_kernel_name_for /
+                         # scail_cross_attn2_kernel_name_for, and the fp8 probe and per-layer selection, scail_rel_err_rows /
                          # scail_dit_fp8_select_layers / scail_dit_fp8_probe / scail_dit_fp8_probe_bytes)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);

@@ -487,6 +487,63 @@ def cross_route(q_rs, k1_rs, k2_rs, o_rs, Lq, Lk1, Lk2, B, H):
     return L.load().scail_cross_attn2_kernel_for(q_rs, k1_rs, k2_rs, o_rs, Lq, Lk1, Lk2, B, H)
 
 
+GEN, W8 = "scail_attn4_m16f", "flash_attn_swp_kernel<4, 4, 0, 1>"
+X_GEN, X_HIP = "scail_attn4_x2", "cross_attn2_kernel"
+# the measurement build's attn_variant codes that the GPU tests force (ATTN_VARIANTS there), by kernel
+VARIANT_KERNELS = {2: "flash_attn_kernel<2, 8>", 258: "flash_attn_kernel<258, 8>", 66: "flash_attn_kernel<2, 4>", 8 | (1 << 12): "flash_attn_swp_kernel<5, 5>",
+                   8 | (6 << 12): "flash_attn_swp_kernel<4, 4>"}
+
+
+def kernel_name(q_rs, k_rs, o_rs, B, H, Lq, Lk, accumulate, prescaled, plan=False, agree=True):
+    """what scail_flash_attn_kernel_name_for says the call runs under the options in force; scail_flash_attn_kernel_for must agree (agree=False:
+    a grid the seven-argument query cannot see).  plan=True (needs the device unless option attn4_rows forces a height): (name, dict(n_launch,
+    launches=[dict(rows, item0, n_items, xcd_mode)]))"""
+    import ctypes as C
+    from scail_amd import lib as L
+    buf, pl = C.create_string_buffer(128), (C.c_int64 * 9)()
+    L.call("scail_flash_attn_kernel_name_for", q_rs, k_rs, o_rs, B, H, Lq, Lk, 1 if accumulate else 0, 1 if prescaled else 0, buf, len(buf),
+           C.cast(pl, C.c_void_p) if plan else None)
+    name = buf.value.decode()
+    if agree:
+        assert flash_route(q_rs, k_rs, o_rs, Lq, Lk, accumulate, prescaled) == (4 if name.startswith("scail_attn4") else 8), name
+    if not plan:
+        return name
+    launches = [dict(zip(("rows", "item0", "n_items", "xcd_mode"), pl[1 + 4 * i:5 + 4 * i])) for i in range(2)]
+    assert pl[0] in (1, 2) and all(v == 0 for l in launches[pl[0]:] for v in l.values()), list(pl)
+    return name, dict(n_launch=pl[0], launches=launches[:pl[0]])
+
+
+def cross_kernel_name(q_rs, k1_rs, k2_rs, o_rs, Lq, Lk1, Lk2, B, H, want_grid=False):
+    """what scail_cross_attn2_kernel_name_for says the call runs under the options in force (want_grid: (name, workgroups), which needs the device
+    for the generated kernel); scail_cross_attn2_kernel_for must agree"""
+    import ctypes as C
+    from scail_amd import lib as L
+    buf, wg = C.create_string_buffer(128), C.c_int64(-1)
+    L.call("scail_cross_attn2_kernel_name_for", q_rs, k1_rs, k2_rs, o_rs, Lq, Lk1, Lk2, B, H, buf, len(buf), C.cast(C.byref(wg), C.c_void_p) if want_grid else None)
+    name = buf.value.decode()
+    assert cross_route(q_rs, k1_rs, k2_rs, o_rs, Lq, Lk1, Lk2, B, H) == {X_GEN: 4, X_HIP: 2}[name], name
+    return (name, wg.value) if want_grid else name
+
+
+def expected_name(case, rows=None, variant=None):
+    """the name the queries must give for a case under its options: a self-attention case by its route -- rows: the generated kernel's launches, 256 / 192
+    = one of that height, 448 = both, None = the base symbol (no plan asked for); variant: the attn_variant code the measurement build forces on the
+    8-wave family -- and a cross-attention case by its route under option cross4 = 1"""
+    if "Lk1" in case:
+        return X_GEN if case["route"] == 4 else X_HIP
+    if case["route"] == 8 or case["opts"].get("attn4", 1) == 0:
+        return f"attn_variant {variant}: {VARIANT_KERNELS[variant]}" if variant in VARIANT_KERNELS else W8
+    return {None: GEN, 256: GEN, 192: GEN + "_q3", 448: GEN + " + " + GEN + "_q3"}[rows]
+
+
+def expected_xcd_mode(pairs, opts, n_launch=1):
+    """the workgroup-id decode of a generated launch: plain below 8 (batch, head) pairs or under attn4_xcd = 0, pairs dealt round-robin for one launch
+    of a multiple of 8 pairs, 8 runs of the item list otherwise"""
+    if opts.get("attn4_xcd", 1) == 0 or pairs < 8:
+        return 0
+    return 1 if pairs % 8 == 0 and n_launch == 1 else 2
+
+
 def strides_of(case):
     """(q_rs, k_rs, o_rs) of a case's call: the strided form takes q and k as column views of a qkv buffer and writes rows with 64 elements of slack"""
     D = case["H"] * HD

@@ -142,6 +142,104 @@ def test_cross_attention_routes(case):
     assert X.with_options({"cross4": 0}, lambda: X.cross_route(*args)) == 2
 
 
+@pytest.mark.parametrize("case", SELF_CASES, ids=lambda c: c["id"])
+def test_self_attention_expected_names(case):
+    """the name query without a plan (no device), under the case's options; kernel_name asserts that the number query agrees"""
+    q_rs, k_rs, o_rs = X.strides_of(case)
+    args = (q_rs, k_rs, o_rs, case["B"], case["H"], case["Lq"], case["Lk"], case["form"] == "accumulate", not case["raw"])
+    assert X.with_options(case["opts"], lambda: X.kernel_name(*args)) == X.expected_name(case)
+    assert X.expected_name(case) == (X.GEN if case["route"] == 4 else X.W8)
+    if case["route"] == 4:
+        assert X.with_options(dict(case["opts"], attn4=0), lambda: X.kernel_name(*args)) == X.W8
+
+
+@pytest.mark.parametrize("case", X.X_CASES, ids=lambda c: c["id"])
+def test_cross_attention_expected_names(case):
+    D = case["H"] * X.HD
+    args = (D, D, D, D, case["Lq"], case["Lk1"], case["Lk2"], case["B"], case["H"])
+    assert X.with_options({"cross4": 1}, lambda: X.cross_kernel_name(*args)) == X.expected_name(case) == (X.X_GEN if case["route"] == 4 else X.X_HIP)
+    assert X.with_options({"cross4": 0}, lambda: X.cross_kernel_name(*args)) == X.X_HIP
+
+
+def test_expected_decode_modes_of_the_named_cases():
+    """what tests/test_attn_exact_gpu.py holds the plan's xcd_mode against, case by case: 1 for 8 pairs in one launch, 2 for 9 and 12 pairs, 0 under
+    attn4_xcd = 0 and below 8 pairs; 2 for both launches of a planned pair of launches"""
+    modes = {c["id"]: X.expected_xcd_mode(c["B"] * c["H"], c["opts"]) for c in X.G4_CASES}
+    assert modes["g4-xcd2-b3h3"] == modes["g4-xcd2-b2h6-raw"] == 2 and modes["g4-xcd-off"] == 0
+    assert [m for i, m in modes.items() if "-b2h4" in i] == [1, 1]
+    assert all(m == 0 for i, m in modes.items() if "-b2h4" not in i and "xcd2" not in i)
+    assert X.expected_xcd_mode(9, {}, 2) == X.expected_xcd_mode(8, {}, 2) == 2 and X.expected_xcd_mode(1, {}, 2) == 0
+
+
+def test_the_self_attention_route_table():
+    """both sides of every boundary of attn_choose (csrc/attn.hip), by kernel name without a plan; kernel_name asserts that scail_flash_attn_kernel_for
+    agrees, except at the grid limit, which the seven-argument query cannot see: it says 4 on both sides"""
+    name = lambda *a, **kw: X.kernel_name(*a, **kw)
+    for pre in (False, True):                                                                # `prescaled` does not change any answer
+        assert name(128, 128, 128, 1, 1, 256, 511, False, pre) == X.W8 and name(128, 128, 128, 1, 1, 256, 512, False, pre) == X.GEN          # key count
+        assert name(128, 128, 128, 1, 1, 256, 512, True, pre) == X.W8                                                                        # accumulate
+        assert X.with_options({"attn4": 1}, lambda: name(128, 128, 128, 1, 1, 256, 512, False, pre)) == X.GEN                                # option attn4
+        assert X.with_options({"attn4": 0}, lambda: name(128, 128, 128, 1, 1, 256, 512, False, pre)) == X.W8
+        # 32-bit byte offsets inside a slice: 69 905 x 15 360 = 1 073 740 800 < 2^30 <= 69 906 x 15 360, for each of the three row strides
+        assert 69905 * 15360 == 1073740800 < 2 ** 30 <= 69906 * 15360
+        for i in range(3):
+            rs = [128, 128, 128]
+            rs[i] = 15360
+            lens = dict(Lq=256, Lk=512)
+            for n, want in ((69905, X.GEN), (69906, X.W8)):
+                lens["Lk" if i == 1 else "Lq"] = n
+                assert name(*rs, 1, 1, lens["Lq"], lens["Lk"], False, pre) == want, (rs, lens)
+        # the V^T image: 128 (Lk + 63) reaches 2^30 at Lk = 8 388 545 (k_rs = 128: the K offsets stay below it up to Lk = 8 388 607, so this term decides)
+        assert 128 * (8388544 + 63) < 2 ** 30 <= 128 * (8388545 + 63) and 8388544 * 128 < 2 ** 30
+        assert name(128, 128, 128, 1, 1, 256, 8388544, False, pre) == X.GEN and name(128, 128, 128, 1, 1, 256, 8388545, False, pre) == X.W8
+        # the workgroup-id decode: 32 768 heads
+        assert name(128, 128, 128, 1, 32767, 1, 512, False, pre, agree=False) == X.GEN and name(128, 128, 128, 1, 32768, 1, 512, False, pre, agree=False) == X.W8
+        assert name(128, 128, 128, 32767, 1, 1, 512, False, pre, agree=False) == X.GEN and name(128, 128, 128, 32768, 1, 1, 512, False, pre, agree=False) == X.W8
+        assert X.flash_route(128, 128, 128, 1, 512, False, pre) == 4                          # ... the blind spot of the seven-argument query, pinned
+
+
+def test_the_cross_attention_route_table():
+    """both sides of every boundary of cross_choose, by kernel name; cross_kernel_name asserts that scail_cross_attn2_kernel_for agrees"""
+    name = lambda *a, **o: X.with_options(o, lambda: X.cross_kernel_name(*a))
+    D = 256
+    assert name(D, D, D, D, 300, 1024, 256, 2, 2) == X.X_HIP and name(D, D, D, D, 300, 1024, 257, 2, 2) == X.X_GEN          # cross4 = 2 (default): 20 / 21 key tiles
+    assert name(D, D, D, D, 300, 1024, 256, 2, 2, cross4=2) == X.X_HIP and name(D, D, D, D, 300, 1024, 257, 2, 2, cross4=2) == X.X_GEN
+    assert name(D, D, D, D, 300, 1024, 257, 2, 2, cross4=0) == X.X_HIP and name(D, D, D, D, 300, 1024, 256, 2, 2, cross4=1) == X.X_GEN       # option cross4
+    for a, b in ((63, 64), (64, 63)):                                                        # at least one whole key tile per set
+        assert name(D, D, D, D, 300, a, b, 2, 2, cross4=1) == X.X_HIP
+    assert name(D, D, D, D, 300, 64, 64, 2, 2, cross4=1) == X.X_GEN
+    assert name(D, D, 2 * D, D, 300, 1024, 257, 2, 2) == X.X_HIP and name(D, 2 * D, 2 * D, D, 300, 1024, 257, 2, 2) == X.X_GEN            # one K row stride for both sets
+    for cross4 in (0, 1, 2):                                                                 # option attn4 = 0: no generated kernel at all
+        assert name(D, D, D, D, 300, 1024, 257, 2, 2, attn4=0, cross4=cross4) == X.X_HIP
+    assert name(D, D, D, D, 300, 1024, 257, 1, 32767) == X.X_GEN and name(D, D, D, D, 300, 1024, 257, 1, 32768) == X.X_HIP                # the workgroup-id decode
+    # the hipcc kernel's workgroup count needs no device: one per (128-row query block, head, batch element)
+    assert X.cross_kernel_name(D, D, D, D, 300, 512, 257, 2, 2, want_grid=True) == (X.X_HIP, 3 * 2 * 2)
+
+
+def test_name_queries_reject_bad_buffers_and_write_nothing():
+    import ctypes as C
+    from scail_amd import lib as L
+    L.load()
+    small, plan, wg = C.create_string_buffer(b"\x55" * 8, 8), (C.c_int64 * 9)(*([77] * 9)), C.c_int64(77)
+    self_args, cross_args = (128, 128, 128, 1, 1, 256, 64, 0, 1), (256, 256, 256, 256, 300, 512, 257, 2, 2)
+    for fn, args, extra in (("scail_flash_attn_kernel_name_for", self_args, plan), ("scail_cross_attn2_kernel_name_for", cross_args, C.byref(wg))):
+        for e in (None, C.cast(extra, C.c_void_p)):
+            with pytest.raises(L.ScailHipError, match="null argument"):
+                L.call(fn, *args, None, 128, e)
+            with pytest.raises(L.ScailHipError, match="buffer too small"):
+                L.call(fn, *args, small, len(small), e)
+            with pytest.raises(L.ScailHipError, match="buffer too small"):
+                L.call(fn, *args, small, 0, e)
+    assert small.raw == b"\x55" * 8 and list(plan) == [77] * 9 and wg.value == 77
+    with pytest.raises(L.ScailHipError, match="at least one"):
+        L.call("scail_flash_attn_kernel_name_for", 128, 128, 128, 0, 1, 256, 64, 0, 1, small, len(small), None)
+    # the 8-wave kernel's plan needs no device: one launch, a workgroup per (256-row query block, head, batch element)
+    assert X.kernel_name(128, 128, 128, 2, 3, 300, 64, False, True, plan=True) == (X.W8, dict(n_launch=1, launches=[dict(rows=256, item0=0, n_items=12, xcd_mode=0)]))
+    # ... and a forced height's neither
+    got = X.with_options({"attn4_rows": 192}, lambda: X.kernel_name(128, 128, 128, 2, 4, 300, 512, False, True, plan=True))
+    assert got == (X.GEN + "_q3", dict(n_launch=1, launches=[dict(rows=192, item0=0, n_items=16, xcd_mode=1)]))
+
+
 # ---- the fp32 restatements pass --------------------------------------------------------------------------------------------------------------
 def _restate(case, d, mode, **kw):
     return X.online_fp32(d["q"], d["k"].expand(case["B"], -1, -1), d["v"].expand(case["B"], -1, -1), case["H"], X.sl2_of(case), case["n_seg"], mode=mode,

@@ -61,8 +61,33 @@ def all_nan(t):
     return bool(torch.isnan(t.float()).all())
 
 
-def run_self(ops, case, d, opts=None):
-    """one scail_flash_attn_bf16 call of a case under its options (+ opts): the output (B, Lq, D) bf16 on the CPU; asserts the route and the slack"""
+def assert_choice(case, opts, args, variant=None):
+    """the kernels and launches the library says the call runs (the name query with a plan) against the case: the kernel by name, and for the generated
+    kernel the plan -- the forced height, every (pair, query block) item once, the workgroup-id decode -- and scail_flash_attn_rows_for's agreement
+    with it.  Returns the plan."""
+    from scail_amd import lib as L
+    B, H, Lq = case["B"], case["H"], case["Lq"]
+    name, plan = X.kernel_name(*args, plan=True)
+    first = plan["launches"][0]
+    if opts.get("attn4", 1) == 0 or case["route"] == 8:
+        assert name == X.expected_name(dict(case, route=8), variant=variant), name
+        qblk = 128 if variant == 66 else 256
+        assert plan == dict(n_launch=1, launches=[dict(rows=qblk, item0=0, n_items=B * H * -(-Lq // qblk), xcd_mode=0)]), plan
+        return plan
+    rows = L.load().scail_flash_attn_rows_for(B, H, Lq)
+    assert rows == (448 if plan["n_launch"] == 2 else first["rows"]) and name == X.expected_name(case, rows), (name, rows, plan)
+    forced = opts.get("attn4_rows", 0)
+    if forced:
+        assert plan["n_launch"] == 1 and first["rows"] == forced
+    if plan["n_launch"] == 1:
+        assert first["item0"] == 0 and first["n_items"] == B * H * -(-Lq // first["rows"]), plan
+    assert all(l["xcd_mode"] == X.expected_xcd_mode(B * H, opts, plan["n_launch"]) for l in plan["launches"]), plan
+    return plan
+
+
+def run_self(ops, case, d, opts=None, variant=None):
+    """one scail_flash_attn_bf16 call of a case under its options (+ opts): the output (B, Lq, D) bf16 on the CPU; asserts the route, the kernel name
+    (variant: the attn_variant code in force), the launch plan and the slack"""
     B, H, Lq, Ls, S = case["B"], case["H"], case["Lq"], case["Lk"], case["n_seg"]
     D = H * X.HD
     strided, acc = case["form"] == "strided", case["form"] == "accumulate"
@@ -84,6 +109,7 @@ def run_self(ops, case, d, opts=None):
 
     def call():
         assert X.flash_route(q.stride(1), kseg.stride(2), out.stride(1), Lq, Ls, acc, not case["raw"]) == (8 if all_opts.get("attn4", 1) == 0 else case["route"]), case["id"]
+        assert_choice(case, all_opts, (q.stride(1), kseg.stride(2), out.stride(1), B, H, Lq, Ls, acc, not case["raw"]), variant)
         kw = dict(scale=X.raw_scale()) if case["raw"] else dict(q_prescaled=True)
         ops.flash_attn(q, kseg[0], vt[0], out=out, accumulate=acc, n_seg=S, k_seg_stride=kseg.stride(0) if S > 1 else 0, vt_seg_stride=vt.stride(0) if S > 1 else 0,
                        k_broadcast=case["form"] == "bcast", **kw)
@@ -119,7 +145,7 @@ def test_transpose_v_is_the_permutation(ops, Lk, heads):
 @pytest.mark.parametrize("case", X.W8_CASES, ids=lambda c: c["id"])
 def test_8wave_kernel_exact(ops, attn_variant, case):
     d = X.self_case(case)
-    o = run_self(ops, case, d)
+    o = run_self(ops, case, d, variant=attn_variant)
     check_self(o, d, f"{case['id']} variant {attn_variant}")
     if case["Lk"] == 1 and case["n_seg"] == 1:                                               # one key: o = v, bit for bit
         X.assert_bits(o, d["v"].expand(case["B"], 1, -1).expand(-1, case["Lq"], -1).to(BF16), "one key")
@@ -191,6 +217,17 @@ def test_attn4_m16f_planned_two_launch_shape(ops, B, H, Lq0):
 
     def planned():
         assert lib.scail_flash_attn_rows_for(B, H, Lq) == 448
+        name, plan = X.kernel_name(H * X.HD, H * X.HD, H * X.HD, B, H, Lq, 512, False, True, plan=True)
+        print(f"{name}: {plan}")
+        assert name == "scail_attn4_m16f + scail_attn4_m16f_q3" and plan["n_launch"] == 2
+        first, second = plan["launches"]
+        n4, n3 = -(-Lq // 256), -(-Lq // 192)
+        assert (first["rows"], first["item0"], second["rows"]) == (256, 0, 192) and 0 < first["n_items"] < B * H * n4
+        # launch 0 ends, and launch 1 starts, at the same query row of the same pair, a multiple of 768 rows: every row exactly once
+        pair, row = first["n_items"] // n4, first["n_items"] % n4 * 256
+        assert (second["item0"] // n3, second["item0"] % n3 * 192) == (pair, row) and row % 768 == 0
+        assert second["item0"] + second["n_items"] == B * H * n3
+        assert [l["xcd_mode"] for l in plan["launches"]] == ([2, 2] if B * H >= 8 else [0, 0])
         return run_self(ops, case, d)
 
     o = X.with_options({"attn4_cus": cus}, planned)
@@ -217,6 +254,10 @@ def test_cross_attention_exact_on_both_kernels(ops, case, raw):
 
         def call():
             assert X.cross_route(q.stride(1), D, D, D + 64, Lq, case["Lk1"], case["Lk2"], B, H) == (case["route"] if cross4 else 2)
+            name, wgs = X.cross_kernel_name(q.stride(1), D, D, D + 64, Lq, case["Lk1"], case["Lk2"], B, H, want_grid=True)
+            assert name == (X.expected_name(case) if cross4 else X.X_HIP)
+            cus = torch.cuda.get_device_properties(0).multi_processor_count
+            assert wgs == (min(cus, B * H * -(-Lq // 256)) if name == X.X_GEN else B * H * -(-Lq // 128)), (name, wgs)
             ops.cross_attn2(q, k1, vt1, k2, vt2, out=obuf[..., :D], **kw)
             torch.cuda.synchronize()
 
