@@ -260,6 +260,21 @@ int scail_dit_profile_read(scail_dit* h, int category, double* ms_total, int64_t
 #define SCAIL_DIT_FP8_ALL 63u
 int64_t scail_dit_fp8_weight_bytes(const scail_dit* h, uint32_t which);
 int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int64_t bytes, void* stream);
+/*
+ * Scaling of the fp8 GEMMs: one per handle, chosen at enable time.  SCAIL_DIT_FP8_SCALE_ROW is the scheme above; the two functions above
+ * are the ROW forms of the two below.  SCAIL_DIT_FP8_SCALE_MX runs scail_quant_mxfp8_rows + scail_gemm_mxfp8 instead (include/scail_hip.h:
+ * e4m3 codes with one E8M0 scale per aligned block of 32 along K, for activations and weights): an outlier then costs the 31 neighbours of
+ * its block, not the rest of its row.  A block lies inside a row, so the row independence, SCAIL_DIT_CFG_PAIR and the last-layer pruning
+ * hold as under ROW.  Under MX the caller's buffer holds [N, K / 32] scale bytes per matrix where ROW holds N floats
+ * (scail_dit_fp8_weight_bytes_scaled), the block scratch holds rows x (widest fp8 K) / 32 scale bytes where ROW holds rows x 4, and every
+ * workspace query answers for the scaling in force.  scail_dit_fp8_select_layers works unchanged and scail_dit_fp8_probe measures whichever
+ * scaling is enabled, in the same table.  An unknown `scaling` is refused with a message that names it (weight_bytes_scaled: -1).
+ * Switching back to bf16 (which == 0 or buf == NULL) also returns the handle to ROW.
+ */
+#define SCAIL_DIT_FP8_SCALE_ROW 0
+#define SCAIL_DIT_FP8_SCALE_MX 1
+int64_t scail_dit_fp8_weight_bytes_scaled(const scail_dit* h, uint32_t which, int scaling);
+int scail_dit_enable_fp8_scaled(scail_dit* h, uint32_t which, int scaling, void* buf, int64_t bytes, void* stream);
 
 /*
  * Per-layer fp8 selection and the on-device GEMM error probe (both opt-in, both on top of scail_dit_enable_fp8).

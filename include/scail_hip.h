@@ -43,7 +43,8 @@ const char* scail_last_error(void);
  * scail_conv3d_kernel_name_for, for the GEMM query scail_gemm_kernel_name_for, for the uint8 output route, scail_frames_u8 and
  * scail_vae_decode_u8 / scail_vae_decode_stream_u8, for the row-kernel query scail_row_kernel_name_for, for the attention queries
  * scail_flash_attn_kernel_name_for / scail_cross_attn2_kernel_name_for, and for the fp8 probe, scail_rel_err_rows and scail_dit.h's scail_dit_fp8_select_layers /
- * scail_dit_fp8_probe / scail_dit_fp8_probe_bytes.) */
+ * scail_dit_fp8_probe / scail_dit_fp8_probe_bytes, and for MX block scaling of the fp8 GEMMs, scail_quant_mxfp8_rows / scail_gemm_mxfp8 and
+ * scail_dit.h's scail_dit_fp8_weight_bytes_scaled / scail_dit_enable_fp8_scaled.) */
 int scail_abi_version(void);
 
 /* ---- epilogues of scail_gemm_bf16 ---------------------------------------------------------- */
@@ -573,6 +574,30 @@ int scail_gemm_fp8(const uint8_t* x, int64_t lda, const float* sx, const uint8_t
                    scail_bf16* y, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
                    const scail_bf16* resid, int64_t ldr, const float* gate, int64_t gate_stride,
                    int64_t rows_per_batch, void* stream);
+
+/* ---- the same GEMMs with MX block scales (OCP MX: e4m3 codes + one E8M0 byte per aligned block of 32 along K) ------------------
+ * scail_quant_mxfp8_rows: q[r, c] (uint8 e4m3 codes, row stride ldq) and e[r, c / 32] (uint8 E8M0, plain row-major, row stride lde) from
+ *   bf16 x[r, c] (row stride ldx).  Per aligned block of 32 columns, bit-exact for finite input:
+ *     amax = max |x|;
+ *     amax == 0 (-0 included): byte 127 and 32 codes 0x00;
+ *     else s = the smallest integer with amax * 2^-s <= 448, clamped to [-127, 127]: with amax = m * 2^E, 1 <= m < 2, s = E - 8 if
+ *       m <= 1.75, else E - 7 (the exponent that never clips; floor(log2 amax) - 8 would saturate maxima in (448, 512) * 2^s);
+ *     byte = s + 127 (never 255);  q = e4m3fn_rne(clamp(x * 2^-s, -448, 448)).
+ *   The multiplication by a power of two is exact in fp32; the clamp never binds for finite bf16 input and stays as the guard against
+ *   the NaN code.  A -0 element of a non-zero block keeps its sign bit, as in scail_quant_fp8_rows.  Non-finite input: unspecified.
+ *   The row is read once.  cols % 32 == 0, ldx % 8 == 0, ldq % 8 == 0, lde >= cols / 32; x 16-byte, q 8-byte aligned.
+ * scail_gemm_mxfp8: y[M,N] = epilogue(sum_b 2^(ex[m,b] + ew[n,b] - 254) * sum_{k in b} xq[m,k] wq[n,k] + bias[n]), b = the blocks of
+ *   32 along K; the scales are the MFMA's scale operands, the epilogue applies none.  ex is [M, K / 32] with row stride ldex (a multiple
+ *   of 4), ew is [N, K / 32] with row stride K / 32; both 4-byte aligned.  Everything else (shapes, epilogues, tile mapping, the
+ *   alignment of x, w, bias, y, resid, gate) as scail_gemm_fp8; a block lies inside a row, so an output row depends on its own input
+ *   row alone here too.  Other shapes are refused before any launch.
+ */
+int scail_quant_mxfp8_rows(const scail_bf16* x, int64_t ldx, uint8_t* q, int64_t ldq, uint8_t* e, int64_t lde, int64_t rows, int64_t cols,
+                           void* stream);
+int scail_gemm_mxfp8(const uint8_t* x, int64_t lda, const uint8_t* ex, int64_t ldex, const uint8_t* w, const uint8_t* ew, const float* bias,
+                     scail_bf16* y, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
+                     const scail_bf16* resid, int64_t ldr, const float* gate, int64_t gate_stride,
+                     int64_t rows_per_batch, void* stream);
 
 /*
  * scail_rel_err_rows: how far the bf16 matrix b [rows, cols] (row stride ldb) is from a (row stride lda), added to the device

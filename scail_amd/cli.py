@@ -242,11 +242,23 @@ def fp8_max_error_arg(value, gemm_precision):
     return value
 
 
+def fp8_scaling_arg(value, gemm_precision):
+    """``--fp8-scaling`` checked against the network's GEMM precision: "row" or "mx" (lib.FP8_SCALINGS), "mx" only with fp8 GEMMs."""
+    if value is None:
+        return None
+    if value not in lib.FP8_SCALINGS:
+        raise ValueError(f"--fp8-scaling must be one of {sorted(lib.FP8_SCALINGS)}, got {value!r}")
+    if value != "row" and gemm_precision != "fp8":
+        raise ValueError(f"--fp8-scaling {value} needs --gemm-precision fp8 (or gemm_precision: fp8 in the network's yaml): it scales the fp8 GEMMs")
+    return value
+
+
 def format_fp8_table(cal, max_rel_err):
-    """The probe's result as text: one row per layer, one column per GEMM, then the (layer, GEMM) pairs left in bf16."""
+    """The probe's result as text: a heading that names the scaling probed (cal["scaling"]; "row" when absent), one row per layer, one
+    column per GEMM, then the (layer, GEMM) pairs left in bf16."""
     names = list(lib.FP8_GEMMS)
     rel, masks = cal["rel_err"], cal["masks"]
-    out = [f"fp8 probe: relative error of each fp8 GEMM against its bf16 twin (first evaluation), threshold {max_rel_err:g}",
+    out = [f"fp8 probe ({cal.get('scaling', 'row')} scaling): relative error of each fp8 GEMM against its bf16 twin (first evaluation), threshold {max_rel_err:g}",
            "layer " + " ".join(f"{n:>8}" for n in names)]
     for i in range(rel.shape[0]):
         out.append(f"{i:5d} " + " ".join(f"{float(rel[i, g]):8.2e}" for g in range(len(names))))
@@ -376,6 +388,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--gemm-precision", choices=("bf16", "fp8"), default=None,
                     help="precision of the six per-token GEMMs of every block (default: the config's, bf16); fp8 = e4m3 with per-token / "
                          "per-channel scales, single GPU")
+    ap.add_argument("--fp8-scaling", choices=tuple(lib.FP8_SCALINGS), default=None,
+                    help="scaling of the fp8 GEMMs (default: the config's fp8_scaling, row): row = one fp32 scale per token / output "
+                         "channel; mx = OCP MX, one power-of-two scale per block of 32 along K in the matrix instruction, so an outlier "
+                         "channel costs its own block and not its whole row.  Not yet measured on a real checkpoint: compare the "
+                         "--fp8-max-error table under both")
     ap.add_argument("--fp8-max-error", type=float, default=None,
                     help="with fp8 GEMMs: before sampling, run the request's first network evaluation through the executor's error probe "
                          "and keep in bf16 every (layer, GEMM) whose fp8 result is further than this (relative error against its bf16 "
@@ -425,6 +442,11 @@ def main(argv=None):
         cfg = copy.deepcopy(cfg)
         cfg["model"]["network_config"].setdefault("params", {})["gemm_precision"] = a.gemm_precision
     try:                                                                # an argument error before any model is built
+        params = cfg["model"]["network_config"].get("params", {})
+        if fp8_scaling_arg(a.fp8_scaling, params.get("gemm_precision", "bf16")) is not None:
+            if a.gemm_precision is None:
+                cfg = copy.deepcopy(cfg)
+            cfg["model"]["network_config"].setdefault("params", {})["fp8_scaling"] = a.fp8_scaling
         tk["fp8_max_error"] = fp8_max_error_arg(a.fp8_max_error, cfg["model"]["network_config"].get("params", {}).get("gemm_precision", "bf16"))
     except ValueError as e:
         ap.error(str(e))

@@ -34,7 +34,8 @@ struct scail_dit {
     // fp8 GEMMs (scail_dit_enable_fp8): the SCAIL_DIT_FP8_* mask in force and, per layer and GEMM (bit index), the e4m3 weight codes and
     // per-channel scales in the caller's buffer
     uint32_t fp8 = 0;
-    struct Fp8W { const uint8_t* q; const float* s; };
+    int fp8_scaling = SCAIL_DIT_FP8_SCALE_ROW;     // one scaling per handle, chosen at enable time
+    struct Fp8W { const uint8_t* q; const float* s; const uint8_t* e; };   // s: fp32 row scales (ROW); e: E8M0 block scales [N, K / 32] (MX)
     std::vector<std::array<Fp8W, 6>> fp8w;
     // scail_dit_fp8_select_layers: per layer, the subset of `fp8` in force (empty: `fp8` in every layer)
     std::vector<uint32_t> fp8_sel;
@@ -214,8 +215,9 @@ static int probe_check(const scail_dit* h, int64_t rows) {
 // ---- workspaces: every layout is stated once; the *_workspace_bytes query and the call that checks it read the same struct ----
 struct BlockBufs {
     scail_bf16 *xn, *qkv, *att, *ff, *vt;
-    uint8_t* xq;   // fp8 GEMMs only (else null): e4m3 rows of the GEMM input and their scales (rows x the widest fp8 K)
-    float* sx;
+    uint8_t* xq;   // fp8 GEMMs only (else null): e4m3 rows of the GEMM input (rows x the widest fp8 K) and their scales:
+    float* sx;     // rows fp32 (per-row scaling) or, through ex(), rows x (the widest fp8 K) / 32 E8M0 bytes (MX)
+    uint8_t* ex() const { return reinterpret_cast<uint8_t*>(sx); }
 };
 // The scratch of a (B, Ltok) block, xn | qkv | att | ff | vt | xq | sx, as byte offsets into a workspace from `at` on; end: the first
 // byte after it.  One rank (sp_mode < 0) or a sequence-parallel rank (bf16 only: xq / sx are empty there and without fp8 GEMMs)
@@ -239,7 +241,7 @@ static BlockWs block_ws(const scail_dit* h, int64_t B, int64_t Ltok, int sp_mode
     s.ff = c.take(rows * FF * 2);
     s.vt = c.take(vt_elems(h->cfg, B, Ltok, sp_mode, ranks) * 2);
     s.xq = c.take(rows * f8_k);
-    s.sx = c.take(f8_k ? rows * 4 : 0);
+    s.sx = c.take(h->fp8_scaling == SCAIL_DIT_FP8_SCALE_MX ? rows * (f8_k / 32) : f8_k ? rows * 4 : 0);
     s.end = c.off;
     return s;
 }
@@ -280,8 +282,21 @@ static SampleWs sample_ws(int64_t step, int64_t Tv, int64_t H, int64_t W, int64_
     return {step, step + pair, step + 2 * pair, step + 2 * pair + align256(Tden * F * 4)};
 }
 
+// x quantised into the block's scratch and multiplied with the quantised weight f, under the handle's scaling
+static int fp8_quant_gemm(const scail_dit* h, const scail_dit::Fp8W& f, const BlockBufs& bf, const scail_bf16* x, int64_t lda, const float* bias,
+                          scail_bf16* y, int64_t ldc, int64_t M, int64_t N, int64_t K, int epi, const scail_bf16* resid, int64_t ldr,
+                          const float* gate, int64_t gs, int64_t rpb, void* stream) {
+    if (h->fp8_scaling == SCAIL_DIT_FP8_SCALE_MX) {
+        DIT_TRY(scail_quant_mxfp8_rows(x, lda, bf.xq, K, bf.ex(), K / 32, M, K, stream));
+        return scail_gemm_mxfp8(bf.xq, K, bf.ex(), K / 32, f.q, f.e, bias, y, ldc, M, N, K, epi, resid, ldr, gate, gs, rpb, stream);
+    }
+    DIT_TRY(scail_quant_fp8_rows(x, lda, bf.xq, K, bf.sx, M, K, stream));
+    return scail_gemm_fp8(bf.xq, K, bf.sx, f.q, f.s, bias, y, ldc, M, N, K, epi, resid, ldr, gate, gs, rpb, stream);
+}
+
 // GEMM g of layer i: scail_gemm_bf16, or (SCAIL_DIT_FP8_* bit g in force in layer i) the rows of x quantized to e4m3 into the block's
-// scratch and scail_gemm_fp8 on the layer's e4m3 weight; the same epilogue either way.  While the probe is on, a GEMM whose weight is
+// scratch and scail_gemm_fp8 on the layer's e4m3 weight (scail_quant_mxfp8_rows + scail_gemm_mxfp8 under MX scaling: fp8_quant_gemm
+// above); the same epilogue either way.  While the probe is on, a GEMM whose weight is
 // quantised (in force or not) first runs twice on these very rows with the plain bias epilogue -- bf16 and fp8, into the probe's two
 // buffers --, their distance goes to table[i][g], and the real GEMM then runs in bf16.
 static int dit_gemm(scail_dit* h, int64_t i, int g, const BlockBufs& bf, const scail_bf16* x, int64_t lda, const float* bias, scail_bf16* y,
@@ -291,13 +306,10 @@ static int dit_gemm(scail_dit* h, int64_t i, int g, const BlockBufs& bf, const s
     if (quantised && h->probe_table != nullptr) {
         const scail_dit::Fp8W& f = h->fp8w[i][g];
         DIT_TRY(scail_gemm_bf16(x, lda, gemm_weight(h->layers[i], g), bias, h->probe_y16, N, M, N, K, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
-        DIT_TRY(scail_quant_fp8_rows(x, lda, bf.xq, K, bf.sx, M, K, stream));
-        DIT_TRY(scail_gemm_fp8(bf.xq, K, bf.sx, f.q, f.s, bias, h->probe_y8, N, M, N, K, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
+        DIT_TRY(fp8_quant_gemm(h, f, bf, x, lda, bias, h->probe_y8, N, M, N, K, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
         DIT_TRY(scail_rel_err_rows(h->probe_y16, N, h->probe_y8, N, h->probe_table + (i * G_COUNT + g) * 4, M, N, stream));
     } else if (quantised && fp8_in_force(h, i, g)) {
-        const scail_dit::Fp8W& f = h->fp8w[i][g];
-        DIT_TRY(scail_quant_fp8_rows(x, lda, bf.xq, K, bf.sx, M, K, stream));
-        return scail_gemm_fp8(bf.xq, K, bf.sx, f.q, f.s, bias, y, ldc, M, N, K, epi, resid, ldr, gate, gs, rpb, stream);
+        return fp8_quant_gemm(h, h->fp8w[i][g], bf, x, lda, bias, y, ldc, M, N, K, epi, resid, ldr, gate, gs, rpb, stream);
     }
     return scail_gemm_bf16(x, lda, gemm_weight(h->layers[i], g), bias, y, ldc, M, N, K, epi, resid, ldr, gate, gs, rpb, stream);
 }
@@ -624,23 +636,33 @@ extern "C" void scail_dit_destroy(scail_dit* h) {
 }
 
 // ---- fp8 per-token GEMMs (include/scail_dit.h scail_dit_enable_fp8) ----
-// caller buffer layout: for every layer, for every selected GEMM in bit order, the e4m3 codes [N, K] then the fp32 scales [N], each
-// block 256-byte aligned
-static int64_t fp8_weight_bytes(const scail_dit_config& c, uint32_t which) {
+// caller buffer layout: for every layer, for every selected GEMM in bit order, the e4m3 codes [N, K] then the fp32 scales [N] (per-row
+// scaling) or the E8M0 block scales [N, K / 32] (MX), each block 256-byte aligned
+static int64_t fp8_scale_bytes(int scaling, int64_t N, int64_t K) { return scaling == SCAIL_DIT_FP8_SCALE_MX ? N * (K / 32) : N * 4; }
+static int fp8_scaling_check(const char* fn, int scaling) {
+    if (scaling == SCAIL_DIT_FP8_SCALE_ROW || scaling == SCAIL_DIT_FP8_SCALE_MX) return 0;
+    scail_set_error(std::string(fn) + ": unknown scaling " + std::to_string(scaling) + " (SCAIL_DIT_FP8_SCALE_ROW = 0 or SCAIL_DIT_FP8_SCALE_MX = 1)");
+    return 1;
+}
+static int64_t fp8_weight_bytes(const scail_dit_config& c, uint32_t which, int scaling) {
     int64_t per_layer = 0;
     for (int g = 0; g < G_COUNT; ++g)
         if (which & (1u << g)) {
             int64_t N, K;
             gemm_shape(c, g, &N, &K);
-            per_layer += align256(N * K) + align256(N * 4);
+            per_layer += align256(N * K) + align256(fp8_scale_bytes(scaling, N, K));
         }
     return per_layer * c.num_layers;
 }
-extern "C" int64_t scail_dit_fp8_weight_bytes(const scail_dit* h, uint32_t which) {
-    if (h == nullptr || (which & ~(uint32_t)SCAIL_DIT_FP8_ALL) != 0) return -1;
-    return fp8_weight_bytes(h->cfg, which);
+extern "C" int64_t scail_dit_fp8_weight_bytes_scaled(const scail_dit* h, uint32_t which, int scaling) {
+    if (h == nullptr || (which & ~(uint32_t)SCAIL_DIT_FP8_ALL) != 0 || fp8_scaling_check("scail_dit_fp8_weight_bytes_scaled", scaling)) return -1;
+    return fp8_weight_bytes(h->cfg, which, scaling);
 }
-extern "C" int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int64_t bytes, void* stream) {
+extern "C" int64_t scail_dit_fp8_weight_bytes(const scail_dit* h, uint32_t which) {
+    return scail_dit_fp8_weight_bytes_scaled(h, which, SCAIL_DIT_FP8_SCALE_ROW);
+}
+extern "C" int scail_dit_enable_fp8_scaled(scail_dit* h, uint32_t which, int scaling, void* buf, int64_t bytes, void* stream) {
+    if (fp8_scaling_check("scail_dit_enable_fp8_scaled", scaling)) return 1;
     SCAIL_REQUIRE(h != nullptr, "null handle");
     SCAIL_REQUIRE((which & ~(uint32_t)SCAIL_DIT_FP8_ALL) == 0, "unknown SCAIL_DIT_FP8_* bit");
     // a new set of quantised matrices: the per-layer selection and the probe (whose buffers were sized for the old set) start over
@@ -648,6 +670,7 @@ extern "C" int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int
     probe_off(h);
     if (which == 0 || buf == nullptr) {     // back to bf16
         h->fp8 = 0;
+        h->fp8_scaling = SCAIL_DIT_FP8_SCALE_ROW;
         h->fp8w.clear();
         return 0;
     }
@@ -661,9 +684,11 @@ extern "C" int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int
                 return 1;
             }
         }
-    SCAIL_REQUIRE(bytes >= fp8_weight_bytes(h->cfg, which), "buffer too small (scail_dit_fp8_weight_bytes)");
+    SCAIL_REQUIRE(bytes >= fp8_weight_bytes(h->cfg, which, scaling), "buffer too small (scail_dit_fp8_weight_bytes_scaled)");
     SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "buffer must be 256-byte aligned");
     h->fp8 = 0;                             // bf16 until every selected matrix is quantized
+    h->fp8_scaling = SCAIL_DIT_FP8_SCALE_ROW;
+    const bool mx = scaling == SCAIL_DIT_FP8_SCALE_MX;
     h->fp8w.assign(h->cfg.num_layers, {});
     char* p = static_cast<char*>(buf);
     for (int64_t i = 0; i < h->cfg.num_layers; ++i)
@@ -673,15 +698,21 @@ extern "C" int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int
             gemm_shape(h->cfg, g, &N, &K);
             uint8_t* q = reinterpret_cast<uint8_t*>(p);
             float* sc = reinterpret_cast<float*>(p + align256(N * K));
-            p += align256(N * K) + align256(N * 4);
-            if (int rc = scail_quant_fp8_rows(gemm_weight(h->layers[i], g), K, q, K, sc, N, K, stream)) {
+            uint8_t* ec = reinterpret_cast<uint8_t*>(sc);
+            p += align256(N * K) + align256(fp8_scale_bytes(scaling, N, K));
+            if (int rc = mx ? scail_quant_mxfp8_rows(gemm_weight(h->layers[i], g), K, q, K, ec, K / 32, N, K, stream)
+                            : scail_quant_fp8_rows(gemm_weight(h->layers[i], g), K, q, K, sc, N, K, stream)) {
                 h->fp8w.clear();
                 return rc;
             }
-            h->fp8w[i][g] = {q, sc};
+            h->fp8w[i][g] = {q, mx ? nullptr : sc, mx ? ec : nullptr};
         }
     h->fp8 = which;
+    h->fp8_scaling = scaling;
     return 0;
+}
+extern "C" int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int64_t bytes, void* stream) {
+    return scail_dit_enable_fp8_scaled(h, which, SCAIL_DIT_FP8_SCALE_ROW, buf, bytes, stream);
 }
 
 extern "C" int scail_dit_fp8_select_layers(scail_dit* h, const uint32_t* masks) {

@@ -5,6 +5,9 @@
 //                         v_mfma_scale_f32_32x32x64_f8f6f4 (twice the bf16 matrix rate per clock), bf16 out.
 // The E8M0 block scales of the MFMA are held at the unit value (127): the per-row fp32 scales are applied in the epilogue, so every
 // output row still depends on its own input row alone (what keeps the executor's CFG-pair and last-layer prunings exact).
+//   scail_quant_mxfp8_rows  bf16 [R, C] -> e4m3 [R, C] + one E8M0 byte per aligned block of 32 columns (the OCP MX layout)
+//   scail_gemm_mxfp8        the same GEMM kernel with the block scales in the MFMA's scale operands and no fp32 scales in the epilogue;
+//                           a block lies inside a row, so the row independence above holds here too.
 #include "common.h"
 #include "gemm_epi.h"
 
@@ -64,6 +67,59 @@ extern "C" int scail_quant_fp8_rows(const scail_bf16* x, int64_t ldx, uint8_t* q
     hipLaunchKernelGGL(scail_quant_fp8_rows_kernel, dim3((unsigned)rows), dim3(QF8_THREADS), 0, (hipStream_t)stream,
                        reinterpret_cast<const u16*>(x), ldx, q, ldq, s, (int)cols);
     return scail_check_launch("scail_quant_fp8_rows");
+}
+
+// ---- MX block quantization (include/scail_hip.h scail_quant_mxfp8_rows) ------------------------------------------------------------
+// One lane per 8 columns (a 16-byte load), the 4 lanes of an aligned quad hold one block of 32: the block's amax is two xor shuffles away
+// and the row is read once.  The lanes are laid over the [rows, cols / 8] chunks linearly, so every shape fills its workgroups; cols % 32
+// == 0 keeps a quad inside one row and makes the tail of the last workgroup whole quads.  Numerics (bit-exact, tests/test_mxfp8_gpu.py):
+//   amax == 0: byte 127, codes 0;  else amax = m 2^E (1 <= m < 2), s = E - 8 + (m > 1.75) clamped to >= -127 (the smallest s with
+//   amax 2^-s <= 448), byte s + 127, q = e4m3_rne(clamp(x 2^-s, -448, 448)).  E and m are read from amax's fp32 bits; a subnormal amax
+//   (biased exponent 0) lands below the clamp either way.  2^-s has the biased exponent 127 - s in [7, 254]: a normal fp32.
+#define QMX_THREADS 256
+__global__ __launch_bounds__(QMX_THREADS) void scail_quant_mxfp8_rows_kernel(const u16* __restrict__ x, int64_t ldx, u8* __restrict__ q,
+                                                                             int64_t ldq, u8* __restrict__ e, int64_t lde, int64_t chunks,
+                                                                             int cpr) {
+    const int64_t i = (int64_t)blockIdx.x * QMX_THREADS + threadIdx.x;
+    if (i >= chunks) return;          // whole quads leave together
+    const int64_t r = i / cpr;
+    const int c = (int)(i - r * cpr) * 8;
+    float f[8];
+    unpack8(*reinterpret_cast<const uint4*>(x + r * ldx + c), f);
+    float amax = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) amax = fmaxf(amax, fabsf(f[k]));
+    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+    const bool zero = amax == 0.f;
+    const uint32_t bits = __float_as_uint(amax);
+    int s = (int)(bits >> 23) - 127 - 8 + ((bits & 0x7fffffu) > 0x600000u ? 1 : 0);
+    s = zero ? 0 : max(s, -127);
+    const float rs = __uint_as_float((uint32_t)(127 - s) << 23);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = fminf(fmaxf(f[k] * rs, -448.0f), 448.0f);
+    int lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+    int hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+    *reinterpret_cast<uint2*>(q + r * ldq + c) = zero ? make_uint2(0u, 0u) : make_uint2((uint32_t)lo, (uint32_t)hi);
+    if ((threadIdx.x & 3) == 0) e[r * lde + (c >> 5)] = (u8)(s + 127);
+}
+
+extern "C" int scail_quant_mxfp8_rows(const scail_bf16* x, int64_t ldx, uint8_t* q, int64_t ldq, uint8_t* e, int64_t lde, int64_t rows,
+                                      int64_t cols, void* stream) {
+    SCAIL_REQUIRE(x != nullptr && q != nullptr && e != nullptr, "null pointer");
+    SCAIL_REQUIRE(rows >= 0 && cols > 0 && cols % 32 == 0 && cols < (1ll << 30), "cols must be a positive multiple of 32");
+    SCAIL_REQUIRE(ldx >= cols && ldq >= cols && ldx % 8 == 0 && ldq % 8 == 0, "ldx / ldq must be >= cols and multiples of 8");
+    SCAIL_REQUIRE(lde >= cols / 32, "lde must be >= cols / 32");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(q) & 7) == 0, "pointer alignment (x 16 B, q 8 B)");
+    SCAIL_REQUIRE(rows < (1ll << 31), "too many rows");
+    const int64_t cpr = cols / 8, chunks = rows * cpr, wgs = (chunks + QMX_THREADS - 1) / QMX_THREADS;
+    SCAIL_REQUIRE(wgs < (1ll << 31), "too many elements (rows * cols / 2048 must stay below 2^31)");
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(scail_quant_mxfp8_rows_kernel, dim3((unsigned)wgs), dim3(QMX_THREADS), 0, (hipStream_t)stream,
+                       reinterpret_cast<const u16*>(x), ldx, q, ldq, e, lde, chunks, (int)cpr);
+    return scail_check_launch("scail_quant_mxfp8_rows");
 }
 
 // ---- relative error of two bf16 matrices (the executor's fp8 probe, include/scail_hip.h scail_rel_err_rows) -------------------------
@@ -177,22 +233,35 @@ extern "C" int scail_rel_err_rows(const scail_bf16* a, int64_t lda, const scail_
 // (r = l & 31, g = l >> 5) of a 32x32x64 step feeds the 32 bytes k = 32 g .. 32 g + 31 of row r of each operand.  A and B take the same
 // k subset per lane, so the dot product is right whatever order the hardware gives those 32 k inside the step (the block scales are
 // all 1); the exact-integer test with an asymmetric W proves the row / column map.
+// MX instantiation (scail_gemm_mxfp8): lane (r, g) passes the E8M0 byte of block g of the step as its scale operand; the hardware applies
+// it to the first (g = 0) or second (g = 1) 16 bytes of both lanes of row r, so this instantiation deals the bytes accordingly (foff below).
+// The 4 blocks of a row's k-tile are one aligned dword of the row-major scale matrix.  The scale dwords are staged with the tile: 4 KB of
+// LDS behind the tiles, [2][512] dwords = x rows 0 .. 255 then W rows 0 .. 255 of the tile, filled by ONE global_load_lds_dword per wave
+// and k-tile (lane -> row 64 wave + lane) next to the tile's own DMA and retired by the same vmcnt(0) + barrier: still one barrier per
+// k-tile.  A lane reads the dword of each of its 2 + 4 fragment rows (ds_read_b32, consecutive rows: no bank conflict) and extracts byte
+// 2 ks + g with a bit-field extract (the index depends on the lane, so it cannot be the instruction's op_sel).  The epilogue then applies
+// no scales.  (First form: every lane loaded its six dwords from global memory, 6 scattered loads of 32 cache lines each per wave and
+// k-tile; it ran at 1.36 - 1.46 x the per-row kernel's time, profiles/fp8_mx_ab_global_scale_loads.log.)  The per-row instantiation takes
+// none of this: it compiles to the instructions it had before.
 #define F8_BK 128
 #define F8_GROUP_M 4
 
 struct GemmFp8Params {
     GemmParams e;                  // epilogue part (x / w unused)
     const u8* x; const u8* w;      // e4m3 [M, lda], [N, K]
-    const float* sx; const float* sw;
+    const float* sx; const float* sw;   // per-row instantiation: fp32 scales [M], [N]
+    const u8* ex; const u8* ew;         // MX instantiation: E8M0 block scales [M, ldex], [N, K / 32]
+    int64_t ldex;
 };
 
-template <int EPI>
+template <int EPI, bool MX>
 __global__ __launch_bounds__(512) void scail_gemm_fp8_kernel(GemmFp8Params P) {
     constexpr int BM = 256, BN = 256, WN = 4, NT = 512;
     constexpr int WTM = 128, WTN = 64, MI = WTM / 32, NI = WTN / 32;
     extern __shared__ __attribute__((aligned(16))) u8 smem8[];
     u8* Xs = smem8;                   // [2][BM][F8_BK]
     u8* Ws = smem8 + 2 * BM * F8_BK;  // [2][BN][F8_BK]
+    uint32_t* Ss = reinterpret_cast<uint32_t*>(smem8 + 2 * (BM + BN) * F8_BK);   // MX only: [2][BM + BN] scale dwords of the k-tile
     const GemmParams& p = P.e;
 
     // ---- tile mapping: XCD-aware bijective remap, then groups of F8_GROUP_M m-tiles sweeping n ----
@@ -242,12 +311,17 @@ __global__ __launch_bounds__(512) void scail_gemm_fp8_kernel(GemmFp8Params P) {
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcw[i_] + (k0_)),          \
                 (__attribute__((address_space(3))) void*)(Ws + ((buf_) * BN + 8 * (wave * PB + i_)) * F8_BK), 16, 0, 0);  \
     }
-    // fragment-read byte offsets in this lane's row: k-step ks, 16-byte half hf -> chunk 4 ks + 2 g + hf, swizzled
+    // fragment-read byte offsets in this lane's row: k-step ks, 16-byte half hf -> chunk 4 ks + 2 g + hf, swizzled.
+    // MX: chunk 4 ks + 2 hf + g instead.  The hardware takes the scale that lane (r, h) supplies for the register half h (registers
+    // 4 h .. 4 h + 3) of BOTH lanes (r, 0) and (r, 1) -- a step is two K = 32 halves, a lane holds 16 bytes of each --, so the block
+    // k = 32 h .. 32 h + 31 of a step has to sit in half h of the two lanes: lane (r, g) takes bytes 16 g .. 16 g + 15 of either block.
+    // (Found on the device: with contiguous 32 bytes per lane, one raised scale byte still moves the right row by the right amount,
+    // but it scales bytes {0..15, 32..47} or {16..31, 48..63} of the step.)
     int foff[2][2];
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int hf = 0; hf < 2; ++hf) foff[ks][hf] = ((4 * ks + 2 * g + hf) ^ ((l31 >> 1) & 7)) << 4;
+        for (int hf = 0; hf < 2; ++hf) foff[ks][hf] = ((4 * ks + (MX ? 2 * hf + g : 2 * g + hf)) ^ ((l31 >> 1) & 7)) << 4;
 
     f32x16 acc[NI][MI];
 #pragma unroll
@@ -258,12 +332,34 @@ __global__ __launch_bounds__(512) void scail_gemm_fp8_kernel(GemmFp8Params P) {
             for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
 
     const int nk = p.K / F8_BK;
+    // MX: this lane's row of the scale stage, 64 wave + lane: waves 0 .. 3 the x rows, 4 .. 7 the W rows (rows past M / N read the last
+    // row's scales, as they read its codes)
+    static_assert(BM == 256 && BN == 256 && NT == 512, "one scale row per thread");
+    const u8* srcs = nullptr;
+    if constexpr (MX) {
+        const int r = (wave & 3) * 64 + lane;
+        srcs = wave < 4 ? P.ex + (int64_t)min(m0 + r, p.M - 1) * P.ldex : P.ew + (int64_t)min(n0 + r, p.N - 1) * (p.K / 32);
+    }
+#define F8_SCALE_DMA(k0_, buf_)                                                                                            \
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcs + ((k0_) >> 5)),                \
+        (__attribute__((address_space(3))) void*)(Ss + (buf_) * (BM + BN) + 64 * wave), 4, 0, 0);
+    if constexpr (MX) F8_SCALE_DMA(0, 0)
     F8_DMA(0, 0)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     for (int t = 0; t < nk; ++t) {
         const int cur = t & 1;
-        if (t + 1 < nk) F8_DMA((t + 1) * F8_BK, cur ^ 1)
+        if (t + 1 < nk) {
+            F8_DMA((t + 1) * F8_BK, cur ^ 1)
+            if constexpr (MX) F8_SCALE_DMA((t + 1) * F8_BK, cur ^ 1)
+        }
+        uint32_t sc[NI + MI];          // MX: the scale dwords of this lane's fragment rows, W then x
+        if constexpr (MX) {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) sc[i] = Ss[cur * (BM + BN) + BM + wn * WTN + i * 32 + l31];
+#pragma unroll
+            for (int i = 0; i < MI; ++i) sc[NI + i] = Ss[cur * (BM + BN) + wm * WTM + i * 32 + l31];
+        }
         const u8* xs = Xs + (cur * BM + wm * WTM + l31) * F8_BK;
         const u8* ws = Ws + (cur * BN + wn * WTN + l31) * F8_BK;
 #pragma unroll
@@ -284,38 +380,48 @@ __global__ __launch_bounds__(512) void scail_gemm_fp8_kernel(GemmFp8Params P) {
 #pragma unroll
             for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-                for (int mi = 0; mi < MI; ++mi)
-                    acc[ni][mi] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[ni], xf[mi], acc[ni][mi], 0, 0, 0, 127, 0, 127);
+                for (int mi = 0; mi < MI; ++mi) {
+                    if constexpr (MX)
+                        acc[ni][mi] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[ni], xf[mi], acc[ni][mi], 0, 0, 0,
+                                                                                     (int)((sc[ni] >> (16 * ks + 8 * g)) & 0xffu), 0,
+                                                                                     (int)((sc[NI + mi] >> (16 * ks + 8 * g)) & 0xffu));
+                    else
+                        acc[ni][mi] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[ni], xf[mi], acc[ni][mi], 0, 0, 0, 127, 0, 127);
+                }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     }
 #undef F8_DMA
+#undef F8_SCALE_DMA
 
     // per-token x per-channel scales: acc[ni][mi][4 rr + e] is (m = .. + l31, n = .. + 8 rr + 4 g + e); v = (acc * sx[m]) * sw[n]
+    if constexpr (!MX) {
 #pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
+        for (int ni = 0; ni < NI; ++ni)
 #pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const int n = n0 + wn * WTN + ni * 32 + 8 * rr + 4 * g;
-            const float4 swn = n < p.N ? *reinterpret_cast<const float4*>(P.sw + n) : make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int rr = 0; rr < 4; ++rr) {
+                const int n = n0 + wn * WTN + ni * 32 + 8 * rr + 4 * g;
+                const float4 swn = n < p.N ? *reinterpret_cast<const float4*>(P.sw + n) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                const float sxm = P.sx[min(m0 + wm * WTM + mi * 32 + l31, p.M - 1)];
-                acc[ni][mi][4 * rr + 0] = acc[ni][mi][4 * rr + 0] * sxm * swn.x;
-                acc[ni][mi][4 * rr + 1] = acc[ni][mi][4 * rr + 1] * sxm * swn.y;
-                acc[ni][mi][4 * rr + 2] = acc[ni][mi][4 * rr + 2] * sxm * swn.z;
-                acc[ni][mi][4 * rr + 3] = acc[ni][mi][4 * rr + 3] * sxm * swn.w;
+                for (int mi = 0; mi < MI; ++mi) {
+                    const float sxm = P.sx[min(m0 + wm * WTM + mi * 32 + l31, p.M - 1)];
+                    acc[ni][mi][4 * rr + 0] = acc[ni][mi][4 * rr + 0] * sxm * swn.x;
+                    acc[ni][mi][4 * rr + 1] = acc[ni][mi][4 * rr + 1] * sxm * swn.y;
+                    acc[ni][mi][4 * rr + 2] = acc[ni][mi][4 * rr + 2] * sxm * swn.z;
+                    acc[ni][mi][4 * rr + 3] = acc[ni][mi][4 * rr + 3] * sxm * swn.w;
+                }
             }
-        }
+    }
     gemm_epilogue<EPI, MI, NI, WTM, WTN>(acc, p, m0, n0, wm, wn, l31, g);
 }
 
-template <int EPI>
+template <int EPI, bool MX>
 static int launch_gemm_fp8(const GemmFp8Params& P, hipStream_t stream) {
-    constexpr int lds = 2 * (256 + 256) * F8_BK;   // 128 KB
+    constexpr int lds = 2 * (256 + 256) * F8_BK + (MX ? 2 * (256 + 256) * 4 : 0);   // 128 KB (+ 4 KB of staged block scales)
     const int tiles = ((P.e.M + 255) / 256) * ((P.e.N + 255) / 256);
-    return scail_launch_lds<scail_gemm_fp8_kernel<EPI>>("scail_gemm_fp8", lds, dim3((unsigned)tiles), dim3(512), lds, stream, P);
+    return scail_launch_lds<scail_gemm_fp8_kernel<EPI, MX>>(MX ? "scail_gemm_mxfp8" : "scail_gemm_fp8", lds, dim3((unsigned)tiles), dim3(512),
+                                                            lds, stream, P);
 }
 
 extern "C" int scail_gemm_fp8(const uint8_t* x, int64_t lda, const float* sx, const uint8_t* w, const float* sw, const float* bias,
@@ -344,13 +450,53 @@ extern "C" int scail_gemm_fp8(const uint8_t* x, int64_t lda, const float* sx, co
     p.resid = reinterpret_cast<const u16*>(resid); p.ldr = ldr; p.gate = gate; p.gate_stride = gate_stride; p.rows_per_batch = rows_per_batch;
     p.group_m = F8_GROUP_M;
     P.x = x; P.w = w; P.sx = sx; P.sw = sw;
+    P.ex = nullptr; P.ew = nullptr; P.ldex = 0;
     hipStream_t s = (hipStream_t)stream;
     switch (epilogue) {
-        case SCAIL_EPI_BIAS: return launch_gemm_fp8<SCAIL_EPI_BIAS>(P, s);
-        case SCAIL_EPI_GELU_TANH: return launch_gemm_fp8<SCAIL_EPI_GELU_TANH>(P, s);
-        case SCAIL_EPI_RESID: return launch_gemm_fp8<SCAIL_EPI_RESID>(P, s);
+        case SCAIL_EPI_BIAS: return launch_gemm_fp8<SCAIL_EPI_BIAS, false>(P, s);
+        case SCAIL_EPI_GELU_TANH: return launch_gemm_fp8<SCAIL_EPI_GELU_TANH, false>(P, s);
+        case SCAIL_EPI_RESID: return launch_gemm_fp8<SCAIL_EPI_RESID, false>(P, s);
         default:
             scail_set_error("scail_gemm_fp8: epilogue must be SCAIL_EPI_BIAS, SCAIL_EPI_GELU_TANH or SCAIL_EPI_RESID");
+            return 1;
+    }
+}
+
+extern "C" int scail_gemm_mxfp8(const uint8_t* x, int64_t lda, const uint8_t* ex, int64_t ldex, const uint8_t* w, const uint8_t* ew,
+                                const float* bias, scail_bf16* y, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
+                                const scail_bf16* resid, int64_t ldr, const float* gate, int64_t gate_stride, int64_t rows_per_batch,
+                                void* stream) {
+    SCAIL_REQUIRE(x != nullptr && ex != nullptr && w != nullptr && ew != nullptr && y != nullptr, "null pointer");
+    SCAIL_REQUIRE(M >= 1 && M < (1ll << 31), "M must be >= 1");
+    SCAIL_REQUIRE(N > 0 && N % 128 == 0 && N < (1ll << 31), "N must be a positive multiple of 128");
+    SCAIL_REQUIRE(K > 0 && K % 128 == 0 && K < (1ll << 31), "K must be a positive multiple of 128");
+    SCAIL_REQUIRE(lda >= K && lda % 16 == 0 && ldc >= N && ldc % 4 == 0, "lda must be >= K and a multiple of 16, ldc >= N and a multiple of 4");
+    SCAIL_REQUIRE(ldex >= K / 32 && ldex % 4 == 0, "ldex must be >= K / 32 and a multiple of 4");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0 &&
+                      (reinterpret_cast<uintptr_t>(ex) & 3) == 0 && (reinterpret_cast<uintptr_t>(ew) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(y) & 7) == 0 && (reinterpret_cast<uintptr_t>(bias) & 15) == 0,
+                  "pointer alignment (x, w, bias 16 B; y 8 B; ex, ew 4 B)");
+    if (epilogue == SCAIL_EPI_RESID) {
+        SCAIL_REQUIRE(resid != nullptr && ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(resid) & 7) == 0, "RESID epilogue needs resid with ldr % 4 == 0");
+        SCAIL_REQUIRE(gate == nullptr || (rows_per_batch > 0 && gate_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(gate) & 15) == 0),
+                      "gate needs rows_per_batch > 0, gate_stride % 4 == 0");
+    }
+    GemmFp8Params P;
+    GemmParams& p = P.e;
+    p.x = nullptr; p.lda = lda; p.w = nullptr; p.bias = bias;
+    p.y = reinterpret_cast<u16*>(y); p.ldc = ldc;
+    p.M = (int)M; p.N = (int)N; p.K = (int)K;
+    p.resid = reinterpret_cast<const u16*>(resid); p.ldr = ldr; p.gate = gate; p.gate_stride = gate_stride; p.rows_per_batch = rows_per_batch;
+    p.group_m = F8_GROUP_M;
+    P.x = x; P.w = w; P.sx = nullptr; P.sw = nullptr;
+    P.ex = ex; P.ew = ew; P.ldex = ldex;
+    hipStream_t s = (hipStream_t)stream;
+    switch (epilogue) {
+        case SCAIL_EPI_BIAS: return launch_gemm_fp8<SCAIL_EPI_BIAS, true>(P, s);
+        case SCAIL_EPI_GELU_TANH: return launch_gemm_fp8<SCAIL_EPI_GELU_TANH, true>(P, s);
+        case SCAIL_EPI_RESID: return launch_gemm_fp8<SCAIL_EPI_RESID, true>(P, s);
+        default:
+            scail_set_error("scail_gemm_mxfp8: epilogue must be SCAIL_EPI_BIAS, SCAIL_EPI_GELU_TANH or SCAIL_EPI_RESID");
             return 1;
     }
 }

@@ -81,26 +81,32 @@ class CStep:
         self._fp8_buf = None
         self._probe = None                               # (table, scratch) while the fp8 probe is on
         self.num_layers = net.num_layers
+        self.fp8_scaling = getattr(net, "fp8_scaling", "row")   # lib.FP8_SCALINGS key that enable_fp8 uses when none is given
         if getattr(net, "fp8_mask", 0):
             self.enable_fp8(net.fp8_mask, W["patch_w"].device)
             if getattr(net, "fp8_layer_masks", None) is not None:
                 self.select_fp8_layers(net.fp8_layer_masks)
 
-    def enable_fp8(self, which: int, device) -> None:
-        """scail_dit_enable_fp8: quantize the selected per-token GEMM weights (lib.FP8_GEMMS bits) into a buffer this object owns;
-        which = 0 returns to bf16."""
+    def enable_fp8(self, which: int, device, scaling=None) -> None:
+        """scail_dit_enable_fp8_scaled: quantize the selected per-token GEMM weights (lib.FP8_GEMMS bits) into a buffer this object owns,
+        under ``scaling`` ("row" | "mx", lib.FP8_SCALINGS; None: the network's); which = 0 returns to bf16."""
         lib = L.load()
+        scaling = self.fp8_scaling if scaling is None else scaling
+        if scaling not in L.FP8_SCALINGS:
+            raise L.ScailHipError(f"enable_fp8: scaling must be one of {sorted(L.FP8_SCALINGS)}, got {scaling!r}")
+        sc = L.FP8_SCALINGS[scaling]
         self._probe = None                               # the executor turns the probe off and forgets the per-layer selection
         if not which:
             L.call("scail_dit_enable_fp8", self._h, 0, None, 0, torch.cuda.current_stream(device).cuda_stream)
             self._fp8_buf = None
             return
-        nbytes = lib.scail_dit_fp8_weight_bytes(self._h, which)
+        nbytes = lib.scail_dit_fp8_weight_bytes_scaled(self._h, which, sc)
         if nbytes < 0:
-            raise L.ScailHipError(f"scail_dit_fp8_weight_bytes: bad mask {which}")
+            raise L.ScailHipError(f"scail_dit_fp8_weight_bytes_scaled: bad mask {which}")
         buf = torch.empty(nbytes, device=device, dtype=torch.uint8)
-        L.call("scail_dit_enable_fp8", self._h, which, buf.data_ptr(), nbytes, torch.cuda.current_stream(device).cuda_stream)
+        L.call("scail_dit_enable_fp8_scaled", self._h, which, sc, buf.data_ptr(), nbytes, torch.cuda.current_stream(device).cuda_stream)
         self._fp8_buf = buf
+        self.fp8_scaling = scaling
 
     def select_fp8_layers(self, masks) -> None:
         """scail_dit_fp8_select_layers: ``masks`` = one lib.FP8_GEMMS mask per layer, each a subset of the enabled mask (the GEMMs that

@@ -88,6 +88,16 @@ def _fp8_options(gemm_precision, fp8_gemms):
     return "fp8", mask
 
 
+def _fp8_scaling_option(fp8_scaling, gemm_precision):
+    """The constructor option ``fp8_scaling``: "row" (one fp32 scale per row, the default) or "mx" (OCP MX: one E8M0 scale per block of
+    32 along K; include/scail_dit.h SCAIL_DIT_FP8_SCALE_*).  "mx" needs gemm_precision='fp8'."""
+    if fp8_scaling not in L.FP8_SCALINGS:
+        raise ValueError(f"fp8_scaling must be one of {sorted(L.FP8_SCALINGS)}, got {fp8_scaling!r}")
+    if fp8_scaling != "row" and gemm_precision != "fp8":
+        raise ValueError(f"fp8_scaling={fp8_scaling!r} needs gemm_precision='fp8'")
+    return fp8_scaling
+
+
 def _fp8_layer_options(fp8_layers, num_layers, mask):
     """Per-layer SCAIL_DIT_FP8_* masks from the constructor option ``fp8_layers`` (None: no per-layer selection): one entry per layer,
     each the mask itself (0 = that layer stays bf16) or an iterable / string of names from lib.FP8_GEMMS, and a subset of ``mask``
@@ -162,7 +172,7 @@ class DiffusionTransformer(nn.Module):
                  parallel_output=True, height_interpolation=1.0, width_interpolation=1.0, time_interpolation=1.0,
                  use_SwiGLU=False, use_RMSNorm=False, cfg_embed_dim=None, ofs_embed_dim=None,
                  layernorm_epsilon=1e-6, inner_hidden_size=None, use_i2v_clip=False, dtype="bf16",
-                 device=None, init_seed=1234, gemm_precision="bf16", fp8_gemms=None, fp8_layers=None, **kwargs):
+                 device=None, init_seed=1234, gemm_precision="bf16", fp8_gemms=None, fp8_layers=None, fp8_scaling="row", **kwargs):
         super().__init__()
         # ---- options of the reference class this engine does not implement: fail loudly ----
         unsupported = []
@@ -215,6 +225,7 @@ class DiffusionTransformer(nn.Module):
                 raise NotImplementedError(f"{nm} must be a multiple of {mult}")
         # opt-in fp8 (e4m3) per-token GEMMs (include/scail_dit.h scail_dit_enable_fp8); a yaml sets them through network_config.params
         self.gemm_precision, self.fp8_mask = _fp8_options(gemm_precision, fp8_gemms)
+        self.fp8_scaling = _fp8_scaling_option(fp8_scaling, self.gemm_precision)
         # fp8_layers: which of those GEMMs stay fp8 in each layer (scail_dit_fp8_select_layers); None = all of them in every layer
         self.fp8_layer_masks = _fp8_layer_options(fp8_layers, num_layers, self.fp8_mask)
         self.fp8_probe_table = None        # the raw (layers, 6, 4) table of the last fp8_probe()

@@ -73,6 +73,9 @@ SIGNATURES = {
     "scail_quant_fp8_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _p],
     "scail_gemm_fp8": [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _i64, _p, _i64, _i64, _p],
     "scail_rel_err_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _p],
+    # MX block scaling: E8M0 bytes [rows, cols / 32] beside the e4m3 codes
+    "scail_quant_mxfp8_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p],
+    "scail_gemm_mxfp8": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _i64, _p, _i64, _i64, _p],
     "scail_resize_crop_aa": [_p, _i, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
     "scail_pose_half": [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p],
     # include/scail_dit.h (structs are passed by pointer; scail_amd/cstep.py builds them)
@@ -102,6 +105,9 @@ SIGNATURES = {
     "scail_dit_sample_tiled": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _p],
     "scail_dit_fp8_weight_bytes": [_p, C.c_uint32],
     "scail_dit_enable_fp8": [_p, C.c_uint32, _p, _i64, _p],
+    # the same two with the scaling (FP8_SCALINGS) named
+    "scail_dit_fp8_weight_bytes_scaled": [_p, C.c_uint32, _i],
+    "scail_dit_enable_fp8_scaled": [_p, C.c_uint32, _i, _p, _i64, _p],
     # per-layer fp8 selection (host uint32 masks [num_layers]) and the on-device GEMM error probe (device fp64 table [layers][6][4])
     "scail_dit_fp8_select_layers": [_p, _p],
     "scail_dit_fp8_probe_bytes": [_p, _i64, _i64],
@@ -119,7 +125,8 @@ SIGNATURES = {
     "scail_vae_decode_stream_u8": [_p, _p, _p, _i64, _i64, _i64, _i64, _p, _i64, _p],
 }
 # return types other than the int status: every *_bytes query answers an int64_t, the destroy functions nothing
-RESTYPES = {"scail_dit_destroy": None, "scail_vae_destroy": None, **{n: _i64 for n in SIGNATURES if n.endswith("_bytes")}}
+RESTYPES = {"scail_dit_destroy": None, "scail_vae_destroy": None, "scail_dit_fp8_weight_bytes_scaled": _i64,
+            **{n: _i64 for n in SIGNATURES if n.endswith("_bytes")}}
 
 # include/scail_hip_ablation.h: only libscail_hip_abl.so (SCAIL_ABLATIONS=1) exports these
 ABLATION_SIGNATURES = {
@@ -135,6 +142,8 @@ ROW_LN_MODULATE, ROW_LN_AFFINE, ROW_RMSNORM, ROW_RMSNORM_ROPE, ROW_COPY = 0, 1, 
 # include/scail_dit.h SCAIL_DIT_FP8_*: the per-token GEMMs of a block that scail_dit_enable_fp8 switches to fp8
 FP8_GEMMS = {"qkv": 1, "o": 2, "cq": 4, "co": 8, "w1": 16, "w2": 32}
 FP8_ALL = 63
+# include/scail_dit.h SCAIL_DIT_FP8_SCALE_*: one fp32 scale per row, or OCP MX (one E8M0 scale per block of 32 along K)
+FP8_SCALINGS = {"row": 0, "mx": 1}
 # include/scail_hip.h scail_resize_crop_aa: source layouts, and the largest in / out per axis its tap budget covers
 SRC_U8_NHWC, SRC_F32_NCHW = 0, 1
 RESIZE_MAX_SCALE = 16
@@ -145,7 +154,8 @@ ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- sc
                          # scail_frames_u8 / scail_vae_decode_u8 / scail_vae_decode_stream_u8, and the row-kernel query
                          # scail_row_kernel_name_for, the attention queries scail_flash_attn_kernel_name_for /
                          # scail_cross_attn2_kernel_name_for, and the fp8 probe and per-layer selection, scail_rel_err_rows /
-                         # scail_dit_fp8_select_layers / scail_dit_fp8_probe / scail_dit_fp8_probe_bytes)
+                         # scail_dit_fp8_select_layers / scail_dit_fp8_probe / scail_dit_fp8_probe_bytes, and MX block scaling,
+                         # scail_quant_mxfp8_rows / scail_gemm_mxfp8 / scail_dit_fp8_weight_bytes_scaled / scail_dit_enable_fp8_scaled)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);
