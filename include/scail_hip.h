@@ -479,6 +479,11 @@ int scail_frames_u8(const scail_bf16* x, int64_t ldx, uint8_t* out, int64_t row_
  * bucket int32 [Lq, Lk] + bias_tab fp32 [n_buckets, heads]: T5 relative-position bias (umt5.py:224-268, 101-113);
  * key_mask int32 [n_batch, key_mask_bs]: 0 -> key excluded (umt5.py:106-110).  CLIP: no bias/mask, scale
  * 1/sqrt(head_dim) (clip.py:96-103).
+ * Precondition: every batch element of key_mask has at least one non-zero entry among its Lk keys.  A fully masked row has
+ * max = -inf, -inf - -inf in every exponent, and comes back as NaN; the entry point does not look at the mask's contents.  The
+ * callers keep it: the only masks are the tokenizer's attention masks, and `</s>` is always there, the empty prompt included
+ * (tests/test_conditioner_mask_cpu.py).  K and V of one head must fit in LDS: Lk * (4 * head_dim + 32) + 16 * head_dim <= 163 840
+ * bytes (512 keys at head_dim 64, 297 at 128), else the call is refused before any launch.
  */
 int scail_attn_small(const scail_bf16* q, const scail_bf16* k, const scail_bf16* v, scail_bf16* o,
                      const int64_t* strides, int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk, int64_t head_dim,
