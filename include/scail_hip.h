@@ -290,7 +290,8 @@ int scail_cross_attn2_bf16(const scail_bf16* q, int64_t q_bs, int64_t q_rs,
                            int64_t n_batch, int64_t heads, int64_t Lq, float scale, void* stream);
 
 /* Sinusoidal timestep embedding in fp64 like sgm/modules/diffusionmodules/util.py:207-231:
- * out[b, :dim/2] = cos(t*f), out[b, dim/2:] = sin(t*f), f_j = exp(-ln(1e4) j/(dim/2)). fp32 out. */
+ * out[b, :dim/2] = cos(t*f), out[b, dim/2:] = sin(t*f), f_j = exp(-ln(1e4) j/(dim/2)). fp32 out; an odd dim gets a trailing zero column.
+ * Errors (host side, before any launch): dim < 1, n outside [0, 2^31), a null pointer with n > 0. */
 int scail_timestep_embedding(const float* t, float* out, int64_t n, int64_t dim, void* stream);
 
 /* y[M,N] = act_out( act_in(x[M,K]) . W[N,K]^T + b ), M <= 8, x/y fp32, W bf16, b fp32.
@@ -298,7 +299,8 @@ int scail_timestep_embedding(const float* t, float* out, int64_t n, int64_t dim,
 int scail_small_linear(const float* x, const scail_bf16* w, const float* b, float* y, int64_t M,
                        int64_t N, int64_t K, int act_in, int act_out, void* stream);
 
-/* out[layer, b, j] = emb[b, j] + table[layer, j]   (AdaLN tables, dit...:1025-1028 and :823). fp32. */
+/* out[layer, b, j] = emb[b, j] + table[layer, j]   (AdaLN tables, dit...:1025-1028 and :823). fp32: one addition, the bits of torch's.
+ * Errors: a size outside [0, 2^20), a null pointer with a non-empty table. */
 int scail_adaln_table(const float* emb, const float* table, float* out, int64_t n_layers,
                       int64_t n_batch, int64_t width, void* stream);
 
@@ -310,6 +312,8 @@ int scail_adaln_table(const float* emb, const float* table, float* out, int64_t 
  * token order [ref | noise | pose], each (t h w) row-major.
  *   x fp32 [n_batch,T,16,H,W] (rounded to bf16 as dit...:1454-1455); ref bf16 [n_ref,1,16,H,W];
  *   pose bf16 [n_pose,T,16,H/2,W/2]; n_ref/n_pose in {1, n_batch} (CFG repeat :1479-1495).
+ * Errors (host side, before any launch): a size outside [0, 2^15), H or W no multiple of 4, kpad < 80 or no multiple of 8, and for a
+ * non-empty token matrix a null pointer, a misaligned one (x 4 bytes, ref / pose 2, tok 16: 16-byte stores) or 2^31 workgroups or more.
  */
 int scail_patchify(const float* x, const scail_bf16* ref, const scail_bf16* pose, scail_bf16* tok,
                    int64_t n_batch, int64_t n_ref, int64_t n_pose, int64_t T, int64_t H, int64_t W,
@@ -329,12 +333,15 @@ int scail_patchify_chars(const float* x, const scail_bf16* ref, const scail_bf16
                          int64_t kpad, void* stream);
 
 /* unpatchify dit...:764-784: tok [n_batch, T*(H/2)*(W/2), 64] bf16 ((o p q c) columns)
- * -> out fp32 [n_batch, T, 16, H, W]. */
+ * -> out fp32 [n_batch, T, 16, H, W]: out[b, t, c, 2h+p, 2w+q] = tok[b, (t h w), 32p + 16q + c].
+ * Errors: a size outside [0, 2^15), H or W odd (the kernel would read a neighbouring token's row, and on the last token past the end),
+ * and for a non-empty latent a null pointer or 2^31 workgroups or more. */
 int scail_unpatchify(const scail_bf16* tok, float* out, int64_t n_batch, int64_t T, int64_t H,
                      int64_t W, void* stream);
 
 /* x += dsigma * (v_u + cfg * (v_c - v_u)),  v = [v_u; v_c] fp32 [2, n]
- * (guiders.py:41-45 + sampling_utils.py:7-10 + Euler update sampling.py:960-963), all fp32. */
+ * (guiders.py:41-45 + sampling_utils.py:7-10 + Euler update sampling.py:960-963), all fp32.  Its two multiply-adds may contract: an element is
+ * one of the four results with each of them fused or rounded separately.  Errors: n < 0 or 2^31 workgroups or more, a null pointer with n > 0. */
 int scail_cfg_euler(float* x, const float* v, int64_t n, float cfg_scale, float dsigma, void* stream);
 
 /*
@@ -431,15 +438,20 @@ int scail_rms_silu(const scail_bf16* x, scail_bf16* y, const float* gamma, int64
  * padded to a multiple of 8 columns in memory (ld % 8 == 0, ld >= ceil8(n)) and columns n .. ceil8(n) are written as zeros. */
 int scail_softmax_rows(scail_bf16* s, int64_t ld, int64_t rows, int64_t n, float scale, void* stream);
 
-/* Batched 2-D transpose (R x C, row stride ldi) -> (C x R, row stride ldo). */
+/* Batched 2-D transpose (R x C, row stride ldi) -> (C x R, row stride ldo); columns from R on of the output are not written.
+ * Errors: a negative size, ceil(R / 64) or batch above 65535 (grid y and z), and for a non-empty call a null pointer, ldi < C or ldo < R. */
 int scail_transpose2d(const scail_bf16* in, int64_t ldi, int64_t in_bs, scail_bf16* out, int64_t ldo,
                       int64_t out_bs, int64_t R, int64_t C, int64_t batch, void* stream);
 
-/* planar fp32 (C, N) -> channels-last bf16 (N, Cpad): y = x*a[c] + b[c] (a, b may be NULL), pad channels zero. */
+/* planar fp32 (C, N) -> channels-last bf16 (N, Cpad): y = x*a[c] + b[c] (a, b may be NULL), pad channels +0.  The multiply-add may contract:
+ * an element is bf16 of the fused or of the separately rounded fp32 result.  Errors: not 0 < C <= Cpad < 2^20, N outside [0, 2^40), and
+ * for N > 0 a null x or y or 2^31 workgroups or more. */
 int scail_to_channels_last(const float* x, scail_bf16* y, const float* a, const float* b, int64_t C,
                            int64_t Cpad, int64_t N, void* stream);
 
-/* channels-last bf16 (N, ldx) -> planar fp32 (C, N): y = clamp((x + b[c]) * a[c], lo, hi). */
+/* channels-last bf16 (N, ldx) -> planar fp32 (C, N): y = clamp((x + b[c]) * a[c], lo, hi) = fminf(fmaxf(., lo), hi), each operation rounded on
+ * its own (nothing to contract).  fmaxf returns its other argument for a NaN: a NaN input comes out as lo.  Errors: not 0 < C <= ldx,
+ * C >= 2^20, N outside [0, 2^40), and for N > 0 a null x or y or 2^31 workgroups or more. */
 int scail_from_channels_last(const scail_bf16* x, int64_t ldx, float* y, const float* a, const float* b,
                              int64_t C, int64_t N, float lo, float hi, void* stream);
 
@@ -561,7 +573,8 @@ int scail_comm_standin(const void* src, void* dst, int64_t bytes, int32_t workgr
  */
 int scail_release_caches(void);
 
-/* fp32 -> bf16 (round to nearest even) and back; plumbing for boundary tensors. */
+/* fp32 -> bf16 (round to nearest even; denormals in and out are kept, not flushed; a NaN stays a NaN) and back (the pattern << 16);
+ * plumbing for boundary tensors.  Errors: n < 0 or 2^31 workgroups or more, a null pointer with n > 0. */
 int scail_f32_to_bf16(const float* x, scail_bf16* y, int64_t n, void* stream);
 int scail_bf16_to_f32(const scail_bf16* x, float* y, int64_t n, void* stream);
 

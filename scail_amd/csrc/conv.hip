@@ -1527,7 +1527,11 @@ extern "C" int scail_softmax_rows(scail_bf16* s, int64_t ld, int64_t rows, int64
 
 extern "C" int scail_transpose2d(const scail_bf16* in, int64_t ldi, int64_t in_bs, scail_bf16* out, int64_t ldo,
                                  int64_t out_bs, int64_t R, int64_t Cc, int64_t batch, void* stream) {
+    SCAIL_REQUIRE(R >= 0 && Cc >= 0 && batch >= 0 && Cc < (1ll << 31), "negative or oversized shape");
+    SCAIL_REQUIRE((R + 63) / 64 <= 65535 && batch <= 65535, "ceil(R / 64) and batch must be <= 65535 (grid y and z)");
     if (R == 0 || Cc == 0 || batch == 0) return 0;
+    SCAIL_REQUIRE(in != nullptr && out != nullptr, "null pointer");
+    SCAIL_REQUIRE(ldi >= Cc && ldo >= R, "row strides must cover a row (ldi >= C, ldo >= R)");
     hipLaunchKernelGGL(transpose2d_kernel, dim3((unsigned)((Cc + 63) / 64), (unsigned)((R + 63) / 64), (unsigned)batch),
                        dim3(256), 0, (hipStream_t)stream, in, ldi, in_bs, out, ldo, out_bs, (int)R, (int)Cc);
     return scail_check_launch("transpose2d");
@@ -1535,8 +1539,11 @@ extern "C" int scail_transpose2d(const scail_bf16* in, int64_t ldi, int64_t in_b
 
 extern "C" int scail_to_channels_last(const float* x, scail_bf16* y, const float* a, const float* b, int64_t C,
                                       int64_t Cpad, int64_t N, void* stream) {
+    SCAIL_REQUIRE(C > 0 && C <= Cpad && Cpad < (1 << 20) && N >= 0 && N < (1ll << 40), "need 0 < C <= Cpad < 2^20 and 0 <= N < 2^40");
     const int64_t total = N * Cpad;
     if (total == 0) return 0;
+    SCAIL_REQUIRE(x != nullptr && y != nullptr, "null pointer");
+    SCAIL_REQUIRE((total + 255) / 256 < (1ll << 31), "too many voxels for one launch");
     hipLaunchKernelGGL(to_channels_last_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
                        y, a, b, (int)C, (int)Cpad, N);
     return scail_check_launch("to_channels_last");
@@ -1544,8 +1551,11 @@ extern "C" int scail_to_channels_last(const float* x, scail_bf16* y, const float
 
 extern "C" int scail_from_channels_last(const scail_bf16* x, int64_t ldx, float* y, const float* a, const float* b,
                                         int64_t C, int64_t N, float lo, float hi, void* stream) {
+    SCAIL_REQUIRE(C > 0 && C < (1 << 20) && ldx >= C && N >= 0 && N < (1ll << 40), "need 0 < C <= ldx, C < 2^20 and 0 <= N < 2^40");
     const int64_t total = N * C;
     if (total == 0) return 0;
+    SCAIL_REQUIRE(x != nullptr && y != nullptr, "null pointer");
+    SCAIL_REQUIRE((total + 255) / 256 < (1ll << 31), "too many voxels for one launch");
     hipLaunchKernelGGL(from_channels_last_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, x, ldx, y, a, b, (int)C, N, lo, hi);
     return scail_check_launch("from_channels_last");

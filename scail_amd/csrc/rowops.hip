@@ -830,7 +830,9 @@ extern "C" int scail_transpose_v(const scail_bf16* v, int64_t ldv, int64_t v_bat
 }
 
 extern "C" int scail_timestep_embedding(const float* t, float* out, int64_t n, int64_t dim, void* stream) {
+    SCAIL_REQUIRE(dim >= 1 && dim < (1ll << 31) && n >= 0 && n < (1ll << 31), "need dim >= 1 and 0 <= n < 2^31 (one workgroup per timestep)");
     if (n == 0) return 0;
+    SCAIL_REQUIRE(t != nullptr && out != nullptr, "null pointer");
     hipLaunchKernelGGL(timestep_embedding_kernel, dim3((unsigned)n), dim3(128), 0, (hipStream_t)stream, t, out,
                        (int)dim);
     return scail_check_launch("timestep_embedding");
@@ -849,8 +851,11 @@ extern "C" int scail_small_linear(const float* x, const scail_bf16* w, const flo
 
 extern "C" int scail_adaln_table(const float* emb, const float* table, float* out, int64_t n_layers,
                                  int64_t n_batch, int64_t width, void* stream) {
+    SCAIL_REQUIRE(n_layers >= 0 && n_batch >= 0 && width >= 0 && n_layers < (1 << 20) && n_batch < (1 << 20) && width < (1 << 20), "sizes must be 0 .. 2^20 - 1");
     const int64_t total = n_layers * n_batch * width;
     if (total == 0) return 0;
+    SCAIL_REQUIRE(emb != nullptr && table != nullptr && out != nullptr, "null pointer");
+    SCAIL_REQUIRE((total + 255) / 256 < (1ll << 31), "table too large for one launch");
     hipLaunchKernelGGL(adaln_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, emb, table, out, n_batch, width, total);
     return scail_check_launch("adaln_table");
@@ -859,12 +864,19 @@ extern "C" int scail_adaln_table(const float* emb, const float* table, float* ou
 extern "C" int scail_patchify(const float* x, const scail_bf16* ref, const scail_bf16* pose,
                               scail_bf16* tok, int64_t n_batch, int64_t n_ref, int64_t n_pose, int64_t T,
                               int64_t H, int64_t W, int64_t kpad, void* stream) {
+    SCAIL_REQUIRE(n_batch >= 0 && T >= 0 && H >= 0 && W >= 0 && n_batch < (1 << 15) && H < (1 << 15) && W < (1 << 15) && T < (1 << 15), "bad shape");
     SCAIL_REQUIRE(H % 4 == 0 && W % 4 == 0, "latent H and W must be multiples of 4 (pose is half size, patch 2)");
-    SCAIL_REQUIRE(kpad >= 80 && kpad % 8 == 0, "kpad must be >= 80 and a multiple of 8");
+    SCAIL_REQUIRE(kpad >= 80 && kpad % 8 == 0 && kpad < (1 << 15), "kpad must be >= 80 and a multiple of 8");
     SCAIL_REQUIRE((n_ref == 1 || n_ref == n_batch) && (n_pose == 1 || n_pose == n_batch), "cond batch must be 1 or n_batch");
     const int64_t L = (1 + T) * (H / 2) * (W / 2) + T * (H / 4) * (W / 4);
     const int64_t total = n_batch * L * (kpad / 8);
     if (total == 0) return 0;
+    SCAIL_REQUIRE(x != nullptr && ref != nullptr && pose != nullptr && tok != nullptr, "null pointer");
+    // the kernel reads single elements and stores 16 bytes per thread
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0 && (reinterpret_cast<uintptr_t>(ref) & 1) == 0 &&
+                      (reinterpret_cast<uintptr_t>(pose) & 1) == 0 && (reinterpret_cast<uintptr_t>(tok) & 15) == 0,
+                  "pointer alignment (x 4, ref / pose 2, tok 16 bytes)");
+    SCAIL_REQUIRE((total + 255) / 256 < (1ll << 31), "token matrix too large for one launch");
     hipLaunchKernelGGL(patchify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, x, ref, pose, tok, n_batch, n_ref, n_pose, (int)T, (int)H, (int)W,
                        (int)kpad, total);
@@ -897,8 +909,12 @@ extern "C" int scail_patchify_chars(const float* x, const scail_bf16* ref, const
 
 extern "C" int scail_unpatchify(const scail_bf16* tok, float* out, int64_t n_batch, int64_t T, int64_t H,
                                 int64_t W, void* stream) {
+    SCAIL_REQUIRE(n_batch >= 0 && T >= 0 && H >= 0 && W >= 0 && n_batch < (1 << 15) && H < (1 << 15) && W < (1 << 15) && T < (1 << 15), "bad shape");
+    SCAIL_REQUIRE(H % 2 == 0 && W % 2 == 0, "latent H and W must be even (patch 2)");
     const int64_t total = n_batch * T * 16 * H * W;
     if (total == 0) return 0;
+    SCAIL_REQUIRE(tok != nullptr && out != nullptr, "null pointer");
+    SCAIL_REQUIRE((total + 255) / 256 < (1ll << 31), "latent too large for one launch");
     hipLaunchKernelGGL(unpatchify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, tok, out, (int)T, (int)H, (int)W, total);
     return scail_check_launch("unpatchify");
@@ -906,7 +922,9 @@ extern "C" int scail_unpatchify(const scail_bf16* tok, float* out, int64_t n_bat
 
 extern "C" int scail_cfg_euler(float* x, const float* v, int64_t n, float cfg_scale, float dsigma,
                                void* stream) {
+    SCAIL_REQUIRE(n >= 0 && (n + 255) / 256 < (1ll << 31), "n must be 0 .. 2^39 - 256 (one launch)");
     if (n == 0) return 0;
+    SCAIL_REQUIRE(x != nullptr && v != nullptr, "null pointer");
     hipLaunchKernelGGL(cfg_euler_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        x, v, n, cfg_scale, dsigma);
     return scail_check_launch("cfg_euler");
@@ -1005,13 +1023,17 @@ extern "C" int scail_tile_finish(float* x, float* den, const float* inv_wsum, in
 }
 
 extern "C" int scail_f32_to_bf16(const float* x, scail_bf16* y, int64_t n, void* stream) {
+    SCAIL_REQUIRE(n >= 0 && (n + 255) / 256 < (1ll << 31), "n must be 0 .. 2^39 - 256 (one launch)");
     if (n == 0) return 0;
+    SCAIL_REQUIRE(x != nullptr && y != nullptr, "null pointer");
     hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, x, y, n);
     return scail_check_launch("f32_to_bf16");
 }
 extern "C" int scail_bf16_to_f32(const scail_bf16* x, float* y, int64_t n, void* stream) {
+    SCAIL_REQUIRE(n >= 0 && (n + 255) / 256 < (1ll << 31), "n must be 0 .. 2^39 - 256 (one launch)");
     if (n == 0) return 0;
+    SCAIL_REQUIRE(x != nullptr && y != nullptr, "null pointer");
     hipLaunchKernelGGL(bf16_to_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, x, y, n);
     return scail_check_launch("bf16_to_f32");
