@@ -18,11 +18,13 @@ extern "C" {
  *                          software-pipelined kernel, bits 12.. filler placement; bit 20 stamps workgroup lifetimes
  *                          (scail_debug_cycles); bits 4-5 are TIMING ABLATIONS with wrong results (no softmax / no staging)
  *   "attn4", "attn4_thr", "attn4_xcd", "attn4_kernel[:suffix]"   4-wave generated attention kernel: on/off, lazy-rescale
- *                          threshold, XCD-aware workgroup ids on/off, variant of asmgen/attn4.py variant_cfgs()
+ *                          threshold, XCD-aware workgroup ids on/off, TIMING ABLATION of asmgen/attn4.py variant_cfgs() (kernel
+ *                          scail_attn4_<suffix>, e.g. "attn4_kernel:m16f_s_abl_dma"; wrong results on purpose)
  *   "gemm_tile"            0 auto, 128, 256, 257, 260, 261 (q8), 262, 266; 1000-1599 = timing ablations (wrong results)
  *   "gemm_group_m"         q8 tile-group height
- *   "gemm4" (0 / 4 / 8), "gemm4_kernel[:suffix]"   generated GEMM kernels: off / gemm4 (the product default) / gemm8 (two waves per
- *                          SIMD, this build only); variant of asmgen/gemm4.py, gemm8.py variant_cfgs() for the bias epilogue
+ *   "gemm4" (0 / 1), "gemm4_kernel[:suffix]"   generated GEMM kernels off / on (the product's option "gemm4"); TIMING ABLATION of
+ *                          asmgen/gemm4.py variant_cfgs() for the bias epilogue (kernel scail_gemm4_e0_<suffix>, e.g.
+ *                          "gemm4_kernel:s_abl_dma"; wrong results on purpose)
  *   "conv_halo"            halo-convolution layout 0-5; 10 / 11: generated conv4 kernels off / on (the product's option "conv4")
  *   "conv4_kernel[:suffix]"   variant of asmgen/conv4.py variant_cfgs() for the bias epilogue (timing ablations abl_*: wrong results;
  *                          "prof": phase timers (s_memtime) written through the residual pointer, 8 uint32 per workgroup)

@@ -14,7 +14,6 @@ from typing import Iterable, Tuple
 
 ASMGEN = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(ASMGEN), "csrc")
-ROOT = os.path.dirname(os.path.dirname(ASMGEN))
 
 
 @dataclass(frozen=True)
@@ -111,7 +110,7 @@ class CodeObject:
     gen: str                   # generator module in this package
     lists: Tuple[str, ...]     # the generator's config lists the code object holds, in order
     variants: bool = True      # the measurement build adds the generator's variant_cfgs()
-    committed: bool = True     # csrc/<stem>.s is committed; False: measurement build only, written to the build directory
+    committed: bool = True     # csrc/<stem>.s is committed: true of every code object (tests/test_codeobj_cpu.py selects by it)
 
     def module(self):
         return importlib.import_module(f"{__package__}.{self.gen}")
@@ -123,8 +122,9 @@ class CodeObject:
     def text(self, variants: bool = False) -> str:
         return self.module().assembly(self.cfgs(variants))
 
-    def path(self, objdir: str) -> str:
-        return os.path.join(CSRC if self.committed else objdir, self.stem + ".s")
+    def path(self, objdir: str = "") -> str:
+        """csrc/<stem>.s (``objdir``: unused, the call form tests/test_codeobj_cpu.py has)"""
+        return os.path.join(CSRC, self.stem + ".s")
 
 
 CODE_OBJECTS = [
@@ -132,8 +132,6 @@ CODE_OBJECTS = [
     CodeObject("gemm4", "gemm4", ("DEFAULTS",)),
     CodeObject("conv4", "conv4", ("DEFAULTS",)),
     CodeObject("conv4u", "conv4", ("UPSAMPLE", "NARROW", "FUSED", "CONT", "RESNORM"), variants=False),
-    # two waves per SIMD never beat the hipcc q8 kernel: measurement build only
-    CodeObject("gemm8", "gemm8", ("DEFAULTS",), committed=False),
 ]
 
 
@@ -143,10 +141,8 @@ def write_if_changed(path: str, text: str) -> None:
 
 
 def main(gen: str) -> None:
-    """``python -m scail_amd.asmgen.<gen> [--check] [--variants DIR]``: rewrite the generator's code objects where stale (a measurement-build
-    object goes to build_abl/); --check: exit 1 if any of them differs from the generator instead; --variants DIR: write the measurement
-    build's <stem>_variants.s into DIR."""
-    objdir = os.path.join(ROOT, "build_abl")
+    """``python -m scail_amd.asmgen.<gen> [--check] [--variants DIR]``: rewrite the generator's code objects where stale; --check: exit 1
+    if any of them differs from the generator instead; --variants DIR: write the measurement build's <stem>_variants.s into DIR."""
     cos = [c for c in CODE_OBJECTS if c.gen == gen]
     if "--variants" in sys.argv:
         dst = sys.argv[sys.argv.index("--variants") + 1]
@@ -156,9 +152,8 @@ def main(gen: str) -> None:
             print(out)
         return
     if "--check" in sys.argv:
-        sys.exit(0 if all(os.path.exists(c.path(objdir)) and open(c.path(objdir)).read() == c.text() for c in cos) else 1)
+        sys.exit(0 if all(os.path.exists(c.path()) and open(c.path()).read() == c.text() for c in cos) else 1)
     for c in cos:
-        out, text = c.path(objdir), c.text()
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        write_if_changed(out, text)
-        print(out, len(text.splitlines()), "lines")
+        text = c.text()
+        write_if_changed(c.path(), text)
+        print(c.path(), len(text.splitlines()), "lines")

@@ -189,12 +189,6 @@ _SCC_WRITERS = {"s_add_u32", "s_sub_u32", "s_add_i32", "s_sub_i32", "s_addc_u32"
 _SCC_READERS = {"s_cselect_b32", "s_addc_u32", "s_cselect_b64"}
 
 
-def mfma(D: Reg, a: Reg, b: Reg, c, **kw) -> Instr:
-    """D(16) = A(4: 32 rows x 16 k, bf16) x B(4: 16 k x 32 cols) + C(16 | 0)  -- v_mfma_f32_32x32x16_bf16."""
-    assert D.n == 16 and a.n == 4 and b.n == 4
-    return Instr("v_mfma_f32_32x32x16_bf16", [D], [a, b, c], **kw)
-
-
 def mfma16(D: Reg, a: Reg, b: Reg, c, **kw) -> Instr:
     """D(4) = A(4: 16 rows x 32 k, bf16) x B(4: 32 k x 16 cols) + C(4 | 0)  -- v_mfma_f32_16x16x32_bf16 (4 passes = 16 cycles).
     Lane l holds A[l % 16][8 (l / 16) .. +7], B[8 (l / 16) .. +7][l % 16] and D[4 (l / 16) + e][l % 16], e = 0..3."""

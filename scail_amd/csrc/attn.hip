@@ -829,7 +829,7 @@ struct Attn4Args {
 };
 static_assert(sizeof(Attn4Args) == 168, "Attn4Args must match asmgen/attn4.py KERNARG_SIZE");
 static const char* const k_attn4_default = "scail_attn4_m16f";   // the shipped kernel
-static std::string g_attn4_name = k_attn4_default;               // A/B variants of the measurement build replace it ("attn4_kernel:<suffix>")
+static std::string g_attn4_name = k_attn4_default;               // the measurement build's timing ablations replace it ("attn4_kernel:<suffix>")
 static std::atomic<float> g_attn4_thr_log2{8.0f};   // lazy-rescale threshold: P <= 2^thr
 static std::atomic<int> g_attn4_xcd{1};      // XCD-aware workgroup-id decode (A/B knob "attn4_xcd")
 
@@ -924,15 +924,11 @@ static int attn4_plan(int64_t n_batch, int64_t heads, int64_t Lq, Attn4Launch ou
 void scail_attn4_rows_hint(int rows) { g_attn4_rows_hint = rows; }
 // scail_attn4_m16f takes ANY key count >= 512 (ragged last tile: K rows fetched from 64 rows earlier, scores masked) and any scale (q in
 // log2 units as it is, a raw scale through a one-time multiplication of the Q fragments in its prologue); what is left to the 8-wave
-// kernel: short key sets, accumulate, slices beyond 32-bit byte offsets.  (A non-ragged A/B variant of the measurement build needs
-// whole 64-key tiles.)
-static bool attn4_variant_is(const char* what) { return g_attn4_name.find(what) != std::string::npos; }
-static bool attn4_eligible(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t Lq, int64_t Lk, int accumulate, bool prescaled) {
+// kernel: short key sets, accumulate, slices beyond 32-bit byte offsets.  (The timing ablations of the measurement build are the same
+// kernel with an instruction class removed: same limits.)
+static bool attn4_eligible(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t Lq, int64_t Lk, int accumulate) {
     const int64_t lim = (1ll << 30);     // elements -> 2^31 bytes
-    const bool is_default = g_attn4_name == k_attn4_default;
-    const bool ragged_ok = is_default, raw_ok = is_default || !(attn4_variant_is("m16f") || attn4_variant_is("m16g"));
-    return (Lk % 64 == 0 || ragged_ok) && (prescaled || raw_ok) && Lk >= 512 && accumulate == 0 && Lq * q_rs < lim && Lk * k_rs < lim &&
-           Lq * o_rs < lim && 128 * (Lk + 63) < lim;
+    return Lk >= 512 && accumulate == 0 && Lq * q_rs < lim && Lk * k_rs < lim && Lq * o_rs < lim && 128 * (Lk + 63) < lim;
 }
 // What the self-attention and the cross-attention choice share: option "attn4", and the generated kernels' 1-D workgroup-id decode -- reciprocal
 // multiplications that are exact while id * divisor < 2^31 (asmgen/attn4.py magic31): query blocks^2 * heads * batch and heads^2 * batch must stay
@@ -949,7 +945,7 @@ static bool attn4_allowed(int64_t n_batch, int64_t heads, int64_t Lq) {
 // and its helpers above (attn4_plan, attn4_eligible, attn4_allowed -- the last shared with cross_choose) reads options "attn4", "attn4_rows",
 // "attn4_cus", "attn4_xcd", the thread's rows hint, g_attn4_name or the measurement build's attn_variant.
 // ------------------------------------------------------------------------------------------------
-enum AttnFamily { ATTN_GEN,          // generated: scail_attn4_m16f (+ _q3), or the variant the measurement build's "attn4_kernel" knob names
+enum AttnFamily { ATTN_GEN,          // generated: scail_attn4_m16f (+ _q3), or the timing ablation the measurement build's "attn4_kernel" knob names
                   ATTN_W8,           // the product's 8-wave kernel
                   ATTN_VARIANT };    // measurement build: a schedule of the 8-wave family forced with "attn_variant"
 // a hipcc kernel of the 8-wave family as the launch needs it: scail_launch_lds of the instantiation (which opts it in to `lds` bytes of
@@ -991,7 +987,6 @@ struct AttnChoice {
     AttnKernel hip = k_attn_w8;  // ATTN_W8 / ATTN_VARIANT: the launch
     int variant = 0;             // ATTN_VARIANT: the attn_variant code
     const char* name = nullptr;  // ATTN_GEN: the base symbol (g_attn4_name's characters); a 192-row launch runs name + "_q3"
-    bool fold = true;            // ATTN_GEN: a 16x16x32 "fold" kernel (scores in log2 units, the scale multiplied into the Q fragments once)
     int n_launch = 0;            // ATTN_GEN with a plan: 1 or 2 launches; -1: the plan needs the device's CU count and there is none
     Attn4Launch launch[2] = {};
 };
@@ -999,12 +994,11 @@ struct AttnChoice {
 // want_plan == false answers the family and the kernel alone, which needs no device; the plan of the shipped generated kernel is sized by the
 // device's compute units (attn4_plan) unless option "attn4_rows" or the thread's hint forces a height.
 static AttnChoice attn_choose(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk, int accumulate,
-                              bool prescaled, bool want_plan) {
+                              bool /* prescaled: every kernel takes q in either form */, bool want_plan) {
     AttnChoice c;
-    if (attn4_allowed(n_batch, heads, Lq) && attn4_eligible(q_rs, k_rs, o_rs, Lq, Lk, accumulate, prescaled)) {
+    if (attn4_allowed(n_batch, heads, Lq) && attn4_eligible(q_rs, k_rs, o_rs, Lq, Lk, accumulate)) {
         c.family = ATTN_GEN;
         c.name = g_attn4_name.c_str();
-        c.fold = attn4_variant_is("m16f") || attn4_variant_is("m16g");      // (the 32x32x16 variants of the measurement build are not)
         if (!want_plan) return c;
         // launch plan (tile heights): the 192-row form exists for the shipped kernel only
         if (g_attn4_name == k_attn4_default) {
@@ -1145,11 +1139,10 @@ extern "C" int scail_tune_set(const char* knob, int value) {
     if (std::string(knob) == "attn4" || std::string(knob) == "attn4_xcd") return scail_set_option(knob, value);   // (the product's options)
     if (std::string(knob) == "attn4_thr") { g_attn4_thr_log2 = (float)value; return 0; }    // lazy-rescale threshold (log2 units), any value: the option checks its range
     if (std::string(knob).rfind("attn4_kernel", 0) == 0) {
-        // A/B of the generated schedules: knob = "attn4_kernel" (default kernel) or "attn4_kernel:<suffix>" -> kernel
-        // scail_attn4_<suffix> of the embedded code object (the variants exist only in the ablation build, SCAIL_ABLATIONS=1)
+        // timing ablations of the generated kernel: knob = "attn4_kernel" (the shipped kernel) or "attn4_kernel:<suffix>" -> kernel
+        // scail_attn4_<suffix> of the embedded code object (asmgen/attn4.py variant_cfgs; they exist only in this build)
         std::string k(knob), name = k_attn4_default;
         if (k.size() > 13) name = "scail_attn4_" + k.substr(13);
-        if (name == "scail_attn4_general") name = "scail_attn4";      // the 32x32x16 kernel (round 2's raw-scale path)
         g_attn4_name = name;
         hipFunction_t fn;
         return scail_module_function("attn4", k_attn4_hsaco, name, &fn);
@@ -1205,10 +1198,9 @@ extern "C" int scail_flash_attn_bf16(const scail_bf16* q, int64_t q_bs, int64_t 
     if (Lq == 0 || n_batch == 0) return 0;
     const AttnChoice c = attn_choose(q_rs, k_rs, o_rs, n_batch, heads, Lq, Lk, accumulate, prescaled, true);
     if (c.family == ATTN_GEN) {
-        // scail_attn4_m16f (or the variant chosen with the measurement build's "attn4_kernel" knob).  The 16x16x32 "fold" kernels
+        // scail_attn4_m16f (or the timing ablation chosen with the measurement build's "attn4_kernel" knob).  The generated kernels
         // work on scores in log2 units: sl2 = 0 says q carries scale * log2(e) already, any other value is multiplied into the Q
-        // fragments once in the prologue; their lazy-rescale threshold is in log2 units.  The 32x32x16 variants of the
-        // measurement build take sl2 per score and the threshold in raw-score units.
+        // fragments once in the prologue; their lazy-rescale threshold is in log2 units.
         if (c.n_launch < 0) return 2;
         const float thr_log2 = g_attn4_thr_log2;
         for (int li = 0; li < c.n_launch; ++li) {
@@ -1216,8 +1208,8 @@ extern "C" int scail_flash_attn_bf16(const scail_bf16* q, int64_t q_bs, int64_t 
             if (int rc = scail_module_function("attn4", k_attn4_hsaco, attn_choice_name(c, li), &fn)) return rc;
             Attn4Args a;
             attn4_fill(a, q, q_bs, q_rs, k, k_ss, k_bs, k_rs, vt, vt_ss, vt_bs, o, o_bs, o_rs, heads, Lq, Lk, n_seg, c.launch[li]);
-            a.sl2 = c.fold ? (prescaled ? 0.0f : sl2) : sl2;
-            a.thr = c.fold ? thr_log2 : thr_log2 / sl2;
+            a.sl2 = prescaled ? 0.0f : sl2;
+            a.thr = thr_log2;
             a.restarts = g_attn4_restart_ctr;
             if (int rc = scail_module_launch("attn4", fn, (unsigned)c.launch[li].grid, 256, a, stream)) return rc;
         }

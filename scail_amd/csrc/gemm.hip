@@ -437,24 +437,18 @@ static int launch_gemm_q8(const GemmParams& p, hipStream_t stream) {
 static const unsigned char k_gemm4_hsaco[] = {
 #include "gemm4_hsaco.inc"
 };
-#ifdef SCAIL_ABLATIONS
-// gemm8 (measurement build): two waves per SIMD (8 waves, wave tile 128 x 64, 128 accumulators in a[0:127]; asmgen/gemm8.py)
-static const unsigned char k_gemm8_hsaco[] = {
-#include "gemm8_hsaco.inc"
-};
-#endif
 struct Gemm4Args {
     const void* x; const void* w; const void* bias; void* y; const void* resid; const void* gate; const void* table;
     int64_t lda, ldc, ldr, gs;
     int32_t M, N, K, rows_per_batch;
-    int32_t grid, entries;      // persistent kernels: workgroups launched (a multiple of 8) and entries of the order table
+    int32_t reserved[2];        // read by no kernel (0)
 };
 static_assert(sizeof(Gemm4Args) == 112, "Gemm4Args must match asmgen/gemm4.py KERNARG_SIZE");
 // per-device cache (a hipMalloc'd table belongs to the device that was current when it was created)
 static std::map<std::tuple<int, int, int, int, int>, std::pair<uint32_t*, int>> g_gemm4_tables;   // (device, m tiles, n tiles, group height, table mode) -> device order table, entries
 static std::mutex g_gemm4_mutex;
-static std::atomic<int> g_gemm4_mode{4};               // generated kernels where eligible: 4 = gemm4 (default), 0 = never (csrc/gemm.hip only), 8 = gemm8 (measurement build)
-static std::string g_gemm4_suffix;         // A/B variants of the measurement build ("gemm4_kernel:<suffix>")
+static std::atomic<int> g_gemm4_mode{4};               // generated kernels where eligible: 4 = gemm4 (default), 0 = never (csrc/gemm.hip only)
+static std::string g_gemm4_suffix;         // timing ablations of the measurement build ("gemm4_kernel:<suffix>")
 static int g_gemm4_table_mode = 1;         // tile -> XCD assignment of the order table (0, 2: measurement build A/B, knob "gemm4_table")
 
 // Tile order table: workgroup id b runs on XCD b % 8 and takes entry b >> 3 of that XCD's sequence; a sequence is made of whole tile
@@ -557,12 +551,12 @@ static bool gemm4_eligible(int64_t lda, int64_t ldc, int64_t ldr, int64_t M, int
 // (scail_gemm_kernel_for, scail_gemm_kernel_name_for) are projections of the same answer.  Nothing else reads option "gemm4", the
 // measurement build's gemm_tile / gemm4 knobs or gemm4_eligible.
 // ------------------------------------------------------------------------------------------------
-enum GemmKernel { GEMM_GEN,                                           // generated (csrc/gemm4.s; measurement build: gemm8, the A/B variants)
+enum GemmKernel { GEMM_GEN,                                           // generated (csrc/gemm4.s; measurement build: + its timing ablations)
                   GEMM_T128, GEMM_T256_DMA, GEMM_Q8,                  // hipcc: gemm_bf16_kernel<128, ..>, gemm_bf16_kernel<256, .., DMA>, gemm_bf16_q8_kernel
                   GEMM_T256, GEMM_T256_DMA_SPREAD, GEMM_T256_4W, GEMM_Q8_PRIO, GEMM_TIMING };      // measurement build, forced by gemm_tile only
 struct GemmChoice {
     GemmKernel kernel = GEMM_T128;
-    int generated = 0;       // 4 / 8: a generated kernel of gemm4.s / gemm8.s (scail_gemm_kernel_for's answer); 0: a hipcc kernel
+    int generated = 0;       // 4: a generated kernel of gemm4.s (scail_gemm_kernel_for's answer); 0: a hipcc kernel
     int forced = 0;          // measurement build: the gemm_tile code that forced the kernel (0: chosen by shape)
     int epilogue = 0;        // SCAIL_EPI_*
     bool gated = false;      // the residual epilogue has a gate (the generated kernels have one entry point for each form)
@@ -622,8 +616,8 @@ static GemmChoice gemm_choose(int64_t lda, int64_t ldc, int64_t ldr, int64_t M, 
 static std::string gemm_choice_name(const GemmChoice& c) {
     if (c.kernel == GEMM_GEN) {
         const int epi4 = c.epilogue == SCAIL_EPI_RESID ? (c.gated ? 3 : 4) : c.epilogue;
-        std::string name = std::string(c.generated == 8 ? "scail_gemm8_e" : "scail_gemm4_e") + std::to_string(epi4);
-        if (epi4 == 0 || g_gemm4_suffix == "_pst" || g_gemm4_suffix == "_part" || g_gemm4_suffix == "_stgnt") name += g_gemm4_suffix;      // A/B variants: bias epilogue only, except the persistent set (ablation build)
+        std::string name = "scail_gemm4_e" + std::to_string(epi4);
+        if (epi4 == 0) name += g_gemm4_suffix;      // timing ablations of the measurement build: bias epilogue only
         return name;
     }
     const std::string e = std::to_string(c.epilogue), t256 = "gemm_bf16_kernel<256, 256, 2, 4, " + e;
@@ -693,7 +687,7 @@ int scail_gemm4_enable(int on) { g_gemm4_mode = on ? 4 : 0; return 0; }
 int scail_gemm4_knob(const char* knob, int value) {
     std::string k(knob);
     std::lock_guard<std::mutex> lk(g_gemm4_mutex);      // gemm4_table / the launch read these under the same mutex
-    if (k == "gemm4") { g_gemm4_mode = (value == 4 || value == 8) ? value : (value ? 4 : 0); return 0; }
+    if (k == "gemm4") { g_gemm4_mode = value ? 4 : 0; return 0; }
     if (k == "gemm4_table") { g_gemm4_table_mode = (value >= 0 && value <= 2) ? value : 1; return 0; }
     if (k.rfind("gemm4_kernel", 0) == 0) { g_gemm4_suffix = k.size() > 13 ? "_" + k.substr(13) : ""; return 0; }
     return -1;
@@ -718,15 +712,8 @@ extern "C" int scail_gemm_bf16(const scail_bf16* x, int64_t lda, const scail_bf1
     }
     const GemmChoice choice = gemm_choose(lda, ldc, ldr, M, N, K, epilogue, epilogue == SCAIL_EPI_RESID && gate != nullptr);
     if (choice.kernel == GEMM_GEN) {
-        const bool is8 = choice.generated == 8;
-        const std::string name = gemm_choice_name(choice);
-#ifdef SCAIL_ABLATIONS
-        const void* image = is8 ? k_gemm8_hsaco : k_gemm4_hsaco;
-#else
-        const void* image = k_gemm4_hsaco;
-#endif
         hipFunction_t fn;
-        if (int rc = scail_module_function("gemm4", image, name, &fn)) return rc;
+        if (int rc = scail_module_function("gemm4", k_gemm4_hsaco, gemm_choice_name(choice), &fn)) return rc;
         uint32_t* table;
         int entries;
         if (int rc = gemm4_table((int)((M + 255) / 256), (int)(N / 256), g_group_m, &table, &entries)) return rc;
@@ -734,18 +721,8 @@ extern "C" int scail_gemm_bf16(const scail_bf16* x, int64_t lda, const scail_bf1
         a.x = x; a.w = w; a.bias = bias; a.y = y; a.resid = resid; a.gate = gate; a.table = table;
         a.lda = lda; a.ldc = ldc; a.ldr = ldr; a.gs = gate_stride;
         a.M = (int32_t)M; a.N = (int32_t)N; a.K = (int32_t)K; a.rows_per_batch = (int32_t)rows_per_batch;
-        // persistent kernels (name ends in "_pst"): one workgroup per CU, rounded down to a multiple of 8 so that workgroup b keeps
-        // walking the sequence of XCD b % 8 (entries b, b + grid, b + 2 grid, ...)
-        unsigned grid = (unsigned)entries;
-        const bool persistent = name.size() > 4 && name.compare(name.size() - 4, 4, "_pst") == 0;
-        if (persistent) {
-            int cus = scail_device_cus();
-            if (cus <= 0) return 2;
-            if (cus < 8) cus = 8;
-            grid = std::min<unsigned>((unsigned)entries, (unsigned)(cus / 8 * 8));
-        }
-        a.grid = (int32_t)grid; a.entries = (int32_t)entries;
-        return scail_module_launch("gemm4", fn, grid, is8 ? 512 : 256, a, stream);
+        a.reserved[0] = a.reserved[1] = 0;
+        return scail_module_launch("gemm4", fn, (unsigned)entries, 256, a, stream);
     }
     GemmParams p;
     p.x = x; p.lda = lda; p.w = w; p.bias = bias; p.y = y; p.ldc = ldc;

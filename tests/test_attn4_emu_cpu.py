@@ -2,7 +2,7 @@
 the same objects that are printed into csrc/attn4.s) runs in the CPU emulator (tools/asm_emu.py: 4 waves, shared LDS,
 in-order memory counters with lazy completion, MFMA result latency, real s_barrier) on small attention problems and is
 compared with fp64 softmax(q k^T / sqrt(128)) v of the oracle formula (sat/transformer_defaults.py:67-72).  Covered: every
-remainder path of the unrolled tile loop (1 ... 11 key tiles), both ring depths, ragged query blocks, several heads / batch
+remainder path of the unrolled tile loop (1 ... 11 key tiles), ragged query blocks, several heads / batch
 elements through the XCD-aware workgroup-id decode, key segments, the lazy-rescale subroutine (spiked keys, thr = 0), lazy and
 eager completion of loads, plus the static hazard re-check of every scheduled block (tests/test_codeobj_cpu.py checks that
 `csrc/attn4.s` is up to date)."""
@@ -89,38 +89,16 @@ def test_emulator_checks_issue_distances_along_the_executed_path():
     R.run(attn4.M16F, q, [k], [v], 1)                      # the shipped program: clean
 
 
-@pytest.mark.parametrize("rd", [4, 2])
-def test_static_hazards_clean(rd):
-    assert R.check_static(attn4.Cfg(rd=rd)) == []
-
-
-@pytest.mark.parametrize("tiles", [1, 2, 3, 4, 5, 6, 7, 9, 11])
-def test_every_remainder_path_of_the_tile_loop(tiles):
-    st = _case(attn4.DEFAULT, 1, 1, 256, 64 * tiles, lazy=bool(tiles & 1), seed=tiles)
-    assert st["mfma"] == 64 * tiles                      # 32 QK^T + 32 P.V MFMAs per tile and wave, nothing recomputed
-
-
-def test_ring_depth_two_variant():
-    cfg = attn4.Cfg(rd=2)
-    for tiles in (1, 2, 3, 5, 8):
-        _case(cfg, 1, 1, 256, 64 * tiles, lazy=True, seed=10 + tiles)
-
-
-def test_heads_batch_ragged_queries_and_workgroup_id_decode():
-    _case(attn4.DEFAULT, 2, 4, 300, 128, seed=1)                    # 8 (batch, head) pairs: XCD-aware decode
-    _case(attn4.DEFAULT, 1, 3, 520, 64, seed=2)                     # pairs % 8 != 0: plain decode; 3 query blocks, ragged last
-    _case(attn4.DEFAULT, 2, 4, 256, 64, seed=3, mode=0)
-
-
-def test_segments_and_lazy_rescale():
-    _case(attn4.DEFAULT, 1, 2, 100, 192, nseg=3, spike=True, seed=4)
-    _case(attn4.DEFAULT, 1, 1, 256, 640, lazy=False, spike=True, thr=0.0, seed=5)       # rescale whenever a row max moves
-    _case(attn4.DEFAULT, 1, 1, 256, 640, lazy=True, spike=True, thr=2.0, seed=6)
-
-
-# ---- the second shipped kernel: 16x16x32 MFMAs, q in log2 units, running maximum folded into the accumulator init (M16F) ----
+# ---- the shipped kernel: 16x16x32 MFMAs, q in log2 units, running maximum folded into the accumulator init (M16F) ----
 def test_m16f_static_hazards_clean():
     assert R.check_static(attn4.M16F) == []
+
+
+@pytest.mark.parametrize("cfg", attn4.variant_cfgs(), ids=lambda c: c.name)
+def test_m16f_timing_ablations_are_hazard_free(cfg):
+    """the measurement build's timing ablations (M16F with an instruction class of the tile loop removed: wrong results on purpose, so
+    nothing to compare) still keep every issue distance"""
+    assert cfg.abl and R.check_static(cfg) == []
 
 
 @pytest.mark.parametrize("tiles", [1, 2, 3, 4, 5, 6, 7, 9, 11])

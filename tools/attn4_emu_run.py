@@ -54,23 +54,21 @@ def reference(q, k, v, heads):
 def run(cfg: attn4.Cfg, q: np.ndarray, ksegs, vsegs, heads: int, lazy: bool = True, thr_log2: float = 8.0, program=None, mode=None,
         raw_scale: bool = False, launches=None, count_restarts: bool = True, sl2=None):
     """q (B, Lq, H*128) fp32; ksegs / vsegs: lists (one per segment) of (B, Lk, H*128) fp32.  Returns O (B, Lq, H*128) fp32
-    and the emulator statistics of the last workgroup.  raw_scale (qscale kernels): q goes in UNSCALED with sl2 = scale * log2(e)
-    as the kernel argument (the prologue multiplies the fragments), instead of pre-multiplied with sl2 = 0.  ``sl2`` (fold kernels): q goes
+    and the emulator statistics of the last workgroup.  raw_scale: q goes in UNSCALED with sl2 = scale * log2(e)
+    as the kernel argument (the prologue multiplies the fragments), instead of pre-multiplied with sl2 = 0.  ``sl2``: q goes
     in AS GIVEN and scores count sl2 log2 units each -- 1.0: q is in log2 units already; any other value is the raw-scale argument."""
     B, Lq, D = q.shape
     n_seg = len(ksegs)
     Lk = ksegs[0].shape[1]
-    assert Lk % 64 == 0 or getattr(cfg, "ragged", False)
     Lkp = (Lk + 63) // 64 * 64
     mem = E.Memory(size=1 << 26)
-    fold = getattr(cfg, "fold", False)
     if sl2 is not None:
-        assert fold and not raw_scale, "an explicit sl2 is for the kernels that work in log2 units"
+        assert not raw_scale, "an explicit sl2 says itself whether the scale is raw"
         raw_scale = sl2 != 1.0
     else:
         sl2 = (1.0 / math.sqrt(128.0)) * 1.4426950408889634
-    # fold: the caller hands over q already multiplied by scale * log2(e) (one rounding to bf16, as scail_rmsnorm_rope_scaled does)
-    qb = to_bf16_bits(q * np.float32(sl2)) if (fold and not raw_scale) else to_bf16_bits(q)
+    # the caller hands over q already multiplied by scale * log2(e) (one rounding to bf16, as scail_rmsnorm_rope_scaled does), or raw
+    qb = to_bf16_bits(q) if raw_scale else to_bf16_bits(q * np.float32(sl2))
     kb = np.stack([to_bf16_bits(x) for x in ksegs])                       # (S, B, Lk, D)
     vt = np.stack([transpose_v(to_bf16_bits(x), heads) for x in vsegs])    # (S, B, H, 128, Lkp)
     pq = mem.alloc("q", qb)
@@ -78,9 +76,9 @@ def run(cfg: attn4.Cfg, q: np.ndarray, ksegs, vsegs, heads: int, lazy: bool = Tr
     pvt = mem.alloc("vt", vt)
     po = mem.alloc("o", np.zeros((B, Lq, D), dtype=np.uint16))
     pctr = mem.alloc("restarts", np.zeros(4, dtype=np.uint32))          # the optional restart counter of the kernel arguments
-    thr = thr_log2 if fold else thr_log2 / sl2           # fold kernels see scores in log2 units
-    if fold and not raw_scale:
-        sl2 = 0.0 if getattr(cfg, "qscale", False) else 1.0       # qscale kernels: 0 = q is in log2 units already
+    thr = thr_log2                                      # the kernels see scores in log2 units
+    if not raw_scale:
+        sl2 = 0.0                                       # 0 = q is in log2 units already
     # one launch over all items, or the launches of a split attention: [(cfg, item0, n_items, mode), ...] (scail_flash_attn_bf16's mixed
     # launch: whole rounds of 256-row tiles, then 192-row tiles for the remaining rows)
     plan = launches if launches is not None else [(cfg, 0, None, mode)]
@@ -94,7 +92,7 @@ def run(cfg: attn4.Cfg, q: np.ndarray, ksegs, vsegs, heads: int, lazy: bool = Tr
                                heads, Lq, Lk, Lkp, n_seg, sl2, thr, n_batch=B, mode=m, rows=lcfg.rows, item0=item0, n_items=n,
                                restarts=pctr if count_restarts else 0)
         for wid in range(attn4.grid_for(n, m)):
-            emu = E.Emu(prog, mem, n_waves=4, lds_bytes=lcfg.lds_bytes, lazy=lazy)
+            emu = E.Emu(prog, mem, n_waves=4, lds_bytes=attn4.LDS_BYTES, lazy=lazy)
             emu.launch(args, block_id=(wid, 0, 0))
             if stats is None or emu.waves[0].stats.get("mfma", 0) > 0:       # xcd_mode 2 pads the grid with workgroups that exit at once
                 stats = emu.waves[0].stats
@@ -132,7 +130,7 @@ def run_x2(cfg: attn4.Cfg, q: np.ndarray, k1, v1, k2, v2, heads: int, n_wgs: int
                               n_batch=B, n_wgs=n_wgs)
     stats = []
     for wid in range(n_wgs):
-        emu = E.Emu(prog, mem, n_waves=4, lds_bytes=cfg.lds_bytes, lazy=lazy)
+        emu = E.Emu(prog, mem, n_waves=4, lds_bytes=attn4.LDS_BYTES, lazy=lazy)
         emu.launch(args, block_id=(wid, 0, 0))
         stats.append(emu.waves[0].stats)
     return from_bf16_bits(mem.read_back("o")), stats
@@ -152,24 +150,24 @@ def check_static(cfg: attn4.Cfg):
     """hazard re-check of every scheduled block (loop bodies circularly)."""
     g = attn4.Gen(cfg)
     errs = []
-    for p in range(cfg.unroll):
+    U = attn4.UNROLL
+    for p in range(U):
         body = g.iter_block(p, tail=False) + g.iter_end(p, "hot")
-        nxt = g.iter_block((p + 1) % cfg.unroll, tail=False)
+        nxt = g.iter_block((p + 1) % U, tail=False)
         errs += sched.check_hazards(body + nxt)
-        errs += sched.check_hazards(body + g.iter_block((p + 1) % cfg.unroll, tail=True))
-        if getattr(cfg, "opt", False):      # the optimistic hot loop: into itself and into the (max-tracking) remainder chain
-            fast = g.iter_block(p, tail=False, nomax=True) + g.iter_end(p, "hotf", nomax=True)
-            errs += sched.check_hazards(fast + g.iter_block((p + 1) % cfg.unroll, tail=False, nomax=True))
-            errs += sched.check_hazards(fast + g.iter_block((p + 1) % cfg.unroll, tail=False, careful=True))
+        errs += sched.check_hazards(body + g.iter_block((p + 1) % U, tail=True))
+        # the optimistic hot loop: into itself and into the (max-tracking) remainder chain
+        fast = g.iter_block(p, tail=False, nomax=True) + g.iter_end(p, "hotf", nomax=True)
+        errs += sched.check_hazards(fast + g.iter_block((p + 1) % U, tail=False, nomax=True))
+        errs += sched.check_hazards(fast + g.iter_block((p + 1) % U, tail=False, careful=True))
     errs += sched.check_hazards(g.prologue() + g.segment_start() + g.iter_block(0, tail=False))
-    if hasattr(g, "segment_end_and_epilogue") and cfg.mi == 16:      # the restart decision lives here (round 6: lane read of a fresh VALU result)
-        errs += sched.check_hazards(g.segment_end_and_epilogue())
+    errs += sched.check_hazards(g.segment_end_and_epilogue())      # the restart decision lives here (round 6: lane read of a fresh VALU result)
     return errs
 
 
 if __name__ == "__main__":
     rng = np.random.default_rng(0)
-    cfg = attn4.Cfg(rd=int(os.environ.get("RD", "4")), cap=int(os.environ.get("CAP", "5")))
+    cfg = attn4.M16F
     B, H, Lq, Lk = 1, 1, 256, int(os.environ.get("LK", "512"))
     q = rng.standard_normal((B, Lq, H * 128)).astype(np.float32)
     k = rng.standard_normal((B, Lk, H * 128)).astype(np.float32)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""GPU check + A/B timing of the generated attn4 schedules (scail_amd/asmgen/attn4.py) against the 8-wave kernel.
-Needs the measurement build for the variants:  SCAIL_ABLATIONS=1 python -m scail_amd.build ; SCAIL_ABLATIONS=1 python tools/attn4_tune.py
+"""GPU check + timing of the generated attn4 kernel (scail_amd/asmgen/attn4.py) and its timing ablations against the 8-wave kernel.
+Needs the measurement build for the ablations:  SCAIL_ABLATIONS=1 python -m scail_amd.build ; SCAIL_ABLATIONS=1 python tools/attn4_tune.py
 One JSON line per case (stdout)."""
 import argparse
 import json
@@ -49,10 +49,11 @@ def main():
     ap.add_argument("--L", type=int, default=48832)
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--iters", type=int, default=3)
-    ap.add_argument("--variants", default=",dmamid,sm48")
-    ap.add_argument("--ablations", default="abl_fma,abl_fma_c4,abl_fma_sm44")
+    ap.add_argument("--variants", default="", help="kernels to check and time (comma separated suffixes of scail_attn4_; '' = the shipped kernel)")
+    ap.add_argument("--ablations", default="m16f_s_abl_dma,m16f_s_abl_lds,m16f_s_abl_valu,m16f_s_abl_bar,m16f_s_abl_dma_lds_valu",
+                    help="timing ablations of asmgen/attn4.py variant_cfgs() (timed only: wrong results on purpose)")
     ap.add_argument("--skip-check", action="store_true")
-    ap.add_argument("--prescaled", action="store_true", help="hand q over in log2 units (scale == 0 path: the fold variants need it)")
+    ap.add_argument("--prescaled", action="store_true", help="hand q over in log2 units (SCAIL_ATTN_Q_PRESCALED) instead of with a raw scale")
     ap.add_argument("--full", action="store_true", help="also time the 40-head launch of the best variant")
     ap.add_argument("--full-also", default="", help="more variants for the 40-head launch (comma separated; '' = the shipped kernel)")
     a = ap.parse_args()

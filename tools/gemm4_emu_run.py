@@ -20,7 +20,7 @@ def gelu_tanh(x):
     return 0.5 * x * (1.0 + np.tanh(0.7978845608028654 * (x + 0.044715 * x ** 3)))
 
 
-def run(cfg: gemm4.Cfg, x, w, bias=None, resid=None, gate=None, rows_per_batch=0, lda=None, lazy=True, grid=8):
+def run(cfg: gemm4.Cfg, x, w, bias=None, resid=None, gate=None, rows_per_batch=0, lda=None, lazy=True):
     """x (M, K), w (N, K), bias (N) | None, resid (M, N) | None, gate (nb, N) | None  (fp32 in; bf16 operands)."""
     M, K = x.shape
     N = w.shape[0]
@@ -29,8 +29,7 @@ def run(cfg: gemm4.Cfg, x, w, bias=None, resid=None, gate=None, rows_per_batch=0
     xs = np.zeros((M, lda), dtype=np.uint16)
     xs[:, :K] = to_bf16_bits(x)
     px = mem.alloc("x", xs)
-    wb = to_bf16_bits(w)
-    pw = mem.alloc("w", gemm4.pack_w(wb, N, K) if getattr(cfg, "wpacked", False) else wb)
+    pw = mem.alloc("w", to_bf16_bits(w))
     pb = mem.alloc("bias", bias.astype(np.float32)) if bias is not None else 0
     py = mem.alloc("y", np.zeros((M, N), dtype=np.uint16))
     pr = mem.alloc("resid", to_bf16_bits(resid)) if resid is not None else 0
@@ -38,11 +37,9 @@ def run(cfg: gemm4.Cfg, x, w, bias=None, resid=None, gate=None, rows_per_batch=0
     table = np.array(gemm4.tile_table(M, N), dtype=np.uint32)
     pt = mem.alloc("table", table)
     prog = gemm4.Gen(cfg).program()
-    # persistent kernels: fewer workgroups than tiles (a multiple of 8, like the launcher's), each walks entries wg, wg + grid, ...
-    grid = min(len(table), grid) if getattr(cfg, "persist", False) else len(table)
-    args = gemm4.pack_args(px, pw, pb, py, pr, pg, pt, lda, N, N, N if gate is not None else 0, M, N, K, rows_per_batch, grid, len(table))
+    args = gemm4.pack_args(px, pw, pb, py, pr, pg, pt, lda, N, N, N if gate is not None else 0, M, N, K, rows_per_batch)
     stats = None
-    for wg in range(grid):
+    for wg in range(len(table)):
         emu = E.Emu(prog, mem, n_waves=4, lds_bytes=163840, lazy=lazy)
         emu.launch(args, block_id=(wg, 0, 0))
         stats = emu.waves[0].stats
@@ -66,8 +63,6 @@ def reference(cfg, x, w, bias=None, resid=None, gate=None, rows_per_batch=0):
 
 def check_static(cfg):
     g = gemm4.Gen(cfg)
-    if getattr(cfg, "persist", False):
-        return sched.check_hazards(g.loop() + g.loop()) + sched.check_hazards([i for i in g.program()])
     lp = g.loop()
     return sched.check_hazards(lp + lp) + sched.check_hazards(g.prologue() + lp)
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """One GEMM kernel family on the QKV shape of the step, a few launches: the process rocprofv3 --pmc wraps to compare the kernels of
-csrc/gemm.hip (q8), gemm4 and gemm8.  usage: python tools/gemm_pmc_probe.py <0|4|8> [iters]"""
+csrc/gemm.hip (q8) and gemm4.  usage: python tools/gemm_pmc_probe.py <0|4> [iters]"""
 import os
 import sys
 
