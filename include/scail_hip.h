@@ -236,6 +236,29 @@ int scail_flash_attn_kernel_name_for(int64_t q_rs, int64_t k_rs, int64_t o_rs, i
                                      int accumulate, int prescaled, char* buf, int64_t len, int64_t* plan);
 
 /*
+ * Self-attention that reads V as the QKV projection wrote it -- no scail_transpose_v pass, no V^T image:
+ *   v  [n_batch, Lk, heads, 128]  element strides (v_bs, v_rs), like k; q, k, o, scale as scail_flash_attn_bf16; ONE key segment, no accumulate.
+ * It runs the V-rows forms of the 4-wave kernels, scail_attn4_m16f_vr / scail_attn4_m16f_q3_vr (generated by asmgen/attn4.py at build time: the V tile arrives row-major by
+ * LDS-DMA and the P.V operand comes out of it through the transposed LDS read ds_read_b64_tr_b16), with scail_flash_attn_bf16's launch plan,
+ * workgroup-id decodes and restart counter.  The same keys sit in the same MFMA k-slots in the same order: the result is bit for bit that of
+ * scail_transpose_v + scail_flash_attn_bf16.  The kernel never reads a row of v past Lk - 1.
+ * There is no other kernel behind this entry: what the 4-wave kernel cannot take -- Lk < 512, v_rs < heads * 128 or no multiple of 8,
+ * Lk * v_rs (or Lk * k_rs, Lq * q_rs, Lq * o_rs) of 2^30 elements or more (32-bit byte offsets), a grid beyond the workgroup-id decode, options
+ * "attn_vrows" or "attn4" at 0 -- is refused (1 + scail_last_error naming the value).  scail_flash_attn_vrows_for answers 1 exactly for the
+ * calls that run (host-only, no device needed); a caller asks it and keeps scail_transpose_v + scail_flash_attn_bf16 for the rest.
+ * scail_flash_attn_vrows_kernel_name_for: the kernels and the plan as scail_flash_attn_kernel_name_for gives them ("none", no launches, for a
+ * call that would be refused).
+ */
+int scail_flash_attn_vrows_bf16(const scail_bf16* q, int64_t q_bs, int64_t q_rs,
+                                const scail_bf16* k, int64_t k_bs, int64_t k_rs,
+                                const scail_bf16* v, int64_t v_bs, int64_t v_rs,
+                                scail_bf16* o, int64_t o_bs, int64_t o_rs,
+                                int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk, float scale, void* stream);
+int scail_flash_attn_vrows_for(int64_t q_rs, int64_t k_rs, int64_t v_rs, int64_t o_rs, int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk);
+int scail_flash_attn_vrows_kernel_name_for(int64_t q_rs, int64_t k_rs, int64_t v_rs, int64_t o_rs, int64_t n_batch, int64_t heads, int64_t Lq,
+                                           int64_t Lk, char* buf, int64_t len, int64_t* plan);
+
+/*
  * Launch shape the 4-wave kernel would use for an attention of n_batch x heads (batch, head) pairs x Lq queries on the current device:
  *   256  one launch of scail_attn4_m16f (256 query rows per workgroup),
  *   192  one launch of scail_attn4_m16f_q3 (192 rows: 3 of the 4 query blocks per wave; 0.79 of the tile cost),
@@ -516,7 +539,10 @@ int scail_row_affine(const scail_bf16* x, scail_bf16* y, const float* rowscale, 
  * old or the new value; an explicit "attn4_rows" wins over the executor's internal per-thread hint.
  *   "attn4"      1 (default): scail_flash_attn_bf16 uses the 4-wave kernel wherever scail_flash_attn_kernel_for says 4;
  *                0: the 8-wave kernel for every shape.
- *   "gemm4"      1 (default): scail_gemm_bf16 uses the generated 4-wave kernels wherever scail_gemm_kernel_for says 4;
+ *   "attn_vrows" 1 (default): scail_flash_attn_vrows_for says yes wherever the V-rows kernels can run, and the DiT executor then skips
+ *                scail_transpose_v (0.39 ms and 2 GB of HBM traffic per layer at 48 832 tokens); 0: it says no, and every caller stages V^T
+ *                as before (bit-identical results either way).
+ *   "gemm4"     1 (default): scail_gemm_bf16 uses the generated 4-wave kernels wherever scail_gemm_kernel_for says 4;
  *                0: the kernels of csrc/gemm.hip for every shape.
  *   "conv4"      1 (default): scail_conv3d_cl uses the generated kernels wherever scail_conv3d_kernel_for says 4;
  *                0: the kernels of csrc/conv.hip for every convolution.

@@ -1,11 +1,13 @@
-"""attn4 -- hand-scheduled flash attention for the SCAIL DiT on gfx950 (generator of csrc/attn4.s).
+"""attn4 -- hand-scheduled flash attention for the SCAIL DiT on gfx950 (generator of csrc/attn4.s and of the build-time code object attn4v).
 
 Reference call site: F.scaled_dot_product_attention in sat/transformer_defaults.py:67-72 reached from
 dit_video_crossattn_sc_xc.py:1058-1105 (no mask, scale 1/sqrt(128)); same C entry point as the 8-wave kernel of
 csrc/attn.hip (scail_flash_attn_bf16), which selects the kernels generated here for Lk >= 512 without accumulate.
 
 One kernel family: scail_attn4_m16f (256-row workgroups), scail_attn4_m16f_q3 (192-row workgroups, Cfg.nq) and scail_attn4_x2 (cross
-attention over two key sets with persistent workgroups, Cfg.x2).
+attention over two key sets with persistent workgroups, Cfg.x2); scail_attn4_m16f_vr / scail_attn4_m16f_q3_vr (Cfg.vr) are the two self-attention
+kernels reading V row-major, as the QKV projection wrote it (scail_flash_attn_vrows_bf16): the V tile goes to LDS as [d quarter-pair][8 keys][32 B]
+and ds_read_b64_tr_b16 hands the MFMA the same V^T fragments -- same keys in the same k-slots, bit-identical results, no scail_transpose_v pass.
 
 Shape of the kernel (MI355X guide: "4-wave, one-wave-per-SIMD" attention structure):
   * workgroup = 256 query rows = 4 waves x 64 rows (4 query blocks of 16); ONE wave per SIMD with the whole 512-register file:
@@ -127,6 +129,14 @@ class Cfg:
                            # own key count, own softmax state, own optimistic pass / restart); set 0's normalised output is stored as bf16 at its
                            # final place and read back (same lane, same address) by set 1's epilogue, which adds and stores.  Kernel arguments:
                            # the base block (set 0 in the k / vt fields, xcd_mode 0, n_items = all items) + X2_EXTRA
+    vr: bool = False       # V ROWS (scail_flash_attn_vrows_bf16): the kernel argument ``vt`` is v itself, (batch, key, heads x 128) row-major with row stride
+                           # ``vt_ss`` (the field has no other use: one key segment) and batch stride ``vt_bs`` -- no V^T image, no scail_transpose_v.
+                           # The 64-key x 128-d V tile (16 KiB, the V^T tile's size and ring) arrives by the same LDS-DMA; the P.V A fragments come
+                           # out of it through ds_read_b64_tr_b16 (two per fragment: the 4 + 4 key rows a lane's k-slots hold, see v_frag_reads16)
+    vr_behind: float = 8.0  # Cfg.vr has 16 more fragment reads than MFMA gaps to put them in: a gap without a v_exp_f32 takes a second cheap filler (sched.schedule
+                           # cheap_extra) once a filler is this many gaps behind its target.  Measured on the config-2 launch against transpose + V^T kernel
+                           # (profiles/attn_vrows_ab.log): no second filler -0.60 ms, any second filler (v_exp included) -4.1 ms, cheap ones from 1 gap
+                           # behind -0.15, from 3 .. 12 gaps behind +0.45 .. +0.79 (a plateau), two cheap extras -0.8 .. -1.0
     abl: str = ""          # TIMING ABLATIONS (wrong results; measurement build only): "dma" / "lds" / "valu" / "bar" removed from the tile loop
     cap: int = 1           # fillers per MFMA gap
     lookahead: float = 2.0
@@ -156,7 +166,7 @@ def Vtf16(db, ks): return V(128 + (db * 2 + ks) * 4, 4)
 
 
 KADDR16 = [[V(192 + ks * 2 + par) for par in range(2)] for ks in range(4)]       # [k-step][parity of the key block]
-VADDR16 = [V(200), V(201)]
+VADDR16 = [V(200), V(201)]                                     # (Cfg.vr: VADDR16[0] serves all 32 transposed reads, VADDR16[1] is unused)
 KDMA = [V(204 + i) for i in range(4)]
 VDMA = [V(208 + i) for i in range(4)]
 NEGM = [V(212 + 4 * qb, 4) for qb in range(4)]                # -M of query block qb as an accumulator-init quad
@@ -183,6 +193,7 @@ S_IPX, S_NITEMS, S_ITEM0 = S(87), S(88), S(89)     # xcd_mode 2: items per XCD r
 S_CLAMP, S_FIRST = S(87), S(88)               # rescale subroutine: lower bound of the maximum step (0, -inf at the very first tile), first-call flag
 S_TAILREL = [S(89 + i) for i in range(4)]     # valid keys of the last tile - first tile row of this wave's K piece i
 S_TAIL = S(93)
+S_VTAILREL = [S(96 + i) for i in range(4)]    # Cfg.vr: valid keys of the last tile - first tile row of this wave's V piece i (kernels with 100 SGPRs)
 S_MODE, S_HEAD = S(94), S(95)     # 0 = optimistic hot loop / 1 = lazy-maximum hot loop after a restart; headroom of the first maximum
 S_KRSRC, S_VRSRC = S(44, 4), S(48, 4)
 S_KOFF, S_VOFF, S_KSTEP, S_VSTEP, S_KMAX, S_VMAX = S(52), S(53), S(54), S(55), S(56), S(57)
@@ -292,6 +303,19 @@ class Gen:
     def v_frag_reads16(self, slot: int, t0: float, step: float) -> List[Instr]:
         out = []
         k = 0
+        if self.cfg.vr:
+            # A fragment of O^T += V^T P^T for (db, ks): lane (m, g) needs d = 16 db + m of the 8 keys its score registers hold, keys
+            # 32 ks + 16 (g >> 1) + 4 (g & 1) + {0..3} and the same + 8 = two transposed reads of 4 consecutive key rows x 16 columns.
+            # V tile image (vdma_offsets): byte offset of 16-byte chunk c of key row r = 8192 (c >> 3) + 1024 (r >> 3) + 256 ((c >> 1) & 3) +
+            # 32 (r & 7) + 16 (c & 1): the 8 rows x 32 bytes a 32-lane half reads are 256 consecutive bytes = all 64 banks once, with no XOR
+            # -- so db, ks and the + 8 go into the immediate offset and ONE address register serves all 32 reads
+            for ks in range(2):
+                for db in range(8):
+                    for h in range(2):
+                        off = slot * 16384 + 8192 * (db >> 2) + 256 * (db & 3) + 4096 * ks + 1024 * h
+                        out.append(isa.ds_read_b64_tr_b16(Vtf16(db, ks).sub(2 * h, 2), VADDR16[0], off, target_gap=t0 + 0.5 * step * k))
+                        k += 1
+            return out
         for ks in range(2):
             for db in range(8):
                 out.append(isa.ds_read_b128(Vtf16(db, ks), VADDR16[ks], slot * 16384 + db * 2048, target_gap=t0 + step * k))
@@ -315,11 +339,16 @@ class Gen:
                                          (S_VLDS, VDMA, S_VRSRC, S_VOFF, S_VSTEP, S_VMAX))
         out = [isa.sop("s_add_u32", M0, lds, I32(slot * 16384), target_gap=t0 - 0.6)]
         if careful:
-            tmp, g, lim = VT0, VT2, ST[4]
+            # (Cfg.vr, V tiles: the same with the lane's row inside a V piece -- a row-major v has no rows past Lk - 1, and a masked key's
+            # P = 0 must meet a row of v, not whatever lies behind it: 0 x NaN is NaN)
+            tmp, g, lim = VT0, (VT2 if which == "k" else VT0), ST[4]
+            tailrel = S_TAILREL if which == "k" else S_VTAILREL
             out.append(isa.sop("s_cmp_eq_u32", None, off, mx, target_gap=t0 - 0.5))
             for i in range(4):
                 tg = t0 + step * i
-                out += [isa.sop("s_cselect_b32", lim, S_TAILREL[i], I32(64), target_gap=tg - 0.4),
+                if which == "v":      # the lane's row inside the 8 tile rows of a V piece: (lane >> 1) & 7 (vdma_offsets)
+                    out.append(isa.vop("v_bfe_u32", g, LANE, I32(1), I32(3), target_gap=tg - 0.45))
+                out += [isa.sop("s_cselect_b32", lim, tailrel[i], I32(64), target_gap=tg - 0.4),
                         isa.v_cmp("v_cmp_le_i32", lim, g, target_gap=tg - 0.3),                      # vcc = row beyond the valid keys
                         isa.vop("v_subrev_u32", tmp, stp, offs[i], target_gap=tg - 0.2),              # offset of the row 64 rows earlier
                         isa.v_cndmask(tmp, offs[i], tmp, target_gap=tg - 0.1),
@@ -344,7 +373,7 @@ class Gen:
         abl = c.abl.split(",")
         if not tail and "dma" not in abl:
             blk += self.dma_tile("k", (p + PK) % RD, c.dma_k_at * gs, c.dma_step * gs, careful=careful)
-            blk += self.dma_tile("v", (p + PV) % RD, c.dma_v_at * gs, c.dma_step * gs)
+            blk += self.dma_tile("v", (p + PV) % RD, c.dma_v_at * gs, c.dma_step * gs, careful=careful and c.vr)
         if "lds" not in abl:
             blk += self.v_frag_reads16(p % RD, (c.v_at if not tail else 0.0) * gs, (c.v_step if not tail else 1.0) * gs)
         if not tail:
@@ -359,7 +388,8 @@ class Gen:
                 blk += self.k_frag_reads16((p + 2) % RD, c.k_at * gs, c.k_step * gs)
             if "valu" not in abl and not nomax:
                 blk += self.rowmax16(nxt, t_kb, 84.0 * c.nq / 4.0)
-        seq = sched.schedule(blk, cap=c.cap, lookahead=c.lookahead)
+        # Cfg.vr: 32 fragment reads instead of 16 beside the same 136 gaps (Cfg.vr_behind)
+        seq = sched.schedule(blk, cap=c.cap, lookahead=c.lookahead, late_extra=c.vr_behind if c.vr else None, cheap_extra=1 if c.vr else 0)
         seq = sched.insert_lgkm_waits(seq)
         return seq
 
@@ -437,10 +467,28 @@ class Gen:
         o = [isa.sop("s_sub_u32", S_TAIL, S_LK, ST[0]), isa.sop("s_lshl_b32", ST[1], S_WAVE, I32(4)), isa.sop("s_sub_u32", ST[1], S_TAIL, ST[1])]
         for i in range(4):
             o.append(isa.sop("s_sub_u32", S_TAILREL[i], ST[1], I32(4 * i)))
+        if self.cfg.vr:       # V piece i of wave w holds tile rows 32 (w & 1) + 8 i + (lane >> 1) % 8
+            o += [isa.sop("s_and_b32", ST[2], S_WAVE, I32(1)), isa.sop("s_lshl_b32", ST[2], ST[2], I32(5)), isa.sop("s_sub_u32", ST[2], S_TAIL, ST[2])]
+            for i in range(4):
+                o.append(isa.sop("s_sub_u32", S_VTAILREL[i], ST[2], I32(8 * i)))
         return o
 
     def vdma_offsets(self, t, lkpb) -> List[Instr]:
         """V^T piece i: rows 32 w + 8 i + (lane >> 3), chunk (lane & 7) ^ ((row >> 1) & 7); t: 7 temporaries, lkpb: V^T row stride in bytes"""
+        if self.cfg.vr:
+            # V piece i (1 KiB of the tile image of v_frag_reads16, at 4096 w + 1024 i): lane l fetches the 16-byte chunk c = 8 (w >> 1) +
+            # 2 (l >> 4) + (l & 1) of tile row 32 (w & 1) + 8 i + ((l >> 1) & 7) -- 8 rows x 128 consecutive bytes per instruction;
+            # lkpb: the row stride of v in bytes (>= 256, so the offset stays >= 0 after the instruction's 1024 i)
+            o = [isa.sop("s_and_b32", ST[0], S_WAVE, I32(1)), isa.sop("s_lshl_b32", ST[0], ST[0], I32(5)),       # 32 (w & 1)
+                 isa.sop("s_lshr_b32", ST[1], S_WAVE, I32(1)), isa.sop("s_lshl_b32", ST[1], ST[1], I32(7))]       # 128 (w >> 1) bytes
+            o += [isa.vop("v_bfe_u32", t[0], LANE, I32(1), I32(3)),
+                  isa.vop("v_lshrrev_b32", t[1], I32(4), LANE), isa.vop("v_lshlrev_b32", t[1], I32(5), t[1]),      # 32 (l >> 4)
+                  isa.vop("v_and_b32", t[2], I32(1), LANE), isa.vop("v_lshl_add_u32", t[1], t[2], I32(4), t[1])]   # + 16 (l & 1)
+            o += [isa.vop("v_add_u32", t[1], ST[1], t[1]), isa.vop("v_add_u32", t[3], ST[0], t[0])]
+            for i in range(4):
+                o += [isa.vop("v_add_u32", t[4], I32(8 * i), t[3]), isa.vop("v_mul_lo_u32", t[4], t[4], lkpb),
+                      isa.vop("v_add_u32", t[4], t[4], t[1]), isa.vop("v_subrev_u32", VDMA[i], I32(1024 * i), t[4])]
+            return o
         o = [isa.vop("v_lshrrev_b32", t[0], I32(3), LANE), isa.vop("v_and_b32", t[1], I32(7), LANE),
              isa.vop("v_lshlrev_b32", t[3], I32(5), S_WAVE)]       # 32 w
         for i in range(4):
@@ -477,6 +525,7 @@ class Gen:
     def prologue(self) -> List[Instr]:
         c = self.cfg
         assert c.nq in (3, 4) and not (c.x2 and c.nq != 4), "3 or 4 query blocks per wave; the x2 kernel exists with 4 only"
+        assert not (c.x2 and c.vr), "the V-rows form exists for the self-attention kernels only"
         o: List[Instr] = [isa.label(c.name)]
         if c.x2:
             # one-time part (V0 = workitem id is overwritten by the score tiles later), then the item loop: every item reloads the kernel
@@ -515,11 +564,12 @@ class Gen:
         o += self.addr64_madd(S_VT, S_VTBS, S_B, 1) + self.addr64_madd(S_O, S_OBS, S_B, 1)
         hb = ST[6]
         o += [isa.sop("s_lshl_b32", hb, S_H, I32(8))]                              # h * 128 elements * 2 bytes
-        for ptr in (S_Q, S_K, S_O):
+        for ptr in (S_Q, S_K, S_O) + ((S_VT,) if c.vr else ()):           # (Cfg.vr: v has k's layout)
             o += [isa.sop("s_add_u32", ptr.sub(0), ptr.sub(0), hb), isa.sop("s_addc_u32", ptr.sub(1), ptr.sub(1), I32(0))]
-        # vt += h * 128 * Lkp * 2 bytes
-        o += [isa.sop("s_lshl_b32", ST[7], S_LKP, I32(8)), isa.sop("s_mul_i32", ST[8], ST[7], S_H), isa.sop("s_mul_hi_u32", ST[9], ST[7], S_H),
-              isa.sop("s_add_u32", S_VT.sub(0), S_VT.sub(0), ST[8]), isa.sop("s_addc_u32", S_VT.sub(1), S_VT.sub(1), ST[9])]
+        if not c.vr:
+            # vt += h * 128 * Lkp * 2 bytes
+            o += [isa.sop("s_lshl_b32", ST[7], S_LKP, I32(8)), isa.sop("s_mul_i32", ST[8], ST[7], S_H), isa.sop("s_mul_hi_u32", ST[9], ST[7], S_H),
+                  isa.sop("s_add_u32", S_VT.sub(0), S_VT.sub(0), ST[8]), isa.sop("s_addc_u32", S_VT.sub(1), S_VT.sub(1), ST[9])]
         # ---- buffer descriptors (raw, no bounds: every address is inside the slice by construction) ----
         for rs, ptr in ((S_KRSRC, S_K), (S_VRSRC, S_VT)):
             o += [isa.sop("s_mov_b32", rs.sub(0), ptr.sub(0)), isa.sop("s_and_b32", rs.sub(1), ptr.sub(1), I32(0xFFFF)),
@@ -533,6 +583,9 @@ class Gen:
               isa.sop("s_mul_i32", S_KMAX, ST[12], S_KSTEP), isa.sop("s_lshl_b32", S_VMAX, ST[12], I32(7)),
               isa.sop("s_lshl_b32", S_KLDS, S_WAVE, I32(12)), isa.sop("s_add_u32", S_VLDS, S_KLDS, I32(RD * 16384)),
               isa.sop("s_mov_b32", S_SEG, I32(0))]
+        if c.vr:      # the V stream walks key rows like the K stream: row stride of v in the vt_ss field, 64 rows per tile, clamped at the last tile
+            o += [isa.sop("s_lshl_b32", lkpb, S_VTSS.sub(0), I32(1)), isa.sop("s_lshl_b32", S_VSTEP, lkpb, I32(6)),
+                  isa.sop("s_mul_i32", S_VMAX, ST[12], S_VSTEP)]
         # ---- lane geometry: ql = lane % 16 (fragment row / query column), g = lane / 16 (16-byte chunk inside a 32-wide k-step) ----
         ql, g = VT1, VT2
         o += [isa.vop("v_and_b32", ql, I32(15), LANE), isa.vop("v_lshrrev_b32", g, I32(4), LANE)]
@@ -556,6 +609,12 @@ class Gen:
         for ks in range(2):
             o += [isa.vop("v_or_b32", t[2], I32(4 * ks), g), isa.vop("v_xor_b32", t[2], t[2], t[0]),
                   isa.vop("v_lshl_add_u32", VADDR16[ks], t[2], I32(4), t[1])]
+        if c.vr:
+            # the one address of the transposed reads (v_frag_reads16): lane 4 q + p of group g points at columns 4 p .. of tile row
+            # 16 (g >> 1) + 4 (g & 1) + q, chunk 0: 2048 (g >> 1) + 128 (g & 1) + 8 ql in the V ring (overwrites the two addresses above)
+            o += [isa.vop("v_lshrrev_b32", t[0], I32(1), g), isa.vop("v_and_b32", t[1], I32(1), g),
+                  isa.vop("v_lshlrev_b32", t[0], I32(11), t[0]), isa.vop("v_lshl_add_u32", t[0], t[1], I32(7), t[0]),
+                  isa.vop("v_lshl_add_u32", t[0], ql, I32(3), t[0]), isa.vop("v_add_u32", VADDR16[0], I32(RD * 16384), t[0])]
         # LDS-DMA source offsets.  K piece i of this wave: tile rows 16 w + 4 i + (lane >> 4), chunk (lane & 15) ^ f(row),
         # f(row) = row bits 0-2 | row bit 4 << 3 (bit 4 of the tile row = wave & 1)
         o += [isa.vop("v_lshrrev_b32", t[0], I32(4), LANE), isa.vop("v_and_b32", t[1], I32(15), LANE),
@@ -814,7 +873,7 @@ HEAD = """// GENERATED by scail_amd/asmgen/attn4.py -- do not edit; regenerate w
 
 def kernel(c: Cfg) -> codeobj.Kernel:
     return codeobj.Kernel(c.name, f"ring depth {RD}, <= {c.cap} fillers per MFMA gap, lookahead {c.lookahead}", isa.render(Gen(c).program()),
-                          lds_bytes=LDS_BYTES, kernarg_size=X2_KERNARG_SIZE if c.x2 else KERNARG_SIZE)
+                          lds_bytes=LDS_BYTES, kernarg_size=X2_KERNARG_SIZE if c.x2 else KERNARG_SIZE, **({"sgprs": 100} if c.vr else {}))
 
 
 def assembly(cfgs) -> str:
@@ -828,7 +887,11 @@ M16F = Cfg(name="scail_attn4_m16f")
 M16F_Q3 = Cfg(name="scail_attn4_m16f_q3", nq=3)
 # cross attention over the text and the CLIP key set (Cfg.x2): the same pipeline with persistent workgroups
 X2 = Cfg(name="scail_attn4_x2", x2=True)
+# the V-rows forms of the two self-attention kernels (Cfg.vr): v as the QKV projection wrote it, no scail_transpose_v in front
+M16F_VR = Cfg(name="scail_attn4_m16f_vr", vr=True)
+M16F_Q3_VR = Cfg(name="scail_attn4_m16f_q3_vr", nq=3, vr=True)
 SHIPPED = [M16F, M16F_Q3, X2]
+VROWS = [M16F_VR, M16F_Q3_VR]      # a code object of their own (attn4v, codeobj.CODE_OBJECTS: generated at build time, not committed): csrc/attn4.s keeps its text
 
 # timing ablations of M16F (wrong results on purpose): what each instruction class costs beside the 136 MFMAs of a tile
 ABLATIONS = ("dma", "lds", "valu", "bar", "dma,lds,valu")

@@ -110,7 +110,8 @@ class CodeObject:
     gen: str                   # generator module in this package
     lists: Tuple[str, ...]     # the generator's config lists the code object holds, in order
     variants: bool = True      # the measurement build adds the generator's variant_cfgs()
-    committed: bool = True     # csrc/<stem>.s is committed: true of every code object (tests/test_codeobj_cpu.py selects by it)
+    committed: bool = True     # csrc/<stem>.s is committed (tests/test_codeobj_cpu.py selects by it); False: the assembly is a build product,
+                               # written to the build directory by scail_amd/build.py -- the generator is its only source
 
     def module(self):
         return importlib.import_module(f"{__package__}.{self.gen}")
@@ -123,12 +124,13 @@ class CodeObject:
         return self.module().assembly(self.cfgs(variants))
 
     def path(self, objdir: str = "") -> str:
-        """csrc/<stem>.s (``objdir``: unused, the call form tests/test_codeobj_cpu.py has)"""
-        return os.path.join(CSRC, self.stem + ".s")
+        """csrc/<stem>.s of a committed code object; <objdir>/<stem>.s (the build directory) otherwise"""
+        return os.path.join(CSRC if self.committed else (objdir or os.path.join(os.path.dirname(os.path.dirname(ASMGEN)), "build")), self.stem + ".s")
 
 
 CODE_OBJECTS = [
     CodeObject("attn4", "attn4", ("SHIPPED",)),
+    CodeObject("attn4v", "attn4", ("VROWS",), variants=False, committed=False),      # 0.6 MB of text nobody reads: generated at build time
     CodeObject("gemm4", "gemm4", ("DEFAULTS",)),
     CodeObject("conv4", "conv4", ("DEFAULTS",)),
     CodeObject("conv4u", "conv4", ("UPSAMPLE", "NARROW", "FUSED", "CONT", "RESNORM"), variants=False),
@@ -143,7 +145,7 @@ def write_if_changed(path: str, text: str) -> None:
 def main(gen: str) -> None:
     """``python -m scail_amd.asmgen.<gen> [--check] [--variants DIR]``: rewrite the generator's code objects where stale; --check: exit 1
     if any of them differs from the generator instead; --variants DIR: write the measurement build's <stem>_variants.s into DIR."""
-    cos = [c for c in CODE_OBJECTS if c.gen == gen]
+    cos = [c for c in CODE_OBJECTS if c.gen == gen and (c.committed or "--variants" in sys.argv)]
     if "--variants" in sys.argv:
         dst = sys.argv[sys.argv.index("--variants") + 1]
         for c in cos:

@@ -255,6 +255,15 @@ def ds_read(nbytes: int, dst: Reg, addr: Reg, offset: int = 0, **kw) -> Instr:
     return Instr(op, [dst], [addr], mods=f"offset:{offset}" if offset else "", offset=offset, **kw)
 
 
+def ds_read_b64_tr_b16(dst: Reg, addr: Reg, offset: int = 0, **kw) -> Instr:
+    """gfx950 transposed LDS read (class DS_READ: an LGKM operation like every ds_read).  Per group of 16 consecutive lanes: lane 4 q + p of the
+    group gives the address of 4 consecutive 16-bit elements, columns 4 p .. 4 p + 3 of row q of a 4-row x 16-column block; lane i of the group
+    receives column i, row q in its 16-bit element q (two registers).  The gather crosses lanes, so EXEC must be all ones (an implicit read
+    here; the emulator refuses a partial mask) and every address must be 8-byte aligned."""
+    assert dst.n == 2 and 0 <= offset <= 65535 and offset % 8 == 0
+    return Instr("ds_read_b64_tr_b16", [dst], [addr], mods=f"offset:{offset}" if offset else "", offset=offset, extra_reads=[EXEC], **kw)
+
+
 def buffer_load_lds(voff: Reg, rsrc: Reg, soff, offset: int = 0, **kw) -> Instr:
     """LDS-DMA: 16 bytes per lane from buffer[voff + soff + offset] to LDS[m0 + offset + 16 lane]."""
     assert rsrc.n == 4 and 0 <= offset <= 4095

@@ -116,12 +116,16 @@ def build_deps(block: Sequence[Instr]) -> List[Dict[int, int]]:
     return deps
 
 
-def schedule(block: Sequence[Instr], cap: int = 5, lookahead: float = 1.0, trailing_cap: int = 0, late_extra: float = None) -> List[Instr]:
+def schedule(block: Sequence[Instr], cap: int = 5, lookahead: float = 1.0, trailing_cap: int = 0, late_extra: float = None,
+             cheap_extra: int = 0) -> List[Instr]:
     """See module docstring.  ``target_gap`` of a filler = index of the MFMA after which it would like to sit (fractional
     values order fillers inside a gap); a filler is not pulled earlier than ``target_gap - lookahead`` gaps.
     ``late_extra``: a gap takes ONE filler beyond ``cap`` when the next candidate is already more than ``late_extra`` gaps behind
     its target -- a backlog is worked off one extra instruction per gap instead of piling up until a dependent MFMA forces the
-    whole cluster into a single gap."""
+    whole cluster into a single gap.
+    ``cheap_extra`` (with ``late_extra``): up to that many fillers beyond ``cap``, and only where neither the gap so far nor the candidate is a
+    transcendental: a v_exp_f32 keeps the vector ALU busy for four issue slots, so a gap that holds one has no room, while LDS reads, LDS-DMA,
+    scalar instructions and v_cvt_pk take one slot each and share a 16-cycle gap."""
     block = list(block)
     n = len(block)
     deps = build_deps(block)
@@ -167,8 +171,18 @@ def schedule(block: Sequence[Instr], cap: int = 5, lookahead: float = 1.0, trail
     for g, m in enumerate(mf):
         force(m)
         placed = 0
+        trans = False
         for i in fillers:
-            if placed >= cap and not (late_extra is not None and placed == cap and block[i].target_gap <= g - late_extra):
+            if cheap_extra:
+                if placed >= cap and (late_extra is None or placed >= cap + cheap_extra or trans):
+                    break
+                if i in pos:
+                    continue
+                if placed >= cap and block[i].target_gap > g - late_extra:
+                    break
+                if placed >= cap and block[i].cls == isa.TRANS:
+                    continue
+            elif placed >= cap and not (late_extra is not None and placed == cap and block[i].target_gap <= g - late_extra):
                 break
             if i in pos or block[i].target_gap > g + lookahead:
                 continue
@@ -176,6 +190,7 @@ def schedule(block: Sequence[Instr], cap: int = 5, lookahead: float = 1.0, trail
                 continue
             emit(i)
             placed += 1
+            trans = trans or block[i].cls == isa.TRANS
     for i in range(n):
         if i not in pos:
             force(i)

@@ -814,6 +814,11 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void flash_attn_swp_kernel(AttnPara
 static const unsigned char k_attn4_hsaco[] = {
 #include "attn4_hsaco.inc"
 };
+// the V-rows forms of the two self-attention kernels (asmgen/attn4.py VROWS): a code object of their own, whose assembly build.py generates
+// into the build directory (not committed: the generator is its source)
+static const unsigned char k_attn4v_hsaco[] = {
+#include "attn4v_hsaco.inc"
+};
 struct Attn4Args {
     const void* q; const void* k; const void* vt; void* o;
     int64_t q_bs, q_rs, k_ss, k_bs, k_rs, vt_ss, vt_bs, o_bs, o_rs;
@@ -840,10 +845,13 @@ int scail_attn4_preload() {
     // every shipped kernel the launch plan / the cross-attention dispatch can pick, and the per-device CU count the plan reads
     for (const char* name : {"scail_attn4_m16f", "scail_attn4_m16f_q3", "scail_attn4_x2"})
         if (int rc = scail_module_function("attn4", k_attn4_hsaco, name, &fn)) return rc;
+    for (const char* name : {"scail_attn4_m16f_vr", "scail_attn4_m16f_q3_vr"})
+        if (int rc = scail_module_function("attn4v", k_attn4v_hsaco, name, &fn)) return rc;
     return scail_device_cus() > 0 ? 0 : 2;
 }
 
 static std::atomic<int> g_attn4_mode{1};     // 1 = use attn4 where eligible (default), 0 = never (8-wave kernels only)
+static std::atomic<int> g_attn_vrows{1};     // option "attn_vrows": 1 = scail_flash_attn_vrows_for says yes where the V-rows kernels can run, 0 = never
 // option "cross4": scail_attn4_x2 for the two-set cross attention.  2 (default) = by key count: measured per 256-row item at the config-2
 // query shape (profiles/r05_cross_x2_phase_probe.log): scail_attn4_x2 22.6 us + 1.5 us per key tile (1.2-1.3 in the hot loop, which a set
 // reaches from 10 tiles on), cross_attn2_kernel 8.5 us + 2.17 us per tile -> the generated kernel wins from 21 tiles of both sets together
@@ -937,6 +945,24 @@ static bool attn4_allowed(int64_t n_batch, int64_t heads, int64_t Lq) {
     const int64_t nqb = (Lq + 191) / 192, lim = 1ll << 31;       // the finer of the two query tilings
     return g_attn4_mode && heads < (1 << 15) && n_batch < (1 << 15) && nqb * heads * n_batch < lim / nqb && heads * n_batch < lim / heads;
 }
+// The V-rows kernels (scail_attn4_m16f_vr / _q3_vr: v row-major, as the QKV projection wrote it) exist for the 4-wave self-attention only, so a
+// call that hands over v this way has no other kernel to fall to: what they cannot take is refused, in words that name the value.  Empty = fine.
+static std::string attn4_vrows_refusal(int64_t q_rs, int64_t k_rs, int64_t v_rs, int64_t o_rs, int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk) {
+    const int64_t lim = (1ll << 30);     // elements -> 2^31 bytes
+    auto n = [](int64_t v) { return std::to_string(v); };
+    if (!g_attn_vrows) return "option attn_vrows is 0";
+    if (!g_attn4_mode) return "option attn4 is 0: the 8-wave kernel reads a V^T image";
+    if (g_attn4_name != k_attn4_default) return "the timing ablation " + g_attn4_name + " has no V-rows form";
+    if (Lk < 512) return "Lk = " + n(Lk) + " is below the 512 keys the 4-wave kernel starts at";
+    if (v_rs < heads * HD || v_rs % 8 != 0) return "v_rs = " + n(v_rs) + " must be a multiple of 8 and at least heads * 128 = " + n(heads * HD);
+    if (Lk * v_rs >= lim) return "Lk * v_rs = " + n(Lk * v_rs) + " elements is beyond the 32-bit byte offsets of the kernel (2^30 elements)";
+    if (Lk * k_rs >= lim) return "Lk * k_rs = " + n(Lk * k_rs) + " elements is beyond the 32-bit byte offsets of the kernel (2^30 elements)";
+    if (Lq * q_rs >= lim) return "Lq * q_rs = " + n(Lq * q_rs) + " elements is beyond the 32-bit byte offsets of the kernel (2^30 elements)";
+    if (Lq * o_rs >= lim) return "Lq * o_rs = " + n(Lq * o_rs) + " elements is beyond the 32-bit byte offsets of the kernel (2^30 elements)";
+    if (!attn4_allowed(n_batch, heads, Lq))
+        return "n_batch = " + n(n_batch) + ", heads = " + n(heads) + ", Lq = " + n(Lq) + " is beyond the kernel's workgroup-id decode";
+    return "";
+}
 
 // ------------------------------------------------------------------------------------------------
 // Which kernels, and which launches of them, a self-attention call runs.  attn_choose is the ONE statement of it: scail_flash_attn_bf16 launches
@@ -945,7 +971,8 @@ static bool attn4_allowed(int64_t n_batch, int64_t heads, int64_t Lq) {
 // and its helpers above (attn4_plan, attn4_eligible, attn4_allowed -- the last shared with cross_choose) reads options "attn4", "attn4_rows",
 // "attn4_cus", "attn4_xcd", the thread's rows hint, g_attn4_name or the measurement build's attn_variant.
 // ------------------------------------------------------------------------------------------------
-enum AttnFamily { ATTN_GEN,          // generated: scail_attn4_m16f (+ _q3), or the timing ablation the measurement build's "attn4_kernel" knob names
+enum AttnFamily { ATTN_NONE,         // v handed over row-major (v_rs > 0) and the V-rows kernels cannot take the call: AttnChoice::why says which value
+                  ATTN_GEN,          // generated: scail_attn4_m16f (+ _q3), or the timing ablation the measurement build's "attn4_kernel" knob names
                   ATTN_W8,           // the product's 8-wave kernel
                   ATTN_VARIANT };    // measurement build: a schedule of the 8-wave family forced with "attn_variant"
 // a hipcc kernel of the 8-wave family as the launch needs it: scail_launch_lds of the instantiation (which opts it in to `lds` bytes of
@@ -987,15 +1014,25 @@ struct AttnChoice {
     AttnKernel hip = k_attn_w8;  // ATTN_W8 / ATTN_VARIANT: the launch
     int variant = 0;             // ATTN_VARIANT: the attn_variant code
     const char* name = nullptr;  // ATTN_GEN: the base symbol (g_attn4_name's characters); a 192-row launch runs name + "_q3"
+    bool vrows = false;          // ATTN_GEN: the V-rows forms, name [+ "_q3"] + "_vr" (v row-major, no scail_transpose_v in front)
+    std::string why;             // ATTN_NONE: the refusal
     int n_launch = 0;            // ATTN_GEN with a plan: 1 or 2 launches; -1: the plan needs the device's CU count and there is none
     Attn4Launch launch[2] = {};
 };
 
 // want_plan == false answers the family and the kernel alone, which needs no device; the plan of the shipped generated kernel is sized by the
 // device's compute units (attn4_plan) unless option "attn4_rows" or the thread's hint forces a height.
+// v_rs: the V layout of the call -- 0: a V^T image of scail_transpose_v (scail_flash_attn_bf16); > 0: v row-major with this row stride
+// (scail_flash_attn_vrows_bf16: the V-rows kernels or nothing, which also reads option "attn_vrows").
 static AttnChoice attn_choose(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk, int accumulate,
-                              bool /* prescaled: every kernel takes q in either form */, bool want_plan) {
+                              bool /* prescaled: every kernel takes q in either form */, bool want_plan, int64_t v_rs = 0) {
     AttnChoice c;
+    if (v_rs != 0) {
+        c.why = attn4_vrows_refusal(q_rs, k_rs, v_rs, o_rs, n_batch, heads, Lq, Lk);
+        c.family = ATTN_NONE;
+        if (!c.why.empty()) return c;
+        c.vrows = true;
+    }
     if (attn4_allowed(n_batch, heads, Lq) && attn4_eligible(q_rs, k_rs, o_rs, Lq, Lk, accumulate)) {
         c.family = ATTN_GEN;
         c.name = g_attn4_name.c_str();
@@ -1019,6 +1056,10 @@ static AttnChoice attn_choose(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t 
         }
         return c;
     }
+    if (v_rs != 0) {                     // (what attn4_vrows_refusal lets through and attn4_eligible does not: the V^T image's own limit)
+        c.why = "Lk = " + std::to_string(Lk) + " is beyond the kernel's 32-bit byte offsets";
+        return c;
+    }
 #ifdef SCAIL_ABLATIONS
     if (g_attn_variant != (8 | (2 << 12))) {
         c.family = ATTN_VARIANT;
@@ -1033,7 +1074,8 @@ static AttnChoice attn_choose(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t 
 // The choice in words: a hipcc kernel's template with the arguments of the instantiation, "attn_variant <code>: " in front where the measurement
 // build forced it; a generated kernel's symbol -- of launch `li` of the plan (the launch resolves its kernel by it), or the base symbol (li < 0)
 static std::string attn_choice_name(const AttnChoice& c, int li) {
-    if (c.family == ATTN_GEN) return li >= 0 && c.launch[li].rows == 192 ? std::string(c.name) + "_q3" : std::string(c.name);
+    if (c.family == ATTN_NONE) return "none";
+    if (c.family == ATTN_GEN) return std::string(c.name) + (li >= 0 && c.launch[li].rows == 192 ? "_q3" : "") + (c.vrows ? "_vr" : "");
     return c.family == ATTN_VARIANT ? "attn_variant " + std::to_string(c.variant) + ": " + c.hip.name : c.hip.name;
 }
 
@@ -1048,11 +1090,28 @@ extern "C" int scail_flash_attn_kernel_for(int64_t q_rs, int64_t k_rs, int64_t o
     return attn_choose(q_rs, k_rs, o_rs, 1, 1, Lq, Lk, accumulate, prescaled != 0, false).family == ATTN_GEN ? 4 : 8;
 }
 
+static int attn_choice_report(const AttnChoice& c, int64_t n_batch, int64_t heads, int64_t Lq, char* buf, int64_t len, int64_t* plan);
 extern "C" int scail_flash_attn_kernel_name_for(int64_t q_rs, int64_t k_rs, int64_t o_rs, int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk,
                                                 int accumulate, int prescaled, char* buf, int64_t len, int64_t* plan) {
     SCAIL_REQUIRE(buf != nullptr, "null argument");
     SCAIL_REQUIRE(n_batch >= 1 && heads >= 1 && Lq >= 1 && Lk >= 1, "need at least one pair, one query and one key");
-    const AttnChoice c = attn_choose(q_rs, k_rs, o_rs, n_batch, heads, Lq, Lk, accumulate, prescaled != 0, plan != nullptr);
+    return attn_choice_report(attn_choose(q_rs, k_rs, o_rs, n_batch, heads, Lq, Lk, accumulate, prescaled != 0, plan != nullptr), n_batch, heads, Lq,
+                              buf, len, plan);
+}
+
+extern "C" int scail_flash_attn_vrows_for(int64_t q_rs, int64_t k_rs, int64_t v_rs, int64_t o_rs, int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk) {
+    return v_rs > 0 && n_batch >= 1 && heads >= 1 && Lq >= 1 && attn_choose(q_rs, k_rs, o_rs, n_batch, heads, Lq, Lk, 0, true, false, v_rs).family == ATTN_GEN;
+}
+
+extern "C" int scail_flash_attn_vrows_kernel_name_for(int64_t q_rs, int64_t k_rs, int64_t v_rs, int64_t o_rs, int64_t n_batch, int64_t heads, int64_t Lq,
+                                                      int64_t Lk, char* buf, int64_t len, int64_t* plan) {
+    SCAIL_REQUIRE(buf != nullptr, "null argument");
+    SCAIL_REQUIRE(n_batch >= 1 && heads >= 1 && Lq >= 1 && Lk >= 1 && v_rs >= 1, "need at least one pair, one query, one key and a row stride of v");
+    return attn_choice_report(attn_choose(q_rs, k_rs, o_rs, n_batch, heads, Lq, Lk, 0, true, plan != nullptr, v_rs), n_batch, heads, Lq, buf, len, plan);
+}
+
+// what the two name queries write: the choice in words and, where asked for, its launches
+static int attn_choice_report(const AttnChoice& c, int64_t n_batch, int64_t heads, int64_t Lq, char* buf, int64_t len, int64_t* plan) {
     if (c.n_launch < 0) return 2;                       // (scail_device_cus left the message)
     std::string name = attn_choice_name(c, c.n_launch > 0 ? 0 : -1);
     if (c.n_launch == 2) name += " + " + attn_choice_name(c, 1);
@@ -1060,6 +1119,7 @@ extern "C" int scail_flash_attn_kernel_name_for(int64_t q_rs, int64_t k_rs, int6
     std::memcpy(buf, name.c_str(), name.size() + 1);
     if (plan == nullptr) return 0;
     std::fill(plan, plan + 9, (int64_t)0);
+    if (c.family == ATTN_NONE) return 0;                // "none": no launch
     if (c.family != ATTN_GEN) {                         // a hipcc kernel: one launch, a workgroup per (query block, head, batch element)
         const int64_t v[5] = {1, c.hip.qblk, 0, (Lq + c.hip.qblk - 1) / c.hip.qblk * heads * n_batch, 0};
         std::copy(v, v + 5, plan);
@@ -1085,6 +1145,7 @@ int scail_conv_s2_enable(int v);       // conv.hip
 extern "C" int scail_set_option(const char* name, int value) {
     const std::string k(name ? name : "");
     if (k == "attn4") { g_attn4_mode = value != 0; return 0; }              // 0: 8-wave kernel for every shape
+    if (k == "attn_vrows") { g_attn_vrows = value != 0; return 0; }         // 0: scail_flash_attn_vrows_for says no: callers transpose V as before
     if (k == "cross4") {                                                    // 2: scail_attn4_x2 from 21 key tiles on; 1: wherever eligible; 0: never
         SCAIL_REQUIRE(value >= 0 && value <= 2, "cross4 must be 0, 1 or 2");
         g_cross4 = value;
@@ -1176,6 +1237,54 @@ static void attn4_fill(Attn4Args& a, const void* q, int64_t q_bs, int64_t q_rs, 
     a.items_per_xcd = (a.n_items + 7) / 8;
 }
 
+// The launches of a generated self-attention choice: scail_attn4_m16f / _q3 (or the timing ablation chosen with the measurement build's
+// "attn4_kernel" knob) on a V^T image, or their V-rows forms, for which ``vt`` is v itself and ``vt_ss`` its row stride (asmgen/attn4.py Cfg.vr).
+// The generated kernels work on scores in log2 units: sl2 = 0 says q carries scale * log2(e) already, any other value is multiplied into the Q
+// fragments once in the prologue; their lazy-rescale threshold is in log2 units.
+static int attn4_launch(const AttnChoice& c, const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_ss, int64_t k_bs, int64_t k_rs,
+                        const void* vt, int64_t vt_ss, int64_t vt_bs, void* o, int64_t o_bs, int64_t o_rs, int64_t /* n_batch */, int64_t heads,
+                        int64_t Lq, int64_t Lk, int64_t n_seg, float sl2_arg, void* stream) {
+    if (c.n_launch < 0) return 2;
+    const float thr_log2 = g_attn4_thr_log2;
+    for (int li = 0; li < c.n_launch; ++li) {
+        hipFunction_t fn;
+        if (int rc = c.vrows ? scail_module_function("attn4v", k_attn4v_hsaco, attn_choice_name(c, li), &fn)
+                             : scail_module_function("attn4", k_attn4_hsaco, attn_choice_name(c, li), &fn)) return rc;
+        Attn4Args a;
+        attn4_fill(a, q, q_bs, q_rs, k, k_ss, k_bs, k_rs, vt, vt_ss, vt_bs, o, o_bs, o_rs, heads, Lq, Lk, n_seg, c.launch[li]);
+        a.sl2 = sl2_arg;
+        a.thr = thr_log2;
+        a.restarts = g_attn4_restart_ctr;
+        if (int rc = scail_module_launch("attn4", fn, (unsigned)c.launch[li].grid, 256, a, stream)) return rc;
+    }
+    return 0;
+}
+
+extern "C" int scail_flash_attn_vrows_bf16(const scail_bf16* q, int64_t q_bs, int64_t q_rs,
+                                           const scail_bf16* k, int64_t k_bs, int64_t k_rs,
+                                           const scail_bf16* v, int64_t v_bs, int64_t v_rs,
+                                           scail_bf16* o, int64_t o_bs, int64_t o_rs,
+                                           int64_t n_batch, int64_t heads, int64_t Lq, int64_t Lk, float scale, void* stream) {
+    SCAIL_REQUIRE(Lk >= 1 && heads >= 1 && n_batch >= 0 && Lq >= 0, "need at least one key and one head");
+    SCAIL_REQUIRE(q_rs % 8 == 0 && k_rs % 8 == 0 && v_rs % 8 == 0 && o_rs % 4 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0 && o_bs % 4 == 0,
+                  "strides must keep 16-byte (q,k,v) / 8-byte (o) alignment");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0 && (reinterpret_cast<uintptr_t>(k) & 15) == 0 &&
+                      (reinterpret_cast<uintptr_t>(v) & 15) == 0 && (reinterpret_cast<uintptr_t>(o) & 7) == 0,
+                  "pointer alignment");
+    const bool prescaled = scale == SCAIL_ATTN_Q_PRESCALED;
+    SCAIL_REQUIRE(prescaled || (scale > 0.0f && scale < 3.0e38f), "scale must be a positive finite number or SCAIL_ATTN_Q_PRESCALED");
+    SCAIL_REQUIRE(Lq < (1ll << 31) && Lk < (1ll << 31) - 64, "sequence too long");
+    SCAIL_REQUIRE(v_rs >= 1, "v_rs = " + std::to_string(v_rs) + ": v is row-major here, its row stride must be positive");
+    const AttnChoice c = attn_choose(q_rs, k_rs, o_rs, n_batch ? n_batch : 1, heads, Lq ? Lq : 1, Lk, 0, prescaled, true, v_rs);
+    if (c.family != ATTN_GEN) {
+        scail_set_error("scail_flash_attn_vrows_bf16: " + c.why + " (scail_flash_attn_vrows_for says which calls run; scail_transpose_v + scail_flash_attn_bf16 takes the rest)");
+        return 1;
+    }
+    if (Lq == 0 || n_batch == 0) return 0;
+    return attn4_launch(c, q, q_bs, q_rs, k, 0, k_bs, k_rs, v, v_rs, v_bs, o, o_bs, o_rs, n_batch, heads, Lq, Lk, 1,
+                        prescaled ? 0.0f : scale * 1.4426950408889634f, stream);
+}
+
 extern "C" int scail_flash_attn_bf16(const scail_bf16* q, int64_t q_bs, int64_t q_rs,
                                      const scail_bf16* k, int64_t k_ss, int64_t k_bs, int64_t k_rs,
                                      const scail_bf16* vt, int64_t vt_ss, int64_t vt_bs,
@@ -1197,24 +1306,8 @@ extern "C" int scail_flash_attn_bf16(const scail_bf16* q, int64_t q_bs, int64_t 
     SCAIL_REQUIRE(Lq < (1ll << 31) && Lkp * n_seg < (1ll << 31), "sequence too long");
     if (Lq == 0 || n_batch == 0) return 0;
     const AttnChoice c = attn_choose(q_rs, k_rs, o_rs, n_batch, heads, Lq, Lk, accumulate, prescaled, true);
-    if (c.family == ATTN_GEN) {
-        // scail_attn4_m16f (or the timing ablation chosen with the measurement build's "attn4_kernel" knob).  The generated kernels
-        // work on scores in log2 units: sl2 = 0 says q carries scale * log2(e) already, any other value is multiplied into the Q
-        // fragments once in the prologue; their lazy-rescale threshold is in log2 units.
-        if (c.n_launch < 0) return 2;
-        const float thr_log2 = g_attn4_thr_log2;
-        for (int li = 0; li < c.n_launch; ++li) {
-            hipFunction_t fn;
-            if (int rc = scail_module_function("attn4", k_attn4_hsaco, attn_choice_name(c, li), &fn)) return rc;
-            Attn4Args a;
-            attn4_fill(a, q, q_bs, q_rs, k, k_ss, k_bs, k_rs, vt, vt_ss, vt_bs, o, o_bs, o_rs, heads, Lq, Lk, n_seg, c.launch[li]);
-            a.sl2 = prescaled ? 0.0f : sl2;
-            a.thr = thr_log2;
-            a.restarts = g_attn4_restart_ctr;
-            if (int rc = scail_module_launch("attn4", fn, (unsigned)c.launch[li].grid, 256, a, stream)) return rc;
-        }
-        return 0;
-    }
+    if (c.family == ATTN_GEN)
+        return attn4_launch(c, q, q_bs, q_rs, k, k_ss, k_bs, k_rs, vt, vt_ss, vt_bs, o, o_bs, o_rs, n_batch, heads, Lq, Lk, n_seg, prescaled ? 0.0f : sl2, stream);
     AttnParams p;
     p.q = q; p.q_bs = q_bs; p.q_rs = q_rs;
     p.k = k; p.k_ss = k_ss; p.k_bs = k_bs; p.k_rs = k_rs;

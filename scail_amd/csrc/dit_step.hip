@@ -408,9 +408,17 @@ static int dit_block(scail_dit* h, int64_t i, scail_bf16* hid, const float* m, c
     DIT_TRY(scail_ln_modulate(hid, D, bf.xn, D, m, m + D, 6 * D, Bs, Ltok, Ltok, 0, D, eps, stream));
     DIT_PROF(SCAIL_DIT_PROF_GEMM, dit_gemm(h, i, G_QKV, bf, bf.xn, D, lw.qkv_b, qkv, 3 * D, M, 3 * D, D, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
     DIT_TRY(scail_rmsnorm_rope(k, 3 * D, k, 3 * D, lw.kn, rope_cos, rope_sin, M, Ltok, D, 128, eps, stream));
-    DIT_TRY(scail_transpose_v(v, 3 * D, Ltok * 3 * D, bf.vt, Bs, nh, 128, Ltok, stream));
+    // V as projected where the V-rows kernels take the call (include/scail_hip.h scail_flash_attn_vrows_bf16: bit-identical, no V^T pass);
+    // the V^T image of the workspace serves every other call
+    const bool vrows = scail_flash_attn_vrows_for(3 * D, 3 * D, 3 * D, D, Bs, nh, rows, Ltok) != 0;
+    if (!vrows) DIT_TRY(scail_transpose_v(v, 3 * D, Ltok * 3 * D, bf.vt, Bs, nh, 128, Ltok, stream));
     // the queries go to the attention in log2 units (q * scale * log2 e, one rounding): its exp2 then needs no scale / shift per score
     DIT_TRY(scail_rmsnorm_rope_scaled(q, 3 * D, q, 3 * D, lw.qn, rope_cos, rope_sin, M, Ltok, D, 128, eps, ATTN_LOG2_SCALE, stream));
+    if (vrows) {
+        DIT_PROF(SCAIL_DIT_PROF_SELF_ATTN, scail_flash_attn_vrows_bf16(q + row0 * 3 * D, Ltok * 3 * D, 3 * D, k, Ltok * 3 * D, 3 * D, v, Ltok * 3 * D, 3 * D,
+                                                                       bf.att + row0 * D, Ltok * D, D, Bs, nh, rows, Ltok, SCAIL_ATTN_Q_PRESCALED, stream));
+        return block_tail(h, i, hid, m, cond, B, Ltok, bf, row0, rows, pair, stream);
+    }
     DIT_PROF(SCAIL_DIT_PROF_SELF_ATTN, scail_flash_attn_bf16(q + row0 * 3 * D, Ltok * 3 * D, 3 * D, k, 0, Ltok * 3 * D, 3 * D, bf.vt, 0, nh * 128 * Lp,
                                                              bf.att + row0 * D, Ltok * D, D, Bs, nh, rows, Ltok, 1, SCAIL_ATTN_Q_PRESCALED, 0, stream));
     return block_tail(h, i, hid, m, cond, B, Ltok, bf, row0, rows, pair, stream);
@@ -519,12 +527,18 @@ static int dit_block_sp(scail_dit* h, int64_t i, scail_bf16* hid, const float* m
             const scail_bf16* recv = sp->recv + b * 3 * N * slab;       // [N * Ltok][3 Dn]: all ranks' tokens (rank-major), q | k | v of my heads
             scail_bf16* vt = bf.vt + b * Hn * 128 * Lfp;
             scail_bf16* of = sp->ofull + b * N * slab;
-            DIT_TRY(scail_transpose_v(recv + 2 * Dn, 3 * Dn, 0, vt, 1, Hn, 128, Lf, s));
+            const bool vrows = scail_flash_attn_vrows_for(3 * Dn, 3 * Dn, 3 * Dn, Dn, 1, Hn, Lf, Lf) != 0;      // (dit_block)
+            if (!vrows) DIT_TRY(scail_transpose_v(recv + 2 * Dn, 3 * Dn, 0, vt, 1, Hn, 128, Lf, s));
             // two elements' launches run side by side on the two streams and fill each other's partial rounds: one 256-row launch each
             // (a lone launch gets the planned shape: whole 256-row rounds + 192-row tiles for the rest, csrc/attn.hip attn4_plan)
             struct Hint { Hint(int r) { scail_attn4_rows_hint(r); } ~Hint() { scail_attn4_rows_hint(0); } } hint(side && B > 1 ? 256 : 0);
-            DIT_PROF_S(SCAIL_DIT_PROF_SELF_ATTN, s, scail_flash_attn_bf16(recv, 0, 3 * Dn, recv + Dn, 0, 0, 3 * Dn, vt, 0, 0, of, 0, Dn, 1, Hn, Lf, Lf, 1,
-                                                                          SCAIL_ATTN_Q_PRESCALED, 0, s));
+            if (vrows) {
+                DIT_PROF_S(SCAIL_DIT_PROF_SELF_ATTN, s, scail_flash_attn_vrows_bf16(recv, 0, 3 * Dn, recv + Dn, 0, 3 * Dn, recv + 2 * Dn, 0, 3 * Dn, of, 0, Dn, 1, Hn,
+                                                                                    Lf, Lf, SCAIL_ATTN_Q_PRESCALED, s));
+            } else {
+                DIT_PROF_S(SCAIL_DIT_PROF_SELF_ATTN, s, scail_flash_attn_bf16(recv, 0, 3 * Dn, recv + Dn, 0, 0, 3 * Dn, vt, 0, 0, of, 0, Dn, 1, Hn, Lf, Lf, 1,
+                                                                              SCAIL_ATTN_Q_PRESCALED, 0, s));
+            }
             DIT_TRY(sp_exchange(sp, SCAIL_SP_BACK_START, i, b, s));
         }
         for (int64_t b = 0; b < B; ++b) {
@@ -564,6 +578,11 @@ static int dit_block_sp(scail_dit* h, int64_t i, scail_bf16* hid, const float* m
             DIT_PROF(SCAIL_DIT_PROF_XCH_FWD_WAIT, sp_exchange(sp, SCAIL_SP_FWD_WAIT, i, b, stream));
             const scail_bf16* recv = sp->recv + b * 2 * N * rowsD;      // [N * Ltok][2 D]: gathered rows (rank-major), k | v
             scail_bf16* vt = bf.vt + b * nh * 128 * Lfp;
+            if (scail_flash_attn_vrows_for(3 * D, 2 * D, 2 * D, D, 1, nh, rows, Lf) != 0) {                       // (dit_block)
+                DIT_PROF(SCAIL_DIT_PROF_SELF_ATTN, scail_flash_attn_vrows_bf16(q + (b * Ltok + row0) * 3 * D, 0, 3 * D, recv, 0, 2 * D, recv + D, 0, 2 * D,
+                                                                               bf.att + b * rowsD + row0 * D, 0, D, 1, nh, rows, Lf, SCAIL_ATTN_Q_PRESCALED, stream));
+                continue;
+            }
             DIT_TRY(scail_transpose_v(recv + D, 2 * D, 0, vt, 1, nh, 128, Lf, stream));
             DIT_PROF(SCAIL_DIT_PROF_SELF_ATTN, scail_flash_attn_bf16(q + (b * Ltok + row0) * 3 * D, 0, 3 * D, recv, 0, 0, 2 * D, vt, 0, 0, bf.att + b * rowsD + row0 * D, 0, D,
                                                                      1, nh, rows, Lf, 1, SCAIL_ATTN_Q_PRESCALED, 0, stream));

@@ -30,6 +30,9 @@ SIGNATURES = {
                               _i64, _i64, _i64, _i64, _i64, _f, _i, _p],
     "scail_flash_attn_kernel_for": [_i64, _i64, _i64, _i64, _i64, _i, _i],
     "scail_flash_attn_kernel_name_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _p, _i64, _p],
+    "scail_flash_attn_vrows_bf16": [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _i64, _i64, _f, _p],
+    "scail_flash_attn_vrows_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64],
+    "scail_flash_attn_vrows_kernel_name_for": [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p],
     "scail_flash_attn_rows_for": [_i64, _i64, _i64],
     "scail_flash_attn_count_restarts": [_p],
     "scail_comm_standin": [_p, _p, _i64, C.c_int32, _i64, _p],

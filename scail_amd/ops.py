@@ -312,6 +312,27 @@ def flash_attn(q, k, vt, out=None, scale=None, accumulate=False, n_seg=1, k_seg_
     return out
 
 
+def flash_attn_vrows(q, k, v, out=None, scale=None, q_prescaled=False):
+    """flash_attn on v as it is -- (B|1, Lk, H*128) view like k, no transpose_v image (include/scail_hip.h scail_flash_attn_vrows_bf16: the 4-wave
+    kernel's V-rows forms or an error; L.load().scail_flash_attn_vrows_for says which calls run).  Bit-identical to transpose_v + flash_attn."""
+    _chk(q, bf16, "flash_attn_vrows.q"); _chk(k, bf16, "k"); _chk(v, bf16, "v")
+    B, Lq, D = q.shape
+    H = D // 128
+    assert D == H * 128 and q.stride(2) == 1 and k.stride(2) == 1 and v.stride(2) == 1 and v.shape == k.shape
+    if out is None:
+        out = torch.empty(B, Lq, D, device=q.device, dtype=bf16)
+    _chk(out, bf16, "flash_attn_vrows.out")
+    assert out.stride(2) == 1
+    if scale is None:
+        scale = 1.0 / math.sqrt(128)
+    if q_prescaled:
+        scale = ATTN_Q_PRESCALED
+    L.call("scail_flash_attn_vrows_bf16", q.data_ptr(), q.stride(0), q.stride(1), k.data_ptr(), 0 if k.shape[0] == 1 else k.stride(0), k.stride(1),
+           v.data_ptr(), 0 if v.shape[0] == 1 else v.stride(0), v.stride(1), out.data_ptr(), out.stride(0), out.stride(1), B, H, Lq, k.shape[1], scale,
+           _stream())
+    return out
+
+
 def cross_attn2(q, k1, vt1, k2, vt2, out=None, scale=None, q_prescaled=False):
     """softmax(q k1^T) v1 + softmax(q k2^T) v2 in one launch (text + CLIP cross attention, dit_video_crossattn_sc_xc.py:1107-1203).
     q (B, Lq, H*128) view; k1 / k2 (B|1, Lk, H*128) views; vt1 / vt2 (B|1, H, 128, ceil64(Lk)) transpose_v images.

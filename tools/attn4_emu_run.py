@@ -74,6 +74,8 @@ def run(cfg: attn4.Cfg, q: np.ndarray, ksegs, vsegs, heads: int, lazy: bool = Tr
     pq = mem.alloc("q", qb)
     pk = mem.alloc("k", kb)
     pvt = mem.alloc("vt", vt)
+    # the V-rows kernels (Cfg.vr) read v as it is: one segment, rows of D elements; the arena refuses any read past its last key row
+    pv = mem.alloc("v", to_bf16_bits(vsegs[0])) if any(l[0].vr for l in (launches or [(cfg,)])) else 0
     po = mem.alloc("o", np.zeros((B, Lq, D), dtype=np.uint16))
     pctr = mem.alloc("restarts", np.zeros(4, dtype=np.uint32))          # the optional restart counter of the kernel arguments
     thr = thr_log2                                      # the kernels see scores in log2 units
@@ -88,7 +90,9 @@ def run(cfg: attn4.Cfg, q: np.ndarray, ksegs, vsegs, heads: int, lazy: bool = Tr
         m = attn4.xcd_mode(B, heads) if lmode is None else lmode
         total = ((Lq + lcfg.rows - 1) // lcfg.rows) * heads * B
         n = total - item0 if n_items is None else n_items
-        args = attn4.pack_args(pq, pk, pvt, po, Lq * D, D, B * Lk * D, Lk * D, D, B * heads * 128 * Lkp, heads * 128 * Lkp, Lq * D, D,
+        assert not (lcfg.vr and n_seg != 1), "the V-rows kernels take one key segment"
+        vargs = (pv, D, Lk * D) if lcfg.vr else (pvt, B * heads * 128 * Lkp, heads * 128 * Lkp)       # vt | vt_ss (Cfg.vr: the row stride of v) | vt_bs
+        args = attn4.pack_args(pq, pk, vargs[0], po, Lq * D, D, B * Lk * D, Lk * D, D, vargs[1], vargs[2], Lq * D, D,
                                heads, Lq, Lk, Lkp, n_seg, sl2, thr, n_batch=B, mode=m, rows=lcfg.rows, item0=item0, n_items=n,
                                restarts=pctr if count_restarts else 0)
         for wid in range(attn4.grid_for(n, m)):

@@ -27,14 +27,20 @@ def main():
             d[(m.group(1), m.group(2))] = float(m.group(3))
     path = os.path.join(ROOT, "profiles", "traffic.json")
     tr = json.load(open(path))
-    if ("scail_attn4_m16f", "FETCH_SIZE") in d:      # (a summary may hold only some of the kernels: the other entries stay)
-      f, w = d[("scail_attn4_m16f", "FETCH_SIZE")], d[("scail_attn4_m16f", "WRITE_SIZE")]
+    # the self-attention kernel the executor runs: scail_attn4_m16f_vr (tools/attn_pmc_probe.py prescaled 3 vrows) where the summary has it,
+    # scail_attn4_m16f (the V^T route, option "attn_vrows" = 0) otherwise
+    ak = next((k for k in ("scail_attn4_m16f_vr", "scail_attn4_m16f") if (k, "FETCH_SIZE") in d and (k, "WRITE_SIZE") in d), None)
+    if ak is not None:      # (a summary may hold only some of the kernels: the other entries stay)
+      f, w = d[(ak, "FETCH_SIZE")], d[(ak, "WRITE_SIZE")]
       tr["flash_attn_self"] = {
         "shape": {"B": 2, "heads": 40, "Lq": 48832, "Lk": 48832}, "fetch_kib": f, "write_kib": w,
         "traffic_bytes": (2 * f + w) * 1024,
-        "kernel": "scail_attn4_m16f (16x16x32 MFMAs, queries in log2 units, optimistic hot loop, XCD-aware workgroup ids)",
+        "kernel": ak + " (16x16x32 MFMAs, queries in log2 units, optimistic hot loop, XCD-aware workgroup ids" +
+                  ("; V row-major as projected, no scail_transpose_v pass in front)" if ak.endswith("_vr") else ")"),
         "source": "attn4.s", "source_blob": blob(os.path.join(ROOT, "scail_amd", "csrc", "attn4.s")),
-        "measured": note + "; algorithmic bytes per launch = Q + K + V^T + O of 80 (batch, head) slices = 4.0 GB"}
+        "measured": note + "; algorithmic bytes per launch = Q + K + V + O of 80 (batch, head) slices = 4.0 GB"}
+      if ak.endswith("_vr"):      # the V-rows kernels are generated at build time (code object attn4v); bench.py keys the entry on attn4.s
+        tr["flash_attn_self"].update(kernel_source="scail_amd/asmgen/attn4.py VROWS (code object attn4v, generated at build time)")
     # the six per-token GEMMs of a block: launches per layer e0 x 2 (qkv, cross q), e3 x 2 (attention out, MLP down), e1 (MLP up), e4 (cross out)
     n = {"e0": 2, "e1": 1, "e3": 2, "e4": 1}
     if all(("scail_gemm4_" + k, "FETCH_SIZE") in d for k in n):
