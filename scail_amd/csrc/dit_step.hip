@@ -1006,6 +1006,8 @@ extern "C" int scail_dit_sample_chars(scail_dit* h, float* x, const float* times
     SCAIL_REQUIRE(step_bytes >= 0, "bad latent shape");
     const SampleWs ws = sample_ws(step_bytes, T, H, W);
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= ws.total, "workspace too small (scail_dit_sample_workspace_bytes)");
+    // (the step refuses it too, but only after this loop has copied x into the workspace: a refused workspace is left untouched)
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
     DIT_TRY(probe_check(h, 2 * tok_lens(n_char, T, H, W).Ltok));
     char* base = static_cast<char*>(workspace);
     float *xin = reinterpret_cast<float*>(base + ws.xin), *v = reinterpret_cast<float*>(base + ws.v);
