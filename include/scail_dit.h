@@ -361,6 +361,72 @@ int scail_dit_sample_tiled(scail_dit* h, float* x, const float* timesteps, const
                            const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
                            void* stream);
 
+/*
+ * ---- step cache (an EXTENSION, opt-in; the scheme the community calls TeaCache: reuse the block residual on skipped steps) ---------------
+ * Over a run of adjacent sampler steps the 40 blocks change the hidden states by nearly the same amount.  A FILL evaluation is a full
+ * evaluation that also keeps r = (hidden states after the last block) - (patch embedding), on the noise rows -- the only rows the final
+ * layer reads, so r is [B, Lnoise, D], not [B, Ltok, D].  A REUSE evaluation adds that r to THIS step's freshly embedded noise rows and
+ * runs the final layer: no block, no pose embedding.  Which steps reuse is the caller's plan; scail_dit_time_distances below gives the
+ * signal the usual plan is made from (it depends on the sigma schedule alone, so the plan is known before the loop starts and the
+ * sampler stays ONE call with no host synchronisation).  Nothing here changes an existing entry point, its launches, its workspace
+ * query or its result.
+ *
+ * scail_dit_step_cache_bytes: bytes of the caller-owned, 256-byte aligned cache of a (B, T, H, W) evaluation (-1: null handle / bad
+ *   shape, like the workspace queries).  Layout: r bf16 [B][Lnoise][D] at offset 0, Lnoise = T (H/2) (W/2) -- callers may read it --, then,
+ *   from the next multiple of 256, FILL's copy of the embedded noise rows, bf16 [B][Lnoise][D] (the blocks work in place, so the
+ *   embedding has to be kept aside until the residual is formed; under SCAIL_DIT_CFG_PAIR its first element serves both), rounded to
+ *   256.  It does not depend on n_char, and the step / sample workspace queries do not change.
+ *
+ * scail_dit_step_cached: scail_dit_step_chars + (mode, cache, cache_bytes).
+ *   SCAIL_DIT_CACHE_FILL   the evaluation of scail_dit_step_chars -- fp8 GEMMs, the probe and SCAIL_DIT_CFG_PAIR included; `out` is
+ *                          bit-identical to it --, which additionally copies the noise rows [Lref, Lref + Lnoise) of the patch embedding into
+ *                          the cache and, after the last block, stores r with scail_resid_store (scail_hip.h).  Under SCAIL_DIT_CFG_PAIR
+ *                          the embedding exists once and serves both elements (batch stride 0).
+ *   SCAIL_DIT_CACHE_REUSE  time and final-layer tables as usual; patchify; the patch GEMM on the noise rows only (once under
+ *                          SCAIL_DIT_CFG_PAIR) -- every kernel computes a row from that row alone, so these are the bits of the full
+ *                          embedding --; scail_resid_apply of r into every element's noise rows, in place; then the existing final layer:
+ *                          scail_ln_modulate, the 64-column GEMM, scail_unpatchify.  No block runs, the pose GEMM does not run, `cond`
+ *                          is not read (it may be NULL) and the cache is only read.
+ *   That the cache was filled by a FILL of this handle with the same (B, T, H, W) is the caller's statement, like SCAIL_DIT_CFG_PAIR: it
+ *   is not checked on the device.  A REUSE on a cache that was never filled adds whatever the buffer holds.
+ *
+ * scail_dit_sample_cached: scail_dit_sample_chars + (reuse, cache, cache_bytes).  reuse = HOST uint8 [n_steps], read during the call:
+ *   step i runs in REUSE mode where reuse[i] == 1, else in FILL mode; the cache is that of (2, T, H, W).  The same loop otherwise: it only
+ *   enqueues, nothing synchronises, and it is capturable on the same terms as scail_dit_sample.  An all-zero mask gives the bits of
+ *   scail_dit_sample_chars.
+ *
+ * Refused before anything is enqueued, with an error that names the value: a mode other than the two; a null cache, one smaller than
+ * scail_dit_step_cache_bytes, one that is not 256-byte aligned; reuse == NULL with n_steps > 0; reuse[0] != 0 (the first step has nothing
+ * to reuse); an entry other than 0 or 1.  The checks that need no handle come first.
+ *
+ * scail_dit_time_distances: for the DEVICE fp32 timesteps [n_steps] (= 1000 sigma_i) the handle's own time embedding of every step, by
+ *   the very calls of a step (scail_timestep_embedding, scail_small_linear; scail_small_linear takes at most 8 rows, so in chunks of 8
+ *   steps), and between consecutive steps out[i] = scail_abs_diff_sums(v_i, v_{i-1}) for i >= 1, out[0] = {0, 0}; out = DEVICE fp64
+ *   [n_steps][2], so out[i][0] / out[i][1] is the relative L1 change of the signal from step i - 1 to step i.  signal 0: v = emb, the
+ *   output of time_embed.2, [time_embed_dim]; signal 1: v = its AdaLN projection, [6 D] (what every block's modulation is made of).
+ *   scratch >= scail_dit_time_distances_bytes(h, signal) bytes (-1: null handle / unknown signal), 256-byte aligned.  Nothing
+ *   synchronises: the host reads the table after the stream has finished.  Refused before anything is enqueued: an unknown signal, n_steps
+ *   outside 0 .. 2^20 - 1 (both named), a null handle / pointer, a scratch that is too small or misaligned.
+ *
+ * Out of scope, each because no *_cached entry point exists for it: the tiled loop (scail_dit_sample_tiled; a follow-up can give it one
+ * cache per tile), the sequence-parallel calls (scail_dit_step_sp*), and the per-block seam (scail_dit_block*).
+ */
+#define SCAIL_DIT_CACHE_FILL 1
+#define SCAIL_DIT_CACHE_REUSE 2
+int64_t scail_dit_step_cache_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W);
+int scail_dit_step_cached(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
+                          const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
+                          const float* rope_cos, const float* rope_sin, float* out,
+                          int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes,
+                          int mode, void* cache, int64_t cache_bytes, void* stream);
+int scail_dit_sample_cached(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                            const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose, int64_t n_char, int64_t pose_frames,
+                            const float* rope_cos, const float* rope_sin, int64_t T, int64_t H, int64_t W,
+                            void* workspace, int64_t workspace_bytes, const uint8_t* reuse, void* cache, int64_t cache_bytes, void* stream);
+int64_t scail_dit_time_distances_bytes(const scail_dit* h, int signal);
+int scail_dit_time_distances(scail_dit* h, const float* timesteps, int64_t n_steps, int signal, double* out, void* scratch,
+                             int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,9 @@ const char* scail_last_error(void);
  * scail_vae_decode_u8 / scail_vae_decode_stream_u8, for the row-kernel query scail_row_kernel_name_for, for the attention queries
  * scail_flash_attn_kernel_name_for / scail_cross_attn2_kernel_name_for, and for the fp8 probe, scail_rel_err_rows and scail_dit.h's scail_dit_fp8_select_layers /
  * scail_dit_fp8_probe / scail_dit_fp8_probe_bytes, and for MX block scaling of the fp8 GEMMs, scail_quant_mxfp8_rows / scail_gemm_mxfp8 and
- * scail_dit.h's scail_dit_fp8_weight_bytes_scaled / scail_dit_enable_fp8_scaled.) */
+ * scail_dit.h's scail_dit_fp8_weight_bytes_scaled / scail_dit_enable_fp8_scaled, and for the step cache, scail_resid_store /
+ * scail_resid_apply / scail_abs_diff_sums and scail_dit.h's scail_dit_step_cache_bytes / scail_dit_step_cached / scail_dit_sample_cached /
+ * scail_dit_time_distances / scail_dit_time_distances_bytes.) */
 int scail_abi_version(void);
 
 /* ---- epilogues of scail_gemm_bf16 ---------------------------------------------------------- */
@@ -603,6 +605,40 @@ int scail_release_caches(void);
  * plumbing for boundary tensors.  Errors: n < 0 or 2^31 workgroups or more, a null pointer with n > 0. */
 int scail_f32_to_bf16(const float* x, scail_bf16* y, int64_t n, void* stream);
 int scail_bf16_to_f32(const scail_bf16* x, float* y, int64_t n, void* stream);
+
+/*
+ * The row kernels of the step cache (scail_dit.h SCAIL_DIT_CACHE_FILL / _REUSE): the change a run of blocks made to a window of hidden-state
+ * rows, kept and added back.  All operands are bf16 with row stride D; element b of an operand starts b * (its batch stride, in elements)
+ * after the base; r is dense [n_batch, rows, D].
+ *   scail_resid_store:  r[b,i,j] = bf16(float(h_out[b,i,j]) - float(h_in[b,i,j]))
+ *   scail_resid_apply:  h[b,i,j] = bf16(float(h_in[b,i,j]) + float(r[b,i,j]))
+ * ONE fp32 operation and ONE rounding to nearest even per element, like scail_f32_to_bf16 and with its conventions: denormals are kept,
+ * not flushed; a NaN stays a NaN (inf - inf and inf + -inf give one); an fp32 result beyond the largest bf16 rounds to inf.  in_bs may be 0:
+ * ONE h_in for every b (the embedded tokens of a classifier-free-guidance pair exist once).  A row window of a larger matrix is passed
+ * as the pointer to its first row.
+ * In place: scail_resid_apply accepts h == h_in with in_bs == h_bs, and h == h_in with in_bs == 0 (element 0 is both the input of every
+ * element and an output).  One thread owns an 8-column chunk of EVERY element: it reads h_in's chunk before it writes h's (in_bs == 0:
+ * once, before its first write), and no other thread touches that chunk of any element.  Any other overlap of h and h_in is refused.
+ * Both are bandwidth-bound streaming passes: 16-byte loads and stores, at most 2048 workgroups with a grid-stride loop.
+ * Checked on the host before any launch, with an error that names the value: n_batch outside 0..64, rows outside 0 .. 2^31 - 1,
+ * D % 8 != 0 or D outside 8 .. 2^20 - 8, a batch stride that is negative or no multiple of 8, h_bs below rows * D with n_batch > 1 (the output elements would
+ * overlap), a null or not 16-byte aligned base pointer, an overlap of h and h_in other than the two above.  scail_resid_store's r must not
+ * overlap its inputs (not checked).  n_batch == 0 or rows == 0 is accepted and launches nothing.
+ */
+int scail_resid_store(const scail_bf16* h_out, int64_t out_bs, const scail_bf16* h_in, int64_t in_bs, scail_bf16* r,
+                      int64_t n_batch, int64_t rows, int64_t D, void* stream);
+int scail_resid_apply(const scail_bf16* h_in, int64_t in_bs, const scail_bf16* r, scail_bf16* h, int64_t h_bs,
+                      int64_t n_batch, int64_t rows, int64_t D, void* stream);
+
+/*
+ * scail_abs_diff_sums: out[0] = sum_j |a_j - b_j|, out[1] = sum_j |b_j| for fp32 a, b [n]; out = device fp64 [2], overwritten.  Every a_j
+ * and b_j is widened to fp64 before the subtraction, so a term carries no fp32 rounding.  ONE launch of ONE workgroup (n is a few 10^4
+ * at most where the library uses it: the 6 D modulation values of two timesteps, scail_dit.h scail_dit_time_distances): thread t of 256
+ * adds its terms j = t, t + 256, .. in ascending order, then a binary tree joins the 256 partial sums.  The order is fixed by n alone
+ * and there are no floating-point atomics: the same inputs give the same bits, as scail_rel_err_rows promises.  n == 0 writes {0, 0}.
+ * Errors before the launch: n outside 0 .. 2^31 - 1 (named), out null or not 8-byte aligned, a or b null with n > 0 or not 4-byte aligned.
+ */
+int scail_abs_diff_sums(const float* a, const float* b, int64_t n, double* out, void* stream);
 
 /* ---- fp8 per-token GEMMs (OCP e4m3fn, one fp32 scale per row of each operand) -------------------------------------------
  * scail_quant_fp8_rows: q[r, c] (uint8 e4m3 codes, row stride ldq) and s[r] from bf16 x[r, c] (row stride ldx), per row:

@@ -253,6 +253,43 @@ def fp8_scaling_arg(value, gemm_precision):
     return value
 
 
+def step_cache_args(threshold, coefficients=None, keep=None, signal=None):
+    """``--step-cache-threshold`` / ``--step-cache-coefficients`` / ``--step-cache-keep`` / ``--step-cache-signal`` -> the ``step_cache`` option
+    of RFSampler.sample_hip, or None when no threshold is given (the other three only shape the plan a threshold makes)."""
+    if threshold is None:
+        if coefficients is not None or keep is not None or signal is not None:
+            raise ValueError("--step-cache-coefficients / --step-cache-keep / --step-cache-signal need --step-cache-threshold (they shape its plan)")
+        return None
+    threshold = float(threshold)
+    if not threshold >= 0.0:
+        raise ValueError(f"--step-cache-threshold must be a number >= 0, got {threshold}")
+    opt = {"threshold": threshold, "signal": "time" if signal is None else signal}
+    if opt["signal"] not in lib.CACHE_SIGNALS:
+        raise ValueError(f"--step-cache-signal must be one of {sorted(lib.CACHE_SIGNALS)}, got {signal!r}")
+    if coefficients is not None:
+        try:
+            opt["coefficients"] = [float(v) for v in str(coefficients).split(",")]
+        except ValueError:
+            raise ValueError(f"--step-cache-coefficients must be numbers separated by commas, highest degree first, got {coefficients!r}")
+        if not opt["coefficients"]:
+            raise ValueError("--step-cache-coefficients must hold at least one number")
+    if keep is not None:
+        try:
+            first, last = (int(v) for v in str(keep).split(","))
+        except ValueError:
+            raise ValueError(f"--step-cache-keep must be FIRST,LAST (two integers), got {keep!r}")
+        if first < 1 or last < 0:
+            raise ValueError(f"--step-cache-keep needs FIRST >= 1 (step 0 has nothing to reuse) and LAST >= 0, got {keep!r}")
+        opt["keep_first"], opt["keep_last"] = first, last
+    return opt
+
+
+def format_step_cache_plan(plan):
+    """The plan as text: which steps compute, and k of n"""
+    computed = [i for i, v in enumerate(plan) if not v]
+    return f"step cache: {len(computed)} of {len(plan)} steps compute the blocks ({', '.join(map(str, computed))}); the others reuse the last computed residual"
+
+
 def format_fp8_table(cal, max_rel_err):
     """The probe's result as text: a heading that names the scaling probed (cal["scaling"]; "row" when absent), one row per layer, one
     column per GEMM, then the (layer, GEMM) pairs left in bf16."""
@@ -276,9 +313,11 @@ def _calibrate(engine, c, uc, shape, steps, fp8_max_error):
 
 
 def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frames=None, engine=None, tile_frames=None, tile_overlap=None,
-        vae_chunk_frames=None, postprocess="torch", fp8_max_error=None):
+        vae_chunk_frames=None, postprocess="torch", fp8_max_error=None, step_cache=None):
     """``fp8_max_error`` (fp8 networks only): probe the request's first evaluation and keep in bf16 every (layer, GEMM) whose fp8 result is
     further than this from bf16 (engine.calibrate_fp8).
+    ``step_cache``: None, or the step-cache option (step_cache_args; RFSampler.sample_hip): steps whose time embedding moved little reuse the
+    block residual of the last computed step.  One window, one rank; the plan is printed.
     ``postprocess``: "torch" (default) returns the video as fp32 (B, 3, T, H, W) in [0, 1]; "hip" returns it as the file writers' pixels,
     uint8 (B, T, H, W, 3) on the device, written by the VAE decoder's last kernel (engine.decode_first_stage_u8; needs a GPU)."""
     if postprocess not in POSTPROCESS_ROUTES:
@@ -300,6 +339,9 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     if n_pix > (net.num_frames if tile_frames is None else tile_frames):      # longer than one window: temporal tiles (an extension)
         if (n_pix - 1) % 4:
             raise ValueError(f"a pose clip longer than one window needs 4n + 1 frames (the causal VAE's frame groups), got {n_pix}")
+        if step_cache is not None:
+            raise NotImplementedError("--step-cache-threshold is not combined with temporal tiles (a pose clip longer than one window): the tiled "
+                                      "loop has no cached form")
         Tt, overlap = tile_args(tile_frames, tile_overlap, net.num_frames)
         tiles = plan_tiles((n_pix - 1) // 4 + 1, Tt, overlap)
         return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames, postprocess, fp8_max_error)
@@ -313,7 +355,11 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     uc = dict(crossattn=req["uncond_context"], **shared)
     _calibrate(engine, c, uc, (T, C, h, w), steps, fp8_max_error)
     torch.manual_seed(seed)
-    z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps)
+    if step_cache is None:
+        z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps)
+    else:
+        z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, step_cache=step_cache)
+        print(format_step_cache_plan(engine.sampler.last_step_cache_plan))
     return _finish(engine, z, t0, vae_chunk_frames, postprocess)
 
 
@@ -398,6 +444,20 @@ def build_parser() -> argparse.ArgumentParser:
                          "and keep in bf16 every (layer, GEMM) whose fp8 result is further than this (relative error against its bf16 "
                          "twin) from bf16; prints the table.  No measured table of a real checkpoint exists yet: choose the value from "
                          "the printed table of your own weights")
+    ap.add_argument("--step-cache-threshold", type=float, default=None,
+                    help="opt-in step cache (an extension): a sampler step reuses the change the blocks made to the hidden states at the last "
+                         "computed step, and runs only the patch embedding and the final layer, while the accumulated relative change of the "
+                         "time embedding since that step stays below this number; 0 computes every step.  The plan is printed.  No value is "
+                         "recommended: nothing has been measured on real weights, and random-init weights say nothing about quality.  "
+                         "Single GPU, one window")
+    ap.add_argument("--step-cache-coefficients", default=None,
+                    help="with --step-cache-threshold: polynomial applied to each step's relative change before it is accumulated, "
+                         "comma-separated, highest degree first (default 1,0: the identity).  No fitted values are shipped")
+    ap.add_argument("--step-cache-keep", default=None,
+                    help="with --step-cache-threshold: FIRST,LAST = steps at the start (>= 1) and at the end that always compute (default 1,1)")
+    ap.add_argument("--step-cache-signal", choices=tuple(lib.CACHE_SIGNALS), default=None,
+                    help="with --step-cache-threshold: what is compared between steps: time = the timestep embedding (default), "
+                         "modulation = its AdaLN projection, the 6 D values every block is modulated with")
     ap.add_argument("--tile-frames", type=int, default=None,
                     help="pixel frames per temporal window, 4n + 1 (default: the network's num_frames); a pose clip with more frames is sampled "
                          "in overlapping windows (RFSamplerLong), an extension of the reference CLI; such a clip needs 4n + 1 frames")
@@ -448,6 +508,9 @@ def main(argv=None):
                 cfg = copy.deepcopy(cfg)
             cfg["model"]["network_config"].setdefault("params", {})["fp8_scaling"] = a.fp8_scaling
         tk["fp8_max_error"] = fp8_max_error_arg(a.fp8_max_error, cfg["model"]["network_config"].get("params", {}).get("gemm_precision", "bf16"))
+        sc = step_cache_args(a.step_cache_threshold, a.step_cache_coefficients, a.step_cache_keep, a.step_cache_signal)
+        if sc is not None:
+            tk["step_cache"] = sc
     except ValueError as e:
         ap.error(str(e))
     lines = [(r, i) for i, r in enumerate(a.request)] + (list(read_from_file(a.input_file)) if a.input_file else [])

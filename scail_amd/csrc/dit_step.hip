@@ -282,6 +282,21 @@ static SampleWs sample_ws(int64_t step, int64_t Tv, int64_t H, int64_t W, int64_
     return {step, step + pair, step + 2 * pair, step + 2 * pair + align256(Tden * F * 4)};
 }
 
+// the step cache of a (B, T, H, W) evaluation: r bf16 [B][Lnoise][D] at offset 0 (documented: callers read it), then FILL's copy of the
+// embedded noise rows, [B][Lnoise][D] too (one element of it is used under SCAIL_DIT_CFG_PAIR)
+enum { CACHE_NONE = 0 };
+struct CacheWs {
+    int64_t r, emb, total;
+};
+static CacheWs cache_ws(const scail_dit_config& c, int64_t B, int64_t Lnoise) {
+    Carve cv;
+    CacheWs s;
+    s.r = cv.take(B * Lnoise * c.hidden_size * 2);
+    s.emb = cv.take(B * Lnoise * c.hidden_size * 2);
+    s.total = cv.off;
+    return s;
+}
+
 // x quantised into the block's scratch and multiplied with the quantised weight f, under the handle's scaling
 static int fp8_quant_gemm(const scail_dit* h, const scail_dit::Fp8W& f, const BlockBufs& bf, const scail_bf16* x, int64_t lda, const float* bias,
                           scail_bf16* y, int64_t ldc, int64_t M, int64_t N, int64_t K, int epi, const scail_bf16* resid, int64_t ldr,
@@ -858,9 +873,10 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
                          const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
                          const float* rope_cos, const float* rope_sin, float* out,
                          int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace, int64_t workspace_bytes,
-                         void* stream) {
+                         void* stream, int mode = CACHE_NONE, void* cache = nullptr) {
     DIT_TRY(chars_check("scail_dit_step", n_char, pose_frames, T));
-    SCAIL_REQUIRE(h != nullptr && cond != nullptr, "null handle / conditioning");
+    const bool reuse = mode == SCAIL_DIT_CACHE_REUSE;      // no block runs: the conditioning is not read
+    SCAIL_REQUIRE(h != nullptr && (cond != nullptr || reuse), "null handle / conditioning");
     SCAIL_REQUIRE((flags & ~(uint32_t)SCAIL_DIT_CFG_PAIR) == 0, "unknown step flag");
     SCAIL_REQUIRE(!(flags & SCAIL_DIT_CFG_PAIR) || (B == 2 && n_ref == 1 && n_pose == 1),
                   "SCAIL_DIT_CFG_PAIR needs B == 2 with one shared ref / pose (element 1 = element 0 except for the conditioning)");
@@ -873,13 +889,13 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
         return 1;
     }
     SCAIL_REQUIRE((n_ref == 1 || n_ref == B) && (n_pose == 1 || n_pose == B), "ref / pose batch must be 1 or B");
-    SCAIL_REQUIRE(cond->Bc == 1 || cond->Bc == B, "clip batch must be 1 or B");
+    SCAIL_REQUIRE(reuse || cond->Bc == 1 || cond->Bc == B, "clip batch must be 1 or B");
     const scail_dit_config& c = h->cfg;
     const Ws s = sp ? layout(h, B, T, H, W, n_char, sp->mode, sp->ranks) : layout(h, B, T, H, W, n_char);
     SCAIL_REQUIRE(c.time_embed_dim == c.hidden_size, "final-layer table add needs time_embed_dim == hidden_size");
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= s.total, "workspace too small (scail_dit_workspace_bytes)");
     SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
-    if (sp == nullptr) DIT_TRY(probe_check(h, B * tok_lens(n_char, T, H, W).Ltok));
+    if (sp == nullptr && !reuse) DIT_TRY(probe_check(h, B * tok_lens(n_char, T, H, W).Ltok));
 
     const int64_t D = c.hidden_size, nl = c.num_layers;
     const float eps = c.layernorm_epsilon;
@@ -916,15 +932,37 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
     } else {
         DIT_TRY(scail_patchify_chars(x, ref, pose, tok, Be, n_ref, n_pose, n_char, T, H, W, KPAD, stream));
     }
-    for (int64_t b = 0; b < Be; ++b) {
+    // the step cache (include/scail_dit.h "step cache"): r = what the blocks added to the noise rows at the last FILL, and FILL's copy of
+    // the embedded noise rows (the blocks work in place on hid)
+    const CacheWs cw = cache_ws(c, B, Lnoise);
+    scail_bf16* cache_r = mode == CACHE_NONE ? nullptr : reinterpret_cast<scail_bf16*>(static_cast<char*>(cache) + cw.r);
+    scail_bf16* cache_emb = mode == CACHE_NONE ? nullptr : reinterpret_cast<scail_bf16*>(static_cast<char*>(cache) + cw.emb);
+    scail_bf16* hid_noise = hid + Lref * D;
+    if (reuse) {
+        // the noise rows of the patch embedding only (every GEMM row comes from its own input row: the bits of the full embedding), plus
+        // the cached residual, into every element's noise rows; then straight to the final layer.  The cache is only read.
+        for (int64_t b = 0; b < Be; ++b)
+            DIT_TRY(scail_gemm_bf16(tok + (b * Ltok + Lref) * KPAD, KPAD, w.patch_w, w.patch_b, hid_noise + b * Ltok * D, D, Lnoise, D, KPAD,
+                                    SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
+        DIT_TRY(scail_resid_apply(hid_noise, pair ? 0 : Ltok * D, cache_r, hid_noise, Ltok * D, B, Lnoise, D, stream));
+    }
+    for (int64_t b = 0; b < (reuse ? 0 : Be); ++b) {
         DIT_TRY(scail_gemm_bf16(tok + b * Ltok * KPAD, KPAD, w.patch_w, w.patch_b, hid + b * Ltok * D, D, Lrn, D, KPAD,
                                 SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
         DIT_TRY(scail_gemm_bf16(tok + (b * Ltok + Lrn) * KPAD, KPAD, w.pose_w, w.pose_b, hid + (b * Ltok + Lrn) * D, D, Lpose, D,
                                 KPAD, SCAIL_EPI_BIAS, nullptr, 0, nullptr, 0, 0, stream));
     }
 
+    if (mode == SCAIL_DIT_CACHE_FILL)
+        for (int64_t b = 0; b < Be; ++b)
+            if (hipMemcpyAsync(cache_emb + b * Lnoise * D, hid_noise + b * Ltok * D, (size_t)Lnoise * D * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream) !=
+                hipSuccess) {
+                scail_set_error("scail_dit_step_cached: hipMemcpyAsync failed");
+                return 2;
+            }
+
     const BlockBufs bf = s.blk.bufs(workspace);
-    for (int64_t i = 0; i < nl; ++i) {
+    for (int64_t i = 0; i < (reuse ? 0 : nl); ++i) {
         // the last layer's output is only read at the noise tokens (final layer below): queries / out-projection / cross attention /
         // MLP of its ref and pose rows are skipped (23 % of that layer's post-K/V work; same result)
         const bool last = i == nl - 1;
@@ -935,6 +973,9 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
             DIT_TRY(dit_block(h, i, hid, mod + i * B * 6 * D, cond, rope_cos, rope_sin, B, Ltok, bf, row0, rows, pair && i == 0, stream));
         }
     }
+
+    // (under the pair flag the embedding exists once and serves both elements: batch stride 0)
+    if (mode == SCAIL_DIT_CACHE_FILL) DIT_TRY(scail_resid_store(hid_noise, Ltok * D, cache_emb, pair ? 0 : Lnoise * D, cache_r, B, Lnoise, D, stream));
 
     // ---- final layer on the noise tokens only + unpatchify (dit...:818-835, :764-784) ----
     DIT_TRY(scail_ln_modulate(hid, D, xf, D, fin, fin + D, 2 * D, B, Lnoise, Ltok, Lref, D, eps, stream));
@@ -996,10 +1037,12 @@ extern "C" int scail_dit_sample(scail_dit* h, float* x, const float* timesteps, 
                                   workspace_bytes, stream);
 }
 
-extern "C" int scail_dit_sample_chars(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps,
-                                      float cfg_scale, const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose,
-                                      int64_t n_char, int64_t pose_frames, const float* rope_cos, const float* rope_sin,
-                                      int64_t T, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes, void* stream) {
+// the Euler loop; reuse == nullptr: every step a plain evaluation (scail_dit_sample_chars), else step i in SCAIL_DIT_CACHE_REUSE mode
+// where reuse[i] != 0 and in SCAIL_DIT_CACHE_FILL mode otherwise (scail_dit_sample_cached, which has checked reuse and the cache)
+static int sample_impl(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps,
+                       float cfg_scale, const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose,
+                       int64_t n_char, int64_t pose_frames, const float* rope_cos, const float* rope_sin,
+                       int64_t T, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes, void* stream, const uint8_t* reuse, void* cache) {
     DIT_TRY(chars_check("scail_dit_sample", n_char, pose_frames, T));
     SCAIL_REQUIRE(h != nullptr && x != nullptr && timesteps != nullptr && dsigma != nullptr && n_steps >= 0, "null argument");
     const int64_t step_bytes = scail_dit_chars_workspace_bytes(h, 2, T, H, W, n_char);
@@ -1020,9 +1063,142 @@ extern "C" int scail_dit_sample_chars(scail_dit* h, float* x, const float* times
             scail_set_error("scail_dit_sample: hipMemcpyAsync failed");
             return 2;
         }
-        DIT_TRY(scail_dit_step_chars(h, xin, timesteps + 2 * i, cond, ref, 1, pose, 1, n_char, pose_frames, rope_cos, rope_sin, v, 2, T, H, W,
-                                     SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream));
+        const int mode = reuse == nullptr ? CACHE_NONE : reuse[i] ? SCAIL_DIT_CACHE_REUSE : SCAIL_DIT_CACHE_FILL;
+        DIT_TRY(dit_step_impl(h, xin, timesteps + 2 * i, cond, ref, 1, pose, 1, n_char, pose_frames, rope_cos, rope_sin, v, 2, T, H, W, nullptr,
+                              SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream, mode, cache));
         DIT_TRY(scail_cfg_euler(x, v, n, cfg_scale, dsigma[i], stream));
+    }
+    return 0;
+}
+extern "C" int scail_dit_sample_chars(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps,
+                                      float cfg_scale, const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose,
+                                      int64_t n_char, int64_t pose_frames, const float* rope_cos, const float* rope_sin,
+                                      int64_t T, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes, void* stream) {
+    return sample_impl(h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose, n_char, pose_frames, rope_cos, rope_sin, T, H, W, workspace,
+                       workspace_bytes, stream, nullptr, nullptr);
+}
+
+// ---- the step cache (include/scail_dit.h "step cache") ----
+extern "C" int64_t scail_dit_step_cache_bytes(const scail_dit* h, int64_t B, int64_t T, int64_t H, int64_t W) {
+    if (h == nullptr || shape_fault(B, T, H, W, 1, 1) != 0) return -1;
+    return cache_ws(h->cfg, B, tok_lens(1, T, H, W).Lnoise).total;
+}
+// mode and cache of a *_cached call, before anything is enqueued: what needs no handle first (the message names the value)
+static int cache_check(const char* who, const scail_dit* h, int mode, bool need_mode, const void* cache, int64_t cache_bytes, int64_t B, int64_t T,
+                       int64_t H, int64_t W) {
+    auto fail = [&](const std::string& msg) {
+        scail_set_error(std::string(who) + ": " + msg);
+        return 1;
+    };
+    if (need_mode && mode != SCAIL_DIT_CACHE_FILL && mode != SCAIL_DIT_CACHE_REUSE)
+        return fail("unknown cache mode " + std::to_string(mode) + " (SCAIL_DIT_CACHE_FILL = 1 or SCAIL_DIT_CACHE_REUSE = 2)");
+    if (cache == nullptr) return fail("null cache (cache_bytes " + std::to_string(cache_bytes) + "; scail_dit_step_cache_bytes)");
+    if ((reinterpret_cast<uintptr_t>(cache) & 255) != 0)
+        return fail("the cache must be 256-byte aligned, got an address that is " + std::to_string(reinterpret_cast<uintptr_t>(cache) & 255) + " past a multiple of 256");
+    if (h == nullptr) return fail("null handle");
+    const int64_t need = scail_dit_step_cache_bytes(h, B, T, H, W);
+    if (need < 0) return fail("bad latent shape (B " + std::to_string(B) + ", T " + std::to_string(T) + ", H " + std::to_string(H) + ", W " + std::to_string(W) + ")");
+    if (cache_bytes < need)
+        return fail("cache too small: " + std::to_string(cache_bytes) + " bytes, needs " + std::to_string(need) + " (scail_dit_step_cache_bytes)");
+    return 0;
+}
+extern "C" int scail_dit_step_cached(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
+                                     const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
+                                     const float* rope_cos, const float* rope_sin, float* out,
+                                     int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes,
+                                     int mode, void* cache, int64_t cache_bytes, void* stream) {
+    DIT_TRY(cache_check("scail_dit_step_cached", h, mode, true, cache, cache_bytes, B, T, H, W));
+    return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, n_char, pose_frames, rope_cos, rope_sin, out, B, T, H, W, nullptr, flags,
+                         workspace, workspace_bytes, stream, mode, cache);
+}
+extern "C" int scail_dit_sample_cached(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps,
+                                       float cfg_scale, const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose,
+                                       int64_t n_char, int64_t pose_frames, const float* rope_cos, const float* rope_sin,
+                                       int64_t T, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
+                                       const uint8_t* reuse, void* cache, int64_t cache_bytes, void* stream) {
+    const char* who = "scail_dit_sample_cached";
+    if (n_steps > 0) {
+        if (reuse == nullptr) {
+            scail_set_error(std::string(who) + ": null reuse mask with n_steps = " + std::to_string(n_steps));
+            return 1;
+        }
+        for (int64_t i = 0; i < n_steps; ++i)
+            if (reuse[i] > 1) {
+                scail_set_error(std::string(who) + ": reuse[" + std::to_string(i) + "] = " + std::to_string((int)reuse[i]) + " (an entry is 0 = compute or 1 = reuse)");
+                return 1;
+            }
+        if (reuse[0] != 0) {
+            scail_set_error(std::string(who) + ": reuse[0] = " + std::to_string((int)reuse[0]) + ": the first step has nothing to reuse, it must compute");
+            return 1;
+        }
+    }
+    DIT_TRY(cache_check(who, h, 0, false, cache, cache_bytes, 2, T, H, W));
+    return sample_impl(h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose, n_char, pose_frames, rope_cos, rope_sin, T, H, W, workspace,
+                       workspace_bytes, stream, reuse, cache);
+}
+
+// ---- the decision signal of the step cache: distances of consecutive steps' time embeddings (include/scail_dit.h) ----
+constexpr int64_t TD_CHUNK = 8;     // scail_small_linear takes M <= 8
+// temb | e1 | emb | adaln: the signal's buffer holds TD_CHUNK + 1 rows -- row 0 is the last step of the chunk before
+struct TimeDistWs {
+    int64_t temb, e1, emb, adaln, total;
+};
+static TimeDistWs time_dist_ws(const scail_dit_config& c, int signal) {
+    Carve cv;
+    TimeDistWs s;
+    s.temb = cv.take(TD_CHUNK * c.time_freq_dim * 4);
+    s.e1 = cv.take(TD_CHUNK * c.time_embed_dim * 4);
+    s.emb = cv.take((TD_CHUNK + 1) * c.time_embed_dim * 4);
+    s.adaln = cv.take(signal == 1 ? (TD_CHUNK + 1) * 6 * (int64_t)c.hidden_size * 4 : 0);
+    s.total = cv.off;
+    return s;
+}
+extern "C" int64_t scail_dit_time_distances_bytes(const scail_dit* h, int signal) {
+    if (h == nullptr || (signal != 0 && signal != 1)) return -1;
+    return time_dist_ws(h->cfg, signal).total;
+}
+extern "C" int scail_dit_time_distances(scail_dit* h, const float* timesteps, int64_t n_steps, int signal, double* out, void* scratch,
+                                        int64_t scratch_bytes, void* stream) {
+    const char* who = "scail_dit_time_distances";
+    auto fail = [&](const std::string& msg) {
+        scail_set_error(std::string(who) + ": " + msg);
+        return 1;
+    };
+    if (signal != 0 && signal != 1) return fail("unknown signal " + std::to_string(signal) + " (0 = the time embedding, 1 = its AdaLN projection)");
+    if (n_steps < 0 || n_steps >= (1 << 20)) return fail("n_steps must be 0 .. 2^20 - 1, got " + std::to_string(n_steps));
+    if (h == nullptr) return fail("null handle");
+    if (n_steps == 0) return 0;
+    if (timesteps == nullptr || out == nullptr) return fail("null pointer: timesteps / out");
+    if ((reinterpret_cast<uintptr_t>(out) & 7) != 0) return fail("out must be 8-byte aligned");
+    const scail_dit_config& c = h->cfg;
+    const TimeDistWs s = time_dist_ws(c, signal);
+    if (scratch == nullptr || scratch_bytes < s.total)
+        return fail("scratch too small: " + std::to_string(scratch_bytes) + " bytes, needs " + std::to_string(s.total) + " (scail_dit_time_distances_bytes)");
+    if ((reinterpret_cast<uintptr_t>(scratch) & 255) != 0) return fail("scratch must be 256-byte aligned");
+    char* base = static_cast<char*>(scratch);
+    float *temb = reinterpret_cast<float*>(base + s.temb), *e1 = reinterpret_cast<float*>(base + s.e1), *emb = reinterpret_cast<float*>(base + s.emb),
+          *adaln = reinterpret_cast<float*>(base + s.adaln);
+    const scail_dit_weights& w = h->w;
+    const int64_t Dt = c.time_embed_dim, width = signal == 1 ? 6 * (int64_t)c.hidden_size : Dt;
+    float* v = signal == 1 ? adaln : emb;            // rows 1 .. m: this chunk's steps; row 0: the step before the chunk
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(out, 0, 2 * sizeof(double), st) != hipSuccess) {      // out[0] = {0, 0}: the first step has no predecessor
+        scail_set_error(std::string(who) + ": hipMemsetAsync failed");
+        return 2;
+    }
+    for (int64_t s0 = 0; s0 < n_steps; s0 += TD_CHUNK) {
+        const int64_t m = std::min(TD_CHUNK, n_steps - s0);
+        // the step's own composition (dit_step_impl): sinusoid -> time_embed.0 + SiLU -> time_embed.2 [-> SiLU + adaln_projection.1]
+        DIT_TRY(scail_timestep_embedding(timesteps + s0, temb, m, c.time_freq_dim, stream));
+        DIT_TRY(scail_small_linear(temb, w.time0_w, w.time0_b, e1, m, Dt, c.time_freq_dim, 0, 1, stream));
+        DIT_TRY(scail_small_linear(e1, w.time2_w, w.time2_b, emb + Dt, m, Dt, Dt, 0, 0, stream));
+        if (signal == 1) DIT_TRY(scail_small_linear(emb + Dt, w.adaln_w, w.adaln_b, adaln + width, m, width, Dt, 1, 0, stream));
+        for (int64_t j = s0 == 0 ? 1 : 0; j < m; ++j)
+            DIT_TRY(scail_abs_diff_sums(v + (j + 1) * width, v + j * width, width, out + 2 * (s0 + j), stream));
+        if (s0 + m < n_steps && hipMemcpyAsync(v, v + m * width, (size_t)width * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+            scail_set_error(std::string(who) + ": hipMemcpyAsync failed");
+            return 2;
+        }
     }
     return 0;
 }

@@ -1040,6 +1040,137 @@ extern "C" int scail_bf16_to_f32(const scail_bf16* x, float* y, int64_t n, void*
 }
 
 // ================================================================================================
+// Step cache (include/scail_hip.h scail_resid_store / scail_resid_apply / scail_abs_diff_sums; the executor's SCAIL_DIT_CACHE_* modes).
+// The two residual kernels are streaming passes: one 16-byte load / store (8 bf16) per lane and operand, a grid capped at
+// RESID_MAX_WGS workgroups with a grid-stride loop over the 8-column chunks.  Rows are D apart in every operand, so the rows of one
+// batch element are one contiguous run of rows * D elements and a chunk index needs no division by D.
+// ================================================================================================
+constexpr int RESID_MAX_WGS = 2048;     // 256 CUs x 8 workgroups
+
+// r[b, c] = bf16(float(hout[b, c]) - float(hin[b, c])): chunk c of element b; hin's batch stride may be 0
+__global__ __launch_bounds__(256) void resid_store_kernel(const u16* __restrict__ hout, int64_t out_bs, const u16* __restrict__ hin, int64_t in_bs,
+                                                          u16* __restrict__ r, int64_t per_b8, int64_t total8) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total8; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / per_b8, c = i - b * per_b8;
+        float fo[8], fi[8];
+        unpack8(*reinterpret_cast<const uint4*>(hout + b * out_bs + c * 8), fo);
+        unpack8(*reinterpret_cast<const uint4*>(hin + b * in_bs + c * 8), fi);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) fo[e] = fo[e] - fi[e];
+        *reinterpret_cast<uint4*>(r + i * 8) = pack8(fo);
+    }
+}
+
+// h[b, c] = bf16(float(hin[b, c]) + float(r[b, c])).  ONE thread owns chunk c of EVERY element: it reads hin[b, c] before it writes
+// h[b, c] (in_bs == 0: hin[c] once, before its first write), and no other thread touches chunk c of any element -- so h may be hin.
+// (no __restrict__ on h / hin: they may alias)
+__global__ __launch_bounds__(256) void resid_apply_kernel(const u16* hin, int64_t in_bs, const u16* __restrict__ r, u16* h, int64_t h_bs,
+                                                          int64_t n_batch, int64_t per_b8) {
+    for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < per_b8; c += (int64_t)gridDim.x * 256) {
+        float fi[8], fr[8], fo[8];
+        for (int64_t b = 0; b < n_batch; ++b) {
+            if (b == 0 || in_bs != 0) unpack8(*reinterpret_cast<const uint4*>(hin + b * in_bs + c * 8), fi);
+            unpack8(*reinterpret_cast<const uint4*>(r + (b * per_b8 + c) * 8), fr);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) fo[e] = fi[e] + fr[e];
+            *reinterpret_cast<uint4*>(h + b * h_bs + c * 8) = pack8(fo);
+        }
+    }
+}
+
+// out[0] = sum_j |a_j - b_j|, out[1] = sum_j |b_j|, every a_j and b_j widened to fp64 first.  ONE workgroup: thread t sums the terms
+// j = t, t + 256, .. in ascending order, then a binary tree over the 256 partial sums in LDS -- an order fixed by n alone.
+__global__ __launch_bounds__(256) void abs_diff_sums_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t n,
+                                                            double* __restrict__ out) {
+    __shared__ double sd[256], sb[256];
+    const int t = threadIdx.x;
+    double d = 0.0, m = 0.0;
+    for (int64_t j = t; j < n; j += 256) {
+        const double bj = (double)b[j];
+        d += fabs((double)a[j] - bj);
+        m += fabs(bj);
+    }
+    sd[t] = d;
+    sb[t] = m;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+            sd[t] += sd[t + s];
+            sb[t] += sb[t + s];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[0] = sd[0];
+        out[1] = sb[0];
+    }
+}
+
+// what the two residual calls share: shapes, strides, alignment (host only; the message names the value)
+static int resid_check(const char* who, int64_t n_batch, int64_t rows, int64_t D, int64_t bs0, const char* bs0_name, int64_t bs1,
+                       const char* bs1_name, const void* p0, const void* p1, const void* p2) {
+    auto fail = [&](const std::string& msg) {
+        scail_set_error(std::string(who) + ": " + msg);
+        return 1;
+    };
+    if (n_batch < 0 || n_batch > 64) return fail("n_batch must be 0..64, got " + std::to_string(n_batch));
+    if (rows < 0 || rows >= (1ll << 31)) return fail("rows must be 0 .. 2^31 - 1, got " + std::to_string(rows));
+    if (D < 8 || D % 8 != 0 || D >= (1 << 20)) return fail("D must be a multiple of 8 in 8 .. 2^20 - 8 (16-byte loads), got " + std::to_string(D));
+    if (bs0 < 0 || bs0 % 8 != 0) return fail(std::string(bs0_name) + " must be a non-negative multiple of 8 elements, got " + std::to_string(bs0));
+    if (bs1 < 0 || bs1 % 8 != 0) return fail(std::string(bs1_name) + " must be a non-negative multiple of 8 elements, got " + std::to_string(bs1));
+    if (n_batch == 0 || rows == 0) return 0;
+    if (p0 == nullptr || p1 == nullptr || p2 == nullptr) return fail("null pointer");
+    if (!aligned16(p0) || !aligned16(p1) || !aligned16(p2)) return fail("every base pointer must be 16-byte aligned");
+    return 0;
+}
+
+extern "C" int scail_resid_store(const scail_bf16* h_out, int64_t out_bs, const scail_bf16* h_in, int64_t in_bs, scail_bf16* r,
+                                 int64_t n_batch, int64_t rows, int64_t D, void* stream) {
+    if (int rc = resid_check("scail_resid_store", n_batch, rows, D, out_bs, "out_bs", in_bs, "in_bs", h_out, h_in, r)) return rc;
+    if (n_batch == 0 || rows == 0) return 0;
+    const int64_t per_b8 = rows * (D / 8), total8 = n_batch * per_b8;
+    const int64_t wgs = std::min<int64_t>((total8 + 255) / 256, RESID_MAX_WGS);
+    hipLaunchKernelGGL(resid_store_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, h_out, out_bs, h_in, in_bs, r, per_b8, total8);
+    return scail_check_launch("resid_store");
+}
+
+extern "C" int scail_resid_apply(const scail_bf16* h_in, int64_t in_bs, const scail_bf16* r, scail_bf16* h, int64_t h_bs,
+                                 int64_t n_batch, int64_t rows, int64_t D, void* stream) {
+    if (int rc = resid_check("scail_resid_apply", n_batch, rows, D, h_bs, "h_bs", in_bs, "in_bs", h_in, r, h)) return rc;
+    if (n_batch == 0 || rows == 0) return 0;
+    const int64_t span = rows * D, per_b8 = rows * (D / 8);
+    if (n_batch > 1 && h_bs < span) {
+        scail_set_error("scail_resid_apply: h_bs = " + std::to_string(h_bs) + " is smaller than one element's rows * D = " + std::to_string(span) +
+                        " (the output elements would overlap)");
+        return 1;
+    }
+    // h may BE h_in (element for element, or in_bs == 0 with h[0] == h_in); any other overlap of the two would let one thread's write
+    // reach another thread's read
+    const int64_t in_lo = (int64_t)reinterpret_cast<uintptr_t>(h_in), in_hi = in_lo + ((n_batch - 1) * in_bs + span) * 2;
+    const int64_t h_lo = (int64_t)reinterpret_cast<uintptr_t>(h), h_hi = h_lo + ((n_batch - 1) * h_bs + span) * 2;
+    if (in_lo < h_hi && h_lo < in_hi && !(h == h_in && (in_bs == 0 || in_bs == h_bs))) {
+        scail_set_error("scail_resid_apply: h overlaps h_in without being h_in (h - h_in = " + std::to_string((h_lo - in_lo) / 2) + " elements, in_bs " +
+                        std::to_string(in_bs) + ", h_bs " + std::to_string(h_bs) + "): in place means h == h_in with in_bs == 0 or in_bs == h_bs");
+        return 1;
+    }
+    const int64_t wgs = std::min<int64_t>((per_b8 + 255) / 256, RESID_MAX_WGS);
+    hipLaunchKernelGGL(resid_apply_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, h_in, in_bs, r, h, h_bs, n_batch, per_b8);
+    return scail_check_launch("resid_apply");
+}
+
+extern "C" int scail_abs_diff_sums(const float* a, const float* b, int64_t n, double* out, void* stream) {
+    if (n < 0 || n >= (1ll << 31)) {
+        scail_set_error("scail_abs_diff_sums: n must be 0 .. 2^31 - 1, got " + std::to_string(n));
+        return 1;
+    }
+    SCAIL_REQUIRE(out != nullptr && (reinterpret_cast<uintptr_t>(out) & 7) == 0, "out must be an 8-byte aligned device pointer");
+    SCAIL_REQUIRE(n == 0 || (a != nullptr && b != nullptr), "null pointer");
+    SCAIL_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 3) == 0, "a and b must be 4-byte aligned");
+    hipLaunchKernelGGL(abs_diff_sums_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a, b, n, out);
+    return scail_check_launch("abs_diff_sums");
+}
+
+// ================================================================================================
 // Small-sequence attention for the conditioning encoders (UMT5: 64 heads x 64, relative-position bias,
 // key padding mask, no scaling -- umt5.py:72-123; CLIP ViT-H: 16 heads x 80, scale 1/sqrt(80) --
 // clip.py:71-108).  Sequences are <= 512 tokens and the FLOPs are negligible (4 GFLOP per T5 layer), so

@@ -78,6 +78,7 @@ class CStep:
         L.call("scail_dit_create", C.byref(cfg), C.byref(w), C.byref(h))
         self._h = h
         self._ws = None
+        self._cache = None                               # ((B, T, H, W, device), buffer) of the step cache, once a FILL has run
         self._fp8_buf = None
         self._probe = None                               # (table, scratch) while the fp8 probe is on
         self.num_layers = net.num_layers
@@ -213,6 +214,89 @@ class CStep:
                C.byref(cc), ref.data_ptr(), pose.data_ptr(), n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), T, H, W,
                ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
         return x32
+
+    # ---- step cache (include/scail_dit.h "step cache") ----
+    def step_cache_bytes(self, B, T, H, W) -> int:
+        n = L.load().scail_dit_step_cache_bytes(self._h, B, T, H, W)
+        if n < 0:
+            raise L.ScailHipError(f"scail_dit_step_cache_bytes: bad shape (B {B}, T {T}, H {H}, W {W})")
+        return n
+
+    def _cache_for(self, B, T, H, W, device, fill: bool) -> torch.Tensor:
+        """The cache of a (B, T, H, W) evaluation.  A FILL gets a new one when the shape or the device changed; a REUSE needs the one a
+        FILL of that shape left.  Handed out by ``_ws_for`` like every other buffer the executor is given, but kept beside the
+        workspace: ``_ws_for`` is asked with no workspace in hand and the workspace is put back afterwards."""
+        key = (B, T, H, W, torch.device(device))
+        if self._cache is None or self._cache[0] != key:
+            if not fill:
+                raise L.ScailHipError(f"step cache: a 'reuse' evaluation of (B {B}, T {T}, H {H}, W {W}) needs a 'fill' evaluation of that shape first")
+            ws, self._ws = self._ws, None
+            try:
+                buf = self._ws_for(self.step_cache_bytes(B, T, H, W), device, f"scail_dit_step_cache_bytes (B {B}, T {T}, H {H}, W {W})")
+            finally:
+                self._ws = ws
+            self._cache = (key, buf)
+        return self._cache[1]
+
+    def step_cache_residual(self, B, T, H, W, D) -> torch.Tensor:
+        """r (B, Lnoise, D) bf16 as the last FILL of this shape left it: a view of offset 0 of the cache"""
+        assert self._cache is not None and self._cache[0][:4] == (B, T, H, W), "no cache of this shape"
+        n = B * T * (H // 2) * (W // 2) * D
+        return self._cache[1][:2 * n].view(torch.bfloat16).view(B, -1, D)
+
+    def step_cached(self, x32, t32, cond, ref, pose, cos, sin, mode: str, cfg_pair: bool = False, n_char: int = 1) -> torch.Tensor:
+        """``step`` in a cache mode (scail_dit_step_cached): "fill" = the full evaluation, which also leaves the blocks' residual on the
+        noise rows in the cache; "reuse" = patch embedding of the noise rows + that residual + the final layer (``cond`` may be None)."""
+        if mode not in L.CACHE_MODES:
+            raise L.ScailHipError(f"step_cached: mode must be one of {sorted(L.CACHE_MODES)}, got {mode!r}")
+        B, T, _, H, W = x32.shape
+        cache = self._cache_for(B, T, H, W, x32.device, mode == "fill")
+        ws = self._ws_for(self.workspace_bytes(B, T, H, W, n_char), x32.device, "scail_dit_chars_workspace_bytes")
+        cc = None if cond is None else _cond_struct(cond)
+        out = torch.empty(B, T, 16, H, W, device=x32.device, dtype=torch.float32)
+        L.call("scail_dit_step_cached", self._h, x32.data_ptr(), t32.data_ptr(), None if cc is None else C.byref(cc), ref.data_ptr(), ref.shape[0],
+               pose.data_ptr(), pose.shape[0], n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), out.data_ptr(), B, T, H, W,
+               self.CFG_PAIR if cfg_pair else 0, ws.data_ptr(), ws.numel(), L.CACHE_MODES[mode], cache.data_ptr(), cache.numel(),
+               torch.cuda.current_stream().cuda_stream)
+        return out
+
+    def sample_cached(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose, cos, sin, reuse, n_char: int = 1) -> torch.Tensor:
+        """``sample`` with a step cache (scail_dit_sample_cached): ``reuse`` = one 0 / 1 per step (sampler.plan_step_cache), 1 = that step
+        reuses the residual of the last computed step.  Still ONE call that only enqueues."""
+        _, T, _, H, W = x32.shape
+        ts, dsa, n = self._schedule(sigmas, x32.device)
+        reuse = [int(v) for v in reuse]
+        if len(reuse) != n:
+            raise L.ScailHipError(f"sample_cached: the reuse mask needs one entry per step ({n}), got {len(reuse)}")
+        if any(v < 0 or v > 255 for v in reuse):
+            raise L.ScailHipError(f"sample_cached: the reuse mask holds 0 / 1 entries, got {reuse}")
+        cache = self._cache_for(2, T, H, W, x32.device, True)
+        ws = self._ws_for(L.load().scail_dit_sample_chars_workspace_bytes(self._h, T, H, W, n_char), x32.device,
+                          f"scail_dit_sample_chars_workspace_bytes (T {T}, H {H}, W {W}, n_char {n_char})")
+        cc = _cond_struct(cond)
+        assert x32.is_contiguous() and x32.dtype == torch.float32 and ref.shape[0] == 1 and pose.shape[0] == 1
+        L.call("scail_dit_sample_cached", self._h, x32.data_ptr(), ts.data_ptr(), C.cast(dsa, C.c_void_p), n, float(cfg_scale),
+               C.byref(cc), ref.data_ptr(), pose.data_ptr(), n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), T, H, W,
+               ws.data_ptr(), ws.numel(), (C.c_uint8 * max(n, 1))(*reuse), cache.data_ptr(), cache.numel(), torch.cuda.current_stream().cuda_stream)
+        return x32
+
+    def time_distances(self, timesteps, signal: str = "time") -> torch.Tensor:
+        """scail_dit_time_distances: for the device fp32 ``timesteps`` (n,) (= 1000 sigma_i) the (n, 2) fp64 CPU table of
+        (sum |v_i - v_{i-1}|, sum |v_{i-1}|) between consecutive steps' time embeddings ("time") or their AdaLN projections ("modulation");
+        row 0 is (0, 0).  One host synchronisation (the copy of the table)."""
+        if signal not in L.CACHE_SIGNALS:
+            raise L.ScailHipError(f"time_distances: signal must be one of {sorted(L.CACHE_SIGNALS)}, got {signal!r}")
+        sg = L.CACHE_SIGNALS[signal]
+        assert timesteps.is_cuda and timesteps.dtype == torch.float32 and timesteps.dim() == 1 and timesteps.is_contiguous()
+        n, dev = timesteps.numel(), timesteps.device
+        need = L.load().scail_dit_time_distances_bytes(self._h, sg)
+        if need < 0:
+            raise L.ScailHipError(f"scail_dit_time_distances_bytes: bad signal {sg}")
+        scratch = torch.empty(need, device=dev, dtype=torch.uint8)
+        out = torch.empty(max(n, 1), 2, device=dev, dtype=torch.float64)
+        L.call("scail_dit_time_distances", self._h, timesteps.data_ptr(), n, sg, out.data_ptr(), scratch.data_ptr(), scratch.numel(),
+               torch.cuda.current_stream(dev).cuda_stream)
+        return out[:n].cpu()
 
     def sample_tiled_workspace_bytes(self, T, Tt, H, W) -> int:
         n = L.load().scail_dit_sample_tiled_workspace_bytes(self._h, T, Tt, H, W)

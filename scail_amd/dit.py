@@ -540,7 +540,21 @@ class DiffusionTransformer(nn.Module):
                 raise ValueError("cfg_pair was passed, but x[0] != x[1] or timesteps[0] != timesteps[1]: the flag states that the batch is ONE latent and "
                                  "ONE sigma twice (scail_amd.sampler.VanillaCFG.prepare_inputs); drop the key for any other batch")
             self._cfg_pair_checked = True
-        return self._run(x32, t32, ctx, ref, pose, clip, H_shift, W_shift, cond_key, cfg_pair=cfg_pair)
+        return self._run(x32, t32, ctx, ref, pose, clip, H_shift, W_shift, cond_key, cfg_pair=cfg_pair, step_cache=kwargs.get("step_cache", None))
+
+    def _step_cache_ok(self, what="step_cache"):
+        """The step cache lives in the one-call C executor on one rank (include/scail_dit.h "step cache": no *_cached form of the
+        sequence-parallel calls or of the per-block seam): everything else is refused by name"""
+        if not self.executor_ok(whole_loop=True) or self._c_blocks:
+            raise NotImplementedError(f"{what} runs in the C executor's one-call step on a single rank only: not on sequence-parallel ranks, not "
+                                      "with SCAIL_C_STEP=0, _tap, kernel_timer or the per-block seam")
+
+    def time_distances(self, timesteps, signal="time"):
+        """The decision signal of the step cache (CStep.time_distances): (n, 2) fp64 CPU table for the host schedule ``timesteps`` (n,)
+        fp32 (= 1000 sigma_i); feed it to sampler.plan_step_cache."""
+        self._step_cache_ok("step_cache (time_distances)")
+        dev = self.prepare()["patch_w"].device
+        return self._executor().time_distances(timesteps.float().to(dev).contiguous(), signal)
 
     def executor_ok(self, whole_loop: bool = False) -> bool:
         """Whether the C executor (include/scail_dit.h) may run a request: C step on, no tap, no kernel timer (both instrument the per-op
@@ -598,13 +612,18 @@ class DiffusionTransformer(nn.Module):
         cos, sin = self._rope(T_rope, x32.shape[3] // 2, x32.shape[4] // 2, 0, 0, dev, n_char)
         return self._executor(), cond, cos, sin, x32.float().contiguous().clone()
 
-    def sample_c(self, x32, sigmas, cfg_scale, ctx, ref, pose, clip, cond_key=None):
+    def sample_c(self, x32, sigmas, cfg_scale, ctx, ref, pose, clip, cond_key=None, reuse=None):
         """The whole RFSampler Euler loop as ONE C call (scail_dit_sample_chars, include/scail_dit.h): x32 (1,T,16,H,W) fp32,
         ctx (2, Lt, text_dim) = [uncond; cond], ref (1,C,16,H,W), pose (1,C*T,16,H/2,W/2) for C >= 1 characters (C = ref.shape[1]),
-        clip (1,Lc,1280).  Single rank."""
+        clip (1,Lc,1280).  Single rank.  ``reuse``: None, or the step cache's plan -- one 0 / 1 per step, 1 = reuse the block residual
+        of the last computed step (scail_dit_sample_cached)."""
         T, n_char, dev = x32.shape[1], ref.shape[1], x32.device
         self._check_chars(n_char, T, pose.shape[1])
+        if reuse is not None:
+            self._step_cache_ok()
         ex, cond, cos, sin, x = self._sample_prelude(x32, ctx, clip, cond_key, T, n_char)
+        if reuse is not None:
+            return ex.sample_cached(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, reuse, n_char=n_char)
         return ex.sample(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, n_char=n_char)
 
     def sample_tiled_c(self, x32, sigmas, cfg_scale, ctx, ref, pose_tiles, clip, tile_indices, tile_w, inv_wsum, cond_key=None):
@@ -620,7 +639,9 @@ class DiffusionTransformer(nn.Module):
         ex, cond, cos, sin, x = self._sample_prelude(x32, ctx, clip, cond_key, Tt, 1)
         return ex.sample_tiled(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose_tiles, dev), tile_indices, tile_w, inv_wsum, cos, sin)
 
-    def _run(self, x32, t32, ctx, ref, pose, clip, H_shift=0, W_shift=0, cond_key=None, cfg_pair=False):
+    def _run(self, x32, t32, ctx, ref, pose, clip, H_shift=0, W_shift=0, cond_key=None, cfg_pair=False, step_cache=None):
+        if step_cache is not None:
+            self._step_cache_ok()
         W = self.prepare()
         dev = x32.device
         B, T, _, H, Wd = x32.shape
@@ -649,6 +670,9 @@ class DiffusionTransformer(nn.Module):
             # the whole evaluation as ONE call into the library (include/scail_dit.h), for any number of characters; same kernels, same
             # order.  A sequence-parallel rank runs the same executor: only the collectives of the per-layer exchange come back to the
             # host (xch)
+            if step_cache is not None:
+                # "fill" | "reuse" (include/scail_dit.h "step cache"; _step_cache_ok above has refused every other route)
+                return ex.step_cached(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, step_cache, cfg_pair=cfg_pair, n_char=n_char)
             if sp is None:
                 return ex.step(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, cfg_pair=cfg_pair, n_char=n_char)
             return ex.step_sp(x32, t32, cond, ref.contiguous(), pose.contiguous(), cos, sin, xch, cfg_pair=cfg_pair, n_char=n_char)

@@ -58,10 +58,16 @@ class SATVideoDiffusionEngine(nn.Module):
     @torch.no_grad()
     def sample(self, cond: Dict, uc: Optional[Dict] = None, batch_size: int = 1, shape: Union[None, Tuple, List] = None,
                prefix=None, concat_images=None, ofs=None, fps=None, tile_indices=None,
-               generator: Optional[torch.Generator] = None, num_steps: Optional[int] = None, fused: bool = True, **kwargs):
+               generator: Optional[torch.Generator] = None, num_steps: Optional[int] = None, fused: bool = True, step_cache=None, **kwargs):
         """diffusion_video.py:456-587.  shape = (T, C, H, W).  Noise is drawn in fp32 on the host RNG
         stream of ``generator`` like ``torch.randn(batch, *shape)`` (:470), broadcast inside the
-        sequence-parallel group (:486-493) and H/W-chunked (:495-552); result gathered to SP rank 0 (:571-585)."""
+        sequence-parallel group (:486-493) and H/W-chunked (:495-552); result gathered to SP rank 0 (:571-585).
+        ``step_cache``: None, or the step-cache option of RFSampler.sample_hip (an extension, opt-in; fused HIP network, one rank, no tiles)."""
+        if step_cache is not None:
+            if not (fused and isinstance(self.network, DiffusionTransformer)):
+                raise NotImplementedError("step_cache needs the fused path of the HIP network (RFSampler.sample_hip)")
+            if self.sp is not None and self.sp.size > 1:
+                raise NotImplementedError("step_cache runs on a single rank only: the sequence-parallel calls have no cached form")
         randn = torch.randn(batch_size, *shape, generator=generator).to(torch.float32).to(self.device)
         if prefix is not None:
             randn = torch.cat([prefix, randn[:, prefix.shape[1]:]], dim=1)
@@ -84,6 +90,8 @@ class SATVideoDiffusionEngine(nn.Module):
         extra = {} if tile_indices is None else {"tile_indices": tile_indices}     # RFSamplerLong, :564-569
         if tile_indices is not None and not isinstance(self.sampler, S.RFSamplerLong):
             raise TypeError("tile_indices needs sampler_config.target = RFSamplerLong")
+        if step_cache is not None:
+            extra["step_cache"] = step_cache
         if fused and isinstance(self.network, DiffusionTransformer):
             samples = self.sampler.sample_hip(self.network, randn, cond, uc, num_steps=num_steps, chunk_dim=chunk_dim, **extra)
         else:

@@ -76,6 +76,10 @@ SIGNATURES = {
     "scail_quant_fp8_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _p],
     "scail_gemm_fp8": [_p, _i64, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _i64, _p, _i64, _i64, _p],
     "scail_rel_err_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _p],
+    # the row kernels of the step cache
+    "scail_resid_store": [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p],
+    "scail_resid_apply": [_p, _i64, _p, _p, _i64, _i64, _i64, _i64, _p],
+    "scail_abs_diff_sums": [_p, _p, _i64, _p, _p],
     # MX block scaling: E8M0 bytes [rows, cols / 32] beside the e4m3 codes
     "scail_quant_mxfp8_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p],
     "scail_gemm_mxfp8": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _i64, _p, _i64, _i64, _p],
@@ -115,6 +119,13 @@ SIGNATURES = {
     "scail_dit_fp8_select_layers": [_p, _p],
     "scail_dit_fp8_probe_bytes": [_p, _i64, _i64],
     "scail_dit_fp8_probe": [_p, _p, _p, _i64],
+    # the step cache: the _chars step / sampler + (mode | host uint8 reuse mask), cache, cache bytes; the time-embedding distances
+    "scail_dit_step_cache_bytes": [_p, _i64, _i64, _i64, _i64],
+    "scail_dit_step_cached": [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, C.c_uint32, _p, _i64,
+                              _i, _p, _i64, _p],
+    "scail_dit_sample_cached": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _p],
+    "scail_dit_time_distances_bytes": [_p, _i],
+    "scail_dit_time_distances": [_p, _p, _i64, _i, _p, _p, _i64, _p],
     # include/scail_vae.h (scail_amd/cvae.py builds the structs)
     "scail_vae_create": [_p, _p],
     "scail_vae_destroy": [_p],
@@ -147,6 +158,9 @@ FP8_GEMMS = {"qkv": 1, "o": 2, "cq": 4, "co": 8, "w1": 16, "w2": 32}
 FP8_ALL = 63
 # include/scail_dit.h SCAIL_DIT_FP8_SCALE_*: one fp32 scale per row, or OCP MX (one E8M0 scale per block of 32 along K)
 FP8_SCALINGS = {"row": 0, "mx": 1}
+# include/scail_dit.h SCAIL_DIT_CACHE_*: the modes of scail_dit_step_cached; the signals of scail_dit_time_distances
+CACHE_MODES = {"fill": 1, "reuse": 2}
+CACHE_SIGNALS = {"time": 0, "modulation": 1}
 # include/scail_hip.h scail_resize_crop_aa: source layouts, and the largest in / out per axis its tap budget covers
 SRC_U8_NHWC, SRC_F32_NCHW = 0, 1
 RESIZE_MAX_SCALE = 16
@@ -158,7 +172,9 @@ ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- sc
                          # scail_row_kernel_name_for, the attention queries scail_flash_attn_kernel_name_for /
                          # scail_cross_attn2_kernel_name_for, and the fp8 probe and per-layer selection, scail_rel_err_rows /
                          # scail_dit_fp8_select_layers / scail_dit_fp8_probe / scail_dit_fp8_probe_bytes, and MX block scaling,
-                         # scail_quant_mxfp8_rows / scail_gemm_mxfp8 / scail_dit_fp8_weight_bytes_scaled / scail_dit_enable_fp8_scaled)
+                         # scail_quant_mxfp8_rows / scail_gemm_mxfp8 / scail_dit_fp8_weight_bytes_scaled / scail_dit_enable_fp8_scaled,
+                         # and the step cache, scail_resid_store / scail_resid_apply / scail_abs_diff_sums / scail_dit_step_cache_bytes /
+                         # scail_dit_step_cached / scail_dit_sample_cached / scail_dit_time_distances / scail_dit_time_distances_bytes)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);

@@ -112,6 +112,57 @@ def rel_err_rows(a, b, acc=None):
     return acc
 
 
+def _batch_rows(t: torch.Tensor, name: str):
+    """(batch stride in elements) of a bf16 (B, rows, D) operand of the residual kernels: rows D apart, last dim contiguous; a batch
+    stride of 0 (``expand``) is one element for every b"""
+    _chk(t, bf16, name)
+    if t.dim() != 3 or t.stride(2) != 1 or (t.shape[1] > 1 and t.stride(1) != t.shape[2]):
+        raise L.ScailHipError(f"{name}: need (B, rows, D) with rows D apart, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t.stride(0) if t.shape[0] > 1 else 0
+
+
+def resid_store(h_out, h_in, out=None):
+    """r = bf16(h_out.float() - h_in.float()) (include/scail_hip.h scail_resid_store): h_out, h_in (B, rows, D) bf16 views with rows D apart
+    (row windows of larger matrices are fine; h_in may be ``expand``ed from one element); r dense (B, rows, D)."""
+    out_bs, in_bs = _batch_rows(h_out, "resid_store.h_out"), _batch_rows(h_in, "resid_store.h_in")
+    B, R, D = h_out.shape
+    assert h_in.shape == h_out.shape
+    if out is None:
+        out = torch.empty(B, R, D, device=h_out.device, dtype=bf16)
+    _chk(out, bf16, "resid_store.out")
+    assert out.shape == h_out.shape and out.is_contiguous()
+    L.call("scail_resid_store", h_out.data_ptr(), out_bs, h_in.data_ptr(), in_bs, out.data_ptr(), B, R, D, _stream())
+    return out
+
+
+def resid_apply(h_in, r, out=None):
+    """h = bf16(h_in.float() + r.float()) (scail_resid_apply): h_in as for resid_store, r dense (B, rows, D); ``out`` (B, rows, D) with rows D
+    apart, which may be h_in itself -- or, for an ``expand``ed h_in, a tensor whose element 0 is h_in's one element."""
+    in_bs = _batch_rows(h_in, "resid_apply.h_in")
+    B, R, D = r.shape
+    _chk(r, bf16, "resid_apply.r")
+    assert h_in.shape == r.shape and r.is_contiguous()
+    if out is None:
+        out = torch.empty(B, R, D, device=r.device, dtype=bf16)
+    h_bs = _batch_rows(out, "resid_apply.out")
+    assert out.shape == r.shape
+    L.call("scail_resid_apply", h_in.data_ptr(), in_bs, r.data_ptr(), out.data_ptr(), h_bs if B > 1 else R * D, B, R, D, _stream())
+    return out
+
+
+def abs_diff_sums(a, b, out=None):
+    """(sum |a - b|, sum |b|) of two fp32 vectors as a device fp64 (2,) tensor, summed in fp64 in an order fixed by the length
+    (scail_abs_diff_sums)."""
+    _chk(a, f32, "abs_diff_sums.a"); _chk(b, f32, "abs_diff_sums.b")
+    assert a.is_contiguous() and b.is_contiguous() and a.numel() == b.numel()
+    if out is None:
+        out = torch.empty(2, device=a.device, dtype=torch.float64)
+    _chk(out, torch.float64, "abs_diff_sums.out")
+    assert out.numel() == 2 and out.is_contiguous()
+    L.call("scail_abs_diff_sums", a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(), _stream())
+    return out
+
+
 def gemm_fp8(xq, sx, wq, sw, bias=None, out=None, epilogue=L.EPI_BIAS, resid=None, gate=None, rows_per_batch=0):
     """y = epilogue((xq @ wq.T) * sx[:, None] * sw[None, :] + bias) (include/scail_hip.h scail_gemm_fp8).  xq (M, K) / wq (N, K) e4m3 codes
     (uint8, from quant_fp8_rows), sx (M,) / sw (N,) fp32; bias, out, resid, gate as for gemm()."""

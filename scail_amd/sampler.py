@@ -141,6 +141,52 @@ def _executor_takes_loop(network) -> bool:
     return getattr(network, "executor_ok", lambda **kw: False)(whole_loop=True)
 
 
+def plan_step_cache(dist, threshold, coefficients=(1.0, 0.0), keep_first=1, keep_last=1):
+    """The step cache's plan (include/scail_dit.h "step cache"): one 0 (compute) / 1 (reuse the block residual of the last computed step)
+    per sampler step, from the table ``dist`` of DiffusionTransformer.time_distances -- n rows (sum |v_i - v_{i-1}|, sum |v_{i-1}|).
+    Pure host fp64; needs no device.
+
+      d_i = dist[i][0] / dist[i][1]                       (a zero denominator: step i computes)
+      acc += polynomial(d_i)                              (``coefficients`` highest degree first, Horner; (1, 0) is the identity)
+      step i computes and resets acc when i < keep_first, i >= n - keep_last, or acc >= threshold; otherwise it reuses.
+
+    Step 0 always computes (keep_first >= 1): it has nothing to reuse.  threshold 0 gives all zeros.  Example: d_i = 0.125 for
+    i = 1..5, threshold 0.3, n = 6 -> [0, 1, 1, 0, 1, 0]."""
+    rows = [(float(r[0]), float(r[1])) for r in dist]
+    n = len(rows)
+    threshold = float(threshold)
+    coefficients = [float(c) for c in coefficients]
+    if not threshold >= 0.0:
+        raise ValueError(f"plan_step_cache: threshold must be >= 0, got {threshold}")
+    if not coefficients or not all(np.isfinite(c) for c in coefficients):
+        raise ValueError(f"plan_step_cache: coefficients must be a non-empty list of finite numbers, got {coefficients}")
+    if int(keep_first) != keep_first or keep_first < 1:
+        raise ValueError(f"plan_step_cache: keep_first must be an integer >= 1 (step 0 has nothing to reuse), got {keep_first}")
+    if int(keep_last) != keep_last or keep_last < 0:
+        raise ValueError(f"plan_step_cache: keep_last must be an integer >= 0, got {keep_last}")
+    if any(not (np.isfinite(a) and np.isfinite(b)) or a < 0 or b < 0 for a, b in rows):
+        raise ValueError("plan_step_cache: dist must hold finite, non-negative sums")
+    mask, acc = [], 0.0
+    for i, (num, den) in enumerate(rows):
+        if i < keep_first or i >= n - keep_last or den == 0.0:
+            mask.append(0)
+            acc = 0.0
+            continue
+        p = 0.0
+        for c in coefficients:
+            p = p * (num / den) + c
+        acc += p
+        if acc < threshold:
+            mask.append(1)
+        else:
+            mask.append(0)
+            acc = 0.0
+    return mask
+
+
+STEP_CACHE_KEYS = ("threshold", "coefficients", "keep_first", "keep_last", "signal", "mask")
+
+
 class RFSampler:
     """sampling.py:920-982.  Only the shipped branch (hunyuan_schedule) is implemented.
 
@@ -181,24 +227,59 @@ class RFSampler:
         return x
 
     # ---- fused path for the HIP network (same arithmetic, fewer passes / no host syncs) ----
+    def step_cache_plan(self, network, sig, step_cache) -> list:
+        """The 0 / 1 plan of a ``step_cache`` option (sample_hip) for the host schedule ``sig``: its explicit ``mask``, or
+        plan_step_cache on the network's time distances (signal "time" | "modulation"; one small device run and one synchronisation,
+        before the loop).  The plan depends on the schedule and the weights alone, never on the latent."""
+        if not isinstance(step_cache, dict) or not step_cache or any(k not in STEP_CACHE_KEYS for k in step_cache):
+            raise ValueError(f"step_cache must be None or a dict with keys out of {STEP_CACHE_KEYS}, got {step_cache!r}")
+        n = len(sig) - 1
+        if step_cache.get("mask") is not None:
+            if len(step_cache) != 1:
+                raise ValueError("step_cache: an explicit 'mask' stands alone (the other keys make a plan from a threshold)")
+            mask = [int(v) for v in step_cache["mask"]]
+            if len(mask) != n or any(v not in (0, 1) for v in mask) or (n > 0 and mask[0] != 0):
+                raise ValueError(f"step_cache: 'mask' needs {n} entries of 0 / 1 and mask[0] == 0 (the first step has nothing to reuse), got {mask}")
+            return mask
+        if "threshold" not in step_cache:
+            raise ValueError("step_cache needs a 'threshold' (or an explicit 'mask'); no default is recommended: nothing has been measured on real weights")
+        dist = network.time_distances((sig[:-1] * 1000.0), step_cache.get("signal", "time"))
+        return plan_step_cache(dist, step_cache["threshold"], step_cache.get("coefficients", (1.0, 0.0)), step_cache.get("keep_first", 1),
+                               step_cache.get("keep_last", 1))
+
     def sample_hip(self, network, x, cond: Dict, uc: Dict, num_steps=None, scale=None, chunk_dim=None,
-                   step_callback=None):
+                   step_callback=None, step_cache=None):
         """x (1,T,16,H,W) fp32 on the GPU; cond/uc as the CLI builds them (sample_video.py:455-470).
-        One step = one batch-2 DiT forward (uncond, cond) + scail_cfg_euler."""
+        One step = one batch-2 DiT forward (uncond, cond) + scail_cfg_euler.
+        ``step_cache`` (opt-in, an extension; None = this method as it was): a dict with ``threshold`` and optionally ``coefficients``,
+        ``keep_first``, ``keep_last``, ``signal`` (plan_step_cache / step_cache_plan), or an explicit ``mask`` of one 0 / 1 per step.  A step
+        planned 1 skips the blocks and adds the block residual of the last computed step to its own embedded tokens
+        (include/scail_dit.h "step cache").  Both routes below take the plan and give the same bits.  ``self.last_step_cache_plan`` keeps it."""
         sig = self.sigmas(num_steps)                     # host fp32, like the reference
         cfg = float(self.guider.scale if scale is None else scale)
         ctx = torch.cat((uc["crossattn"], cond["crossattn"]), 0)
         shared = {k: v for k, v in cond.items() if k != "crossattn"}
+        plan = None
+        if step_cache is not None:
+            if chunk_dim is not None or not _executor_takes_loop(network):
+                raise NotImplementedError("step_cache runs in the C executor on a single rank only: not on sequence-parallel ranks (chunk_dim), not "
+                                          "with SCAIL_C_STEP=0, _tap or kernel_timer")
+            plan = self.last_step_cache_plan = self.step_cache_plan(network, sig, step_cache)
         if (_executor_takes_loop(network) and step_callback is None and chunk_dim is None
                 and shared["ref_concat"].shape[0] == 1 and shared["concat_smpl_render"].shape[0] == 1):
             # the whole loop enqueued by ONE call into the library (scail_dit_sample_chars; any number of reference frames / pose
             # streams); same kernels, same order
+            if plan is not None:
+                return network.sample_c(x, sig, cfg, ctx, shared["ref_concat"], shared["concat_smpl_render"],
+                                        shared["image_clip_features"], cond_key=("sample_hip", id(cond)), reuse=plan)
             return network.sample_c(x, sig, cfg, ctx, shared["ref_concat"], shared["concat_smpl_render"],
                                     shared["image_clip_features"], cond_key=("sample_hip", id(cond)))
         x = x.float().contiguous().clone()
         for i in range(len(sig) - 1):
             xin = torch.cat([x, x], 0)
             t = (sig[i] * 1000.0).repeat(2).to(x.device)                 # c_noise = 1000 sigma (RFScaling)
+            if plan is not None:
+                shared["step_cache"] = "reuse" if plan[i] else "fill"
             v = network.forward_f32(xin, t, ctx, None, cond_key=("sample_hip", id(cond)), chunk_dim=chunk_dim, **shared)
             ops.cfg_euler_(x, v, cfg, float(sig[i + 1] - sig[i]))
             if step_callback is not None:
@@ -291,9 +372,12 @@ class RFSamplerLong(RFSampler):
         return idxs, tile_w, 1.0 / wsum
 
     def sample_hip(self, network, x, cond: Dict, uc: Dict, num_steps=None, scale=None, chunk_dim=None,
-                   step_callback=None, tile_indices=None):
+                   step_callback=None, tile_indices=None, step_cache=None):
         """Fused path for the HIP network: per step and tile one batch-2 DiT forward (fp32 out); the text / CLIP
         conditioning (step- AND tile-invariant) is computed once per request."""
+        if step_cache is not None:
+            raise NotImplementedError("step_cache is not combined with temporal tiles (RFSamplerLong): the tiled loop has no cached form "
+                                      "(include/scail_dit.h \"step cache\", out of scope)")
         self._check(tile_indices)
         n = len(tile_indices)
         sig = self.sigmas(num_steps)
