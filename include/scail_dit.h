@@ -275,6 +275,19 @@ int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int64_t bytes,
 #define SCAIL_DIT_FP8_SCALE_MX 1
 int64_t scail_dit_fp8_weight_bytes_scaled(const scail_dit* h, uint32_t which, int scaling);
 int scail_dit_enable_fp8_scaled(scail_dit* h, uint32_t which, int scaling, void* buf, int64_t bytes, void* stream);
+/*
+ * 6-bit per-token GEMMs (opt-in): the selected GEMMs run as scail_quant_mxfp6_rows + scail_gemm_mxfp6 (include/scail_hip.h: packed OCP
+ * e2m3 codes with one E8M0 scale per aligned block of 32 along K, for activations and weights).  `which` takes the SCAIL_DIT_FP8_* bits.
+ * A handle holds ONE quantised form: scail_dit_enable_fp6 replaces an fp8 form and scail_dit_enable_fp8[_scaled] replaces fp6; which == 0
+ * or buf == NULL in any of them returns the handle to bf16.  The caller's buffer holds, per layer and selected GEMM in bit order, the
+ * packed codes [N, 3 K / 4 bytes] then the scale bytes [N, K / 32], each 256-byte aligned (scail_dit_fp6_weight_bytes; -1 for a null
+ * handle or an unknown bit); the block scratch holds rows x 3/4 (widest quantised K) code bytes and rows x (that K) / 32 scale bytes,
+ * and every workspace query answers for the form in force.  Blocks lie inside a row: the row independence, SCAIL_DIT_CFG_PAIR and the
+ * last-layer pruning hold.  scail_dit_fp8_select_layers and scail_dit_fp8_probe act on whichever quantised form is enabled; the
+ * sequence-parallel calls refuse an fp6 handle as they refuse fp8.  This is not a third `scaling` of scail_dit_enable_fp8_scaled.
+ */
+int64_t scail_dit_fp6_weight_bytes(const scail_dit* h, uint32_t which);
+int scail_dit_enable_fp6(scail_dit* h, uint32_t which, void* buf, int64_t bytes, void* stream);
 
 /*
  * Per-layer fp8 selection and the on-device GEMM error probe (both opt-in, both on top of scail_dit_enable_fp8).

@@ -46,7 +46,8 @@ const char* scail_last_error(void);
  * scail_dit_fp8_probe / scail_dit_fp8_probe_bytes, and for MX block scaling of the fp8 GEMMs, scail_quant_mxfp8_rows / scail_gemm_mxfp8 and
  * scail_dit.h's scail_dit_fp8_weight_bytes_scaled / scail_dit_enable_fp8_scaled, and for the step cache, scail_resid_store /
  * scail_resid_apply / scail_abs_diff_sums and scail_dit.h's scail_dit_step_cache_bytes / scail_dit_step_cached / scail_dit_sample_cached /
- * scail_dit_time_distances / scail_dit_time_distances_bytes.) */
+ * scail_dit_time_distances / scail_dit_time_distances_bytes, and for the 6-bit GEMMs, scail_quant_mxfp6_rows / scail_gemm_mxfp6 and
+ * scail_dit.h's scail_dit_fp6_weight_bytes / scail_dit_enable_fp6.) */
 int scail_abi_version(void);
 
 /* ---- epilogues of scail_gemm_bf16 ---------------------------------------------------------- */
@@ -675,6 +676,35 @@ int scail_gemm_fp8(const uint8_t* x, int64_t lda, const float* sx, const uint8_t
 int scail_quant_mxfp8_rows(const scail_bf16* x, int64_t ldx, uint8_t* q, int64_t ldq, uint8_t* e, int64_t lde, int64_t rows, int64_t cols,
                            void* stream);
 int scail_gemm_mxfp8(const uint8_t* x, int64_t lda, const uint8_t* ex, int64_t ldex, const uint8_t* w, const uint8_t* ew, const float* bias,
+                     scail_bf16* y, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
+                     const scail_bf16* resid, int64_t ldr, const float* gate, int64_t gate_stride,
+                     int64_t rows_per_batch, void* stream);
+
+/* ---- the same GEMMs on 6-bit operands (OCP MXFP6 e2m3: packed 6-bit codes + one E8M0 byte per aligned block of 32 along K) -----
+ * Format: 1 sign, 2 exponent (bias 1), 3 mantissa bits, code = sign << 5 | exp << 3 | man; no infinity, no NaN.  Magnitudes: 0,
+ *   0.125 .. 0.875 (exp 0, subnormal, man / 8), 1 .. 1.875 by 0.125, 2 .. 3.75 by 0.25, 4 .. 7.5 by 0.5.
+ * Packing: a block of 32 codes is 24 bytes; code j of the block occupies bits [6 j, 6 j + 6) of the block's little-endian 192-bit
+ *   string (bit i of the string = bit i % 8 of byte i / 8).  A row of K elements is 3 K / 4 bytes, block b at byte 24 b; leading
+ *   dimensions of packed matrices are in BYTES.  This is also the order in which the MFMA reads a lane's 6 operand registers.
+ * scail_quant_mxfp6_rows: q (packed codes, row stride ldq bytes) and e[r, c / 32] (uint8 E8M0, row stride lde) from bf16 x[r, c] (row
+ *   stride ldx).  Per aligned block of 32 columns, bit-exact:
+ *     amax = max |x| over the block's non-NaN elements;
+ *     amax == 0 (-0 included, or every element NaN): byte 127 and 32 codes 0x00;
+ *     else s = the smallest integer with amax * 2^-s <= 7.5, clamped to >= -127: with amax = m * 2^E, 1 <= m < 2, s = E - 2 if
+ *       m <= 1.875, else E - 1;  byte = s + 127 (at most 253);  q = e2m3_rne(clamp(x * 2^-s, -7.5, 7.5)), ties to even.
+ *   The multiplication by a power of two is exact in fp32 and the clamp never binds for finite input.  A -0 element, or one that
+ *   rounds to zero, keeps its sign bit (code 0x20) in a non-zero block.  Non-finite input: an infinity counts as 2^128 in the amax
+ *   (byte 253: the block's finite elements keep their exact scaled values, nearly all rounding to zero) and becomes +-7.5 (0x1f / 0x3f);
+ *   a NaN is left out of the amax and becomes code 0x00 -- the format has no code for it, and a zero adds nothing to a product.
+ *   The row is read once.  cols % 32 == 0, ldx % 8 == 0, ldq >= 3 cols / 4 and ldq % 4 == 0, lde >= cols / 32; x 16-byte, q 4-byte aligned.
+ * scail_gemm_mxfp6: y[M,N] = epilogue(sum_b 2^(ex[m,b] + ew[n,b] - 254) * sum_{k in b} xq[m,k] wq[n,k] + bias[n]) on the packed codes,
+ *   v_mfma_scale_f32_32x32x64_f8f6f4 with 6-bit operands.  x rows are lda BYTES apart (lda >= 3 K / 4, lda % 16 == 0), W rows 3 K / 4
+ *   bytes; ex, ew, epilogues, tile mapping, alignment and shape limits (M >= 1, N % 128 == 0, K % 128 == 0) as scail_gemm_mxfp8.  An
+ *   output row depends on its own input row alone.  Other shapes are refused before any launch.
+ */
+int scail_quant_mxfp6_rows(const scail_bf16* x, int64_t ldx, uint8_t* q, int64_t ldq, uint8_t* e, int64_t lde, int64_t rows, int64_t cols,
+                           void* stream);
+int scail_gemm_mxfp6(const uint8_t* x, int64_t lda, const uint8_t* ex, int64_t ldex, const uint8_t* w, const uint8_t* ew, const float* bias,
                      scail_bf16* y, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
                      const scail_bf16* resid, int64_t ldr, const float* gate, int64_t gate_stride,
                      int64_t rows_per_batch, void* stream);

@@ -231,13 +231,13 @@ def build_engine(cfg, load=None, device="cuda"):
 
 
 def fp8_max_error_arg(value, gemm_precision):
-    """``--fp8-max-error`` checked against the network's GEMM precision: a number >= 0 (inf allowed), and only with fp8 GEMMs."""
+    """``--fp8-max-error`` checked against the network's GEMM precision: a number >= 0 (inf allowed), and only with quantised (fp8 or fp6) GEMMs."""
     if value is None:
         return None
     value = float(value)
     if not value >= 0.0:
         raise ValueError(f"--fp8-max-error must be a number >= 0, got {value}")
-    if gemm_precision != "fp8":
+    if gemm_precision not in lib.GEMM_PRECISIONS:
         raise ValueError("--fp8-max-error needs --gemm-precision fp8 (or gemm_precision: fp8 in the network's yaml): it chooses which fp8 GEMMs to keep")
     return value
 
@@ -295,7 +295,9 @@ def format_fp8_table(cal, max_rel_err):
     column per GEMM, then the (layer, GEMM) pairs left in bf16."""
     names = list(lib.FP8_GEMMS)
     rel, masks = cal["rel_err"], cal["masks"]
-    out = [f"fp8 probe ({cal.get('scaling', 'row')} scaling): relative error of each fp8 GEMM against its bf16 twin (first evaluation), threshold {max_rel_err:g}",
+    head = "fp6 probe (MXFP6 e2m3)" if cal.get("precision", "fp8") == "fp6" else f"fp8 probe ({cal.get('scaling', 'row')} scaling)"
+    kind = cal.get("precision", "fp8")
+    out = [f"{head}: relative error of each {kind} GEMM against its bf16 twin (first evaluation), threshold {max_rel_err:g}",
            "layer " + " ".join(f"{n:>8}" for n in names)]
     for i in range(rel.shape[0]):
         out.append(f"{i:5d} " + " ".join(f"{float(rel[i, g]):8.2e}" for g in range(len(names))))
@@ -431,9 +433,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--request", action="append", default=[], help="'<prompt>@@<example_dir>' (the reference's cli input line); repeatable")
     ap.add_argument("--input-file", default=None, help="text file of request lines (the reference's --input-type txt)")
     ap.add_argument("--output-dir", default="outputs", help="results of --request / --input-file go to <output-dir>/<example>/")
-    ap.add_argument("--gemm-precision", choices=("bf16", "fp8"), default=None,
+    ap.add_argument("--gemm-precision", choices=("bf16",) + lib.GEMM_PRECISIONS, default=None,
                     help="precision of the six per-token GEMMs of every block (default: the config's, bf16); fp8 = e4m3 with per-token / "
-                         "per-channel scales, single GPU")
+                         "per-channel scales, single GPU; fp6 = OCP MXFP6 e2m3, 6-bit codes with one power-of-two scale per block of 32 "
+                         "along K (--fp8-max-error works under it; --fp8-scaling does not apply), single GPU")
     ap.add_argument("--fp8-scaling", choices=tuple(lib.FP8_SCALINGS), default=None,
                     help="scaling of the fp8 GEMMs (default: the config's fp8_scaling, row): row = one fp32 scale per token / output "
                          "channel; mx = OCP MX, one power-of-two scale per block of 32 along K in the matrix instruction, so an outlier "

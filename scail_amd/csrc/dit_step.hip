@@ -23,6 +23,9 @@ struct ProfPool {
     size_t used = 0;
 };
 
+// the third quantised form of a handle beside SCAIL_DIT_FP8_SCALE_ROW / _MX: packed e2m3 codes + E8M0 block scales (scail_dit_enable_fp6).
+// Internal: scail_dit_enable_fp8_scaled does not accept it.
+enum { QFORM_FP6 = 2 };
 struct scail_dit {
     scail_dit_config cfg;
     scail_dit_weights w;
@@ -34,7 +37,7 @@ struct scail_dit {
     // fp8 GEMMs (scail_dit_enable_fp8): the SCAIL_DIT_FP8_* mask in force and, per layer and GEMM (bit index), the e4m3 weight codes and
     // per-channel scales in the caller's buffer
     uint32_t fp8 = 0;
-    int fp8_scaling = SCAIL_DIT_FP8_SCALE_ROW;     // one scaling per handle, chosen at enable time
+    int fp8_scaling = SCAIL_DIT_FP8_SCALE_ROW;     // one quantised form per handle, chosen at enable time: a SCAIL_DIT_FP8_SCALE_* or QFORM_FP6
     struct Fp8W { const uint8_t* q; const float* s; const uint8_t* e; };   // s: fp32 row scales (ROW); e: E8M0 block scales [N, K / 32] (MX)
     std::vector<std::array<Fp8W, 6>> fp8w;
     // scail_dit_fp8_select_layers: per layer, the subset of `fp8` in force (empty: `fp8` in every layer)
@@ -215,8 +218,8 @@ static int probe_check(const scail_dit* h, int64_t rows) {
 // ---- workspaces: every layout is stated once; the *_workspace_bytes query and the call that checks it read the same struct ----
 struct BlockBufs {
     scail_bf16 *xn, *qkv, *att, *ff, *vt;
-    uint8_t* xq;   // fp8 GEMMs only (else null): e4m3 rows of the GEMM input (rows x the widest fp8 K) and their scales:
-    float* sx;     // rows fp32 (per-row scaling) or, through ex(), rows x (the widest fp8 K) / 32 E8M0 bytes (MX)
+    uint8_t* xq;   // fp8 GEMMs only (else null): e4m3 rows of the GEMM input (rows x the widest fp8 K; fp6: rows x 3/4 of it, packed) and their scales:
+    float* sx;     // rows fp32 (per-row scaling) or, through ex(), rows x (the widest fp8 K) / 32 E8M0 bytes (MX and fp6)
     uint8_t* ex() const { return reinterpret_cast<uint8_t*>(sx); }
 };
 // The scratch of a (B, Ltok) block, xn | qkv | att | ff | vt | xq | sx, as byte offsets into a workspace from `at` on; end: the first
@@ -240,8 +243,8 @@ static BlockWs block_ws(const scail_dit* h, int64_t B, int64_t Ltok, int sp_mode
     s.att = c.take(rows * D * 2);
     s.ff = c.take(rows * FF * 2);
     s.vt = c.take(vt_elems(h->cfg, B, Ltok, sp_mode, ranks) * 2);
-    s.xq = c.take(rows * f8_k);
-    s.sx = c.take(h->fp8_scaling == SCAIL_DIT_FP8_SCALE_MX ? rows * (f8_k / 32) : f8_k ? rows * 4 : 0);
+    s.xq = c.take(h->fp8_scaling == QFORM_FP6 ? rows * (f8_k / 4 * 3) : rows * f8_k);
+    s.sx = c.take(h->fp8_scaling != SCAIL_DIT_FP8_SCALE_ROW ? rows * (f8_k / 32) : f8_k ? rows * 4 : 0);
     s.end = c.off;
     return s;
 }
@@ -301,6 +304,10 @@ static CacheWs cache_ws(const scail_dit_config& c, int64_t B, int64_t Lnoise) {
 static int fp8_quant_gemm(const scail_dit* h, const scail_dit::Fp8W& f, const BlockBufs& bf, const scail_bf16* x, int64_t lda, const float* bias,
                           scail_bf16* y, int64_t ldc, int64_t M, int64_t N, int64_t K, int epi, const scail_bf16* resid, int64_t ldr,
                           const float* gate, int64_t gs, int64_t rpb, void* stream) {
+    if (h->fp8_scaling == QFORM_FP6) {
+        DIT_TRY(scail_quant_mxfp6_rows(x, lda, bf.xq, K / 4 * 3, bf.ex(), K / 32, M, K, stream));
+        return scail_gemm_mxfp6(bf.xq, K / 4 * 3, bf.ex(), K / 32, f.q, f.e, bias, y, ldc, M, N, K, epi, resid, ldr, gate, gs, rpb, stream);
+    }
     if (h->fp8_scaling == SCAIL_DIT_FP8_SCALE_MX) {
         DIT_TRY(scail_quant_mxfp8_rows(x, lda, bf.xq, K, bf.ex(), K / 32, M, K, stream));
         return scail_gemm_mxfp8(bf.xq, K, bf.ex(), K / 32, f.q, f.e, bias, y, ldc, M, N, K, epi, resid, ldr, gate, gs, rpb, stream);
@@ -310,8 +317,8 @@ static int fp8_quant_gemm(const scail_dit* h, const scail_dit::Fp8W& f, const Bl
 }
 
 // GEMM g of layer i: scail_gemm_bf16, or (SCAIL_DIT_FP8_* bit g in force in layer i) the rows of x quantized to e4m3 into the block's
-// scratch and scail_gemm_fp8 on the layer's e4m3 weight (scail_quant_mxfp8_rows + scail_gemm_mxfp8 under MX scaling: fp8_quant_gemm
-// above); the same epilogue either way.  While the probe is on, a GEMM whose weight is
+// scratch and scail_gemm_fp8 on the layer's e4m3 weight (scail_quant_mxfp8_rows + scail_gemm_mxfp8 under MX scaling, scail_quant_mxfp6_rows
+// + scail_gemm_mxfp6 under fp6: fp8_quant_gemm above); the same epilogue either way.  While the probe is on, a GEMM whose weight is
 // quantised (in force or not) first runs twice on these very rows with the plain bias epilogue -- bf16 and fp8, into the probe's two
 // buffers --, their distance goes to table[i][g], and the real GEMM then runs in bf16.
 static int dit_gemm(scail_dit* h, int64_t i, int g, const BlockBufs& bf, const scail_bf16* x, int64_t lda, const float* bias, scail_bf16* y,
@@ -672,7 +679,9 @@ extern "C" void scail_dit_destroy(scail_dit* h) {
 // ---- fp8 per-token GEMMs (include/scail_dit.h scail_dit_enable_fp8) ----
 // caller buffer layout: for every layer, for every selected GEMM in bit order, the e4m3 codes [N, K] then the fp32 scales [N] (per-row
 // scaling) or the E8M0 block scales [N, K / 32] (MX), each block 256-byte aligned
-static int64_t fp8_scale_bytes(int scaling, int64_t N, int64_t K) { return scaling == SCAIL_DIT_FP8_SCALE_MX ? N * (K / 32) : N * 4; }
+// (fp6: the packed e2m3 codes [N, 3 K / 4 bytes] then the E8M0 block scales)
+static int64_t fp8_scale_bytes(int scaling, int64_t N, int64_t K) { return scaling != SCAIL_DIT_FP8_SCALE_ROW ? N * (K / 32) : N * 4; }
+static int64_t fp8_code_bytes(int scaling, int64_t N, int64_t K) { return scaling == QFORM_FP6 ? N * (K / 4 * 3) : N * K; }
 static int fp8_scaling_check(const char* fn, int scaling) {
     if (scaling == SCAIL_DIT_FP8_SCALE_ROW || scaling == SCAIL_DIT_FP8_SCALE_MX) return 0;
     scail_set_error(std::string(fn) + ": unknown scaling " + std::to_string(scaling) + " (SCAIL_DIT_FP8_SCALE_ROW = 0 or SCAIL_DIT_FP8_SCALE_MX = 1)");
@@ -684,7 +693,7 @@ static int64_t fp8_weight_bytes(const scail_dit_config& c, uint32_t which, int s
         if (which & (1u << g)) {
             int64_t N, K;
             gemm_shape(c, g, &N, &K);
-            per_layer += align256(N * K) + align256(fp8_scale_bytes(scaling, N, K));
+            per_layer += align256(fp8_code_bytes(scaling, N, K)) + align256(fp8_scale_bytes(scaling, N, K));
         }
     return per_layer * c.num_layers;
 }
@@ -695,10 +704,19 @@ extern "C" int64_t scail_dit_fp8_weight_bytes_scaled(const scail_dit* h, uint32_
 extern "C" int64_t scail_dit_fp8_weight_bytes(const scail_dit* h, uint32_t which) {
     return scail_dit_fp8_weight_bytes_scaled(h, which, SCAIL_DIT_FP8_SCALE_ROW);
 }
-extern "C" int scail_dit_enable_fp8_scaled(scail_dit* h, uint32_t which, int scaling, void* buf, int64_t bytes, void* stream) {
-    if (fp8_scaling_check("scail_dit_enable_fp8_scaled", scaling)) return 1;
-    SCAIL_REQUIRE(h != nullptr, "null handle");
-    SCAIL_REQUIRE((which & ~(uint32_t)SCAIL_DIT_FP8_ALL) == 0, "unknown SCAIL_DIT_FP8_* bit");
+// scail_dit_enable_fp8_scaled and scail_dit_enable_fp6: `scaling` is a SCAIL_DIT_FP8_SCALE_* or QFORM_FP6
+// (errors carry the public entry's name, as SCAIL_REQUIRE would give them there)
+static int enable_quantised(scail_dit* h, uint32_t which, int scaling, void* buf, int64_t bytes, void* stream) {
+    const char* const fn = scaling == QFORM_FP6 ? "scail_dit_enable_fp6" : "scail_dit_enable_fp8_scaled";
+#define QREQ(cond, msg)                                                                  \
+    do {                                                                                 \
+        if (!(cond)) {                                                                   \
+            scail_set_error(std::string(fn) + ": " + (msg) + " [" #cond "]");            \
+            return 1;                                                                    \
+        }                                                                                \
+    } while (0)
+    QREQ(h != nullptr, "null handle");
+    QREQ((which & ~(uint32_t)SCAIL_DIT_FP8_ALL) == 0, "unknown SCAIL_DIT_FP8_* bit");
     // a new set of quantised matrices: the per-layer selection and the probe (whose buffers were sized for the old set) start over
     h->fp8_sel.clear();
     probe_off(h);
@@ -718,11 +736,13 @@ extern "C" int scail_dit_enable_fp8_scaled(scail_dit* h, uint32_t which, int sca
                 return 1;
             }
         }
-    SCAIL_REQUIRE(bytes >= fp8_weight_bytes(h->cfg, which, scaling), "buffer too small (scail_dit_fp8_weight_bytes_scaled)");
-    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "buffer must be 256-byte aligned");
+    QREQ(bytes >= fp8_weight_bytes(h->cfg, which, scaling),
+         scaling == QFORM_FP6 ? "buffer too small (scail_dit_fp6_weight_bytes)" : "buffer too small (scail_dit_fp8_weight_bytes_scaled)");
+    QREQ((reinterpret_cast<uintptr_t>(buf) & 255) == 0, "buffer must be 256-byte aligned");
+#undef QREQ
     h->fp8 = 0;                             // bf16 until every selected matrix is quantized
     h->fp8_scaling = SCAIL_DIT_FP8_SCALE_ROW;
-    const bool mx = scaling == SCAIL_DIT_FP8_SCALE_MX;
+    const bool mx = scaling != SCAIL_DIT_FP8_SCALE_ROW;      // block scales (MX and fp6) or fp32 row scales
     h->fp8w.assign(h->cfg.num_layers, {});
     char* p = static_cast<char*>(buf);
     for (int64_t i = 0; i < h->cfg.num_layers; ++i)
@@ -731,10 +751,11 @@ extern "C" int scail_dit_enable_fp8_scaled(scail_dit* h, uint32_t which, int sca
             int64_t N, K;
             gemm_shape(h->cfg, g, &N, &K);
             uint8_t* q = reinterpret_cast<uint8_t*>(p);
-            float* sc = reinterpret_cast<float*>(p + align256(N * K));
+            float* sc = reinterpret_cast<float*>(p + align256(fp8_code_bytes(scaling, N, K)));
             uint8_t* ec = reinterpret_cast<uint8_t*>(sc);
-            p += align256(N * K) + align256(fp8_scale_bytes(scaling, N, K));
-            if (int rc = mx ? scail_quant_mxfp8_rows(gemm_weight(h->layers[i], g), K, q, K, ec, K / 32, N, K, stream)
+            p += align256(fp8_code_bytes(scaling, N, K)) + align256(fp8_scale_bytes(scaling, N, K));
+            if (int rc = scaling == QFORM_FP6 ? scail_quant_mxfp6_rows(gemm_weight(h->layers[i], g), K, q, K / 4 * 3, ec, K / 32, N, K, stream)
+                         : mx ? scail_quant_mxfp8_rows(gemm_weight(h->layers[i], g), K, q, K, ec, K / 32, N, K, stream)
                             : scail_quant_fp8_rows(gemm_weight(h->layers[i], g), K, q, K, sc, N, K, stream)) {
                 h->fp8w.clear();
                 return rc;
@@ -744,6 +765,17 @@ extern "C" int scail_dit_enable_fp8_scaled(scail_dit* h, uint32_t which, int sca
     h->fp8 = which;
     h->fp8_scaling = scaling;
     return 0;
+}
+extern "C" int scail_dit_enable_fp8_scaled(scail_dit* h, uint32_t which, int scaling, void* buf, int64_t bytes, void* stream) {
+    if (fp8_scaling_check("scail_dit_enable_fp8_scaled", scaling)) return 1;
+    return enable_quantised(h, which, scaling, buf, bytes, stream);
+}
+extern "C" int64_t scail_dit_fp6_weight_bytes(const scail_dit* h, uint32_t which) {
+    if (h == nullptr || (which & ~(uint32_t)SCAIL_DIT_FP8_ALL) != 0) return -1;
+    return fp8_weight_bytes(h->cfg, which, QFORM_FP6);
+}
+extern "C" int scail_dit_enable_fp6(scail_dit* h, uint32_t which, void* buf, int64_t bytes, void* stream) {
+    return enable_quantised(h, which, QFORM_FP6, buf, bytes, stream);
 }
 extern "C" int scail_dit_enable_fp8(scail_dit* h, uint32_t which, void* buf, int64_t bytes, void* stream) {
     return scail_dit_enable_fp8_scaled(h, which, SCAIL_DIT_FP8_SCALE_ROW, buf, bytes, stream);

@@ -8,6 +8,9 @@
 //   scail_quant_mxfp8_rows  bf16 [R, C] -> e4m3 [R, C] + one E8M0 byte per aligned block of 32 columns (the OCP MX layout)
 //   scail_gemm_mxfp8        the same GEMM kernel with the block scales in the MFMA's scale operands and no fp32 scales in the epilogue;
 //                           a block lies inside a row, so the row independence above holds here too.
+//   scail_quant_mxfp6_rows  bf16 [R, C] -> packed OCP e2m3 codes [R, 3 C / 4 bytes] + one E8M0 byte per aligned block of 32 columns
+//   scail_gemm_mxfp6        the MX GEMM on 6-bit operands (cbsz = blgp = 2: half the MFMA cycles, 3/4 of the operand bytes); a sibling
+//                           kernel at the end of this file.
 #include "common.h"
 #include "gemm_epi.h"
 
@@ -120,6 +123,74 @@ extern "C" int scail_quant_mxfp8_rows(const scail_bf16* x, int64_t ldx, uint8_t*
     hipLaunchKernelGGL(scail_quant_mxfp8_rows_kernel, dim3((unsigned)wgs), dim3(QMX_THREADS), 0, (hipStream_t)stream,
                        reinterpret_cast<const u16*>(x), ldx, q, ldq, e, lde, chunks, (int)cpr);
     return scail_check_launch("scail_quant_mxfp8_rows");
+}
+
+// ---- MXFP6 block quantization (include/scail_hip.h scail_quant_mxfp6_rows) ---------------------------------------------------------
+// One lane per 16 columns (two 16-byte loads), the 2 lanes of an aligned pair hold one block of 32: the block's amax is one xor shuffle
+// away and the row is read once.  A lane's 16 codes are 96 bits = 3 dwords, written with one 12-byte store at byte 12 * (c / 16) of the
+// row: consecutive lanes write consecutive bytes.  (A lane's piece of the packed row is 12 bytes at a 12-byte pitch, so 16-byte stores
+// would need a 4-lane exchange; the pass moves 2 bytes in and 0.78 out per element.)  Plain integer code, no convert instruction.
+// Numerics (bit-exact, tests/test_mxfp6_gpu.py):
+//   amax == 0: byte 127, codes 0;  else amax = m 2^E (1 <= m < 2), s = E - 2 + (m > 1.875) clamped to >= -127 (the smallest s with
+//   amax 2^-s <= 7.5), byte s + 127, q = e2m3_rne(clamp(x 2^-s, -7.5, 7.5)).  e2m3_rne: |v| < 2 has the step 1/8 (subnormals and the first
+//   binade), [2, 4) 1/4, [4, 7.5] 1/2; n = rint(|v| / step) (ties to even) and the code magnitude is n, n + 8, n + 16: n and the code have
+//   the same parity, so the tie rule carries over, and n = 16 is the next binade's first code.  The sign bit of v is kept (-0 too).
+//   A NaN is skipped by the amax and becomes code 0; an infinity counts as 2^128 (byte 253) and becomes +-7.5.
+#define QF6_THREADS 256
+__device__ __forceinline__ uint32_t e2m3_code(float v) {
+    const float a = fabsf(v);
+    const float inv = a < 2.f ? 8.f : a < 4.f ? 4.f : 2.f;
+    const uint32_t base = a < 2.f ? 0u : a < 4.f ? 8u : 16u;
+    return ((uint32_t)__builtin_rintf(a * inv) + base) | ((__float_as_uint(v) >> 31) << 5);
+}
+__global__ __launch_bounds__(QF6_THREADS) void scail_quant_mxfp6_rows_kernel(const u16* __restrict__ x, int64_t ldx, u8* __restrict__ q,
+                                                                             int64_t ldq, u8* __restrict__ e, int64_t lde, int64_t chunks,
+                                                                             int cpr) {
+    const int64_t i = (int64_t)blockIdx.x * QF6_THREADS + threadIdx.x;
+    if (i >= chunks) return;          // whole pairs leave together
+    const int64_t r = i / cpr;
+    const int c16 = (int)(i - r * cpr);
+    float f[16];
+    unpack8(*reinterpret_cast<const uint4*>(x + r * ldx + c16 * 16), f);
+    unpack8(*reinterpret_cast<const uint4*>(x + r * ldx + c16 * 16 + 8), f + 8);
+    float amax = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) amax = fmaxf(amax, fabsf(f[k]));      // fmaxf skips a NaN
+    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+    const bool zero = amax == 0.f;
+    const uint32_t bits = __float_as_uint(amax);
+    int s = (int)(bits >> 23) - 127 - 2 + ((bits & 0x7fffffu) > 0x700000u ? 1 : 0);
+    s = zero ? 0 : max(s, -127);
+    const float rs = __uint_as_float((uint32_t)(127 - s) << 23);
+    uint32_t cd[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        float v = f[k] * rs;
+        v = v != v ? 0.f : fminf(fmaxf(v, -7.5f), 7.5f);
+        cd[k] = zero ? 0u : e2m3_code(v);
+    }
+    uint32_t* out = reinterpret_cast<uint32_t*>(q + r * ldq + c16 * 12);
+    out[0] = cd[0] | cd[1] << 6 | cd[2] << 12 | cd[3] << 18 | cd[4] << 24 | cd[5] << 30;
+    out[1] = cd[5] >> 2 | cd[6] << 4 | cd[7] << 10 | cd[8] << 16 | cd[9] << 22 | cd[10] << 28;
+    out[2] = cd[10] >> 4 | cd[11] << 2 | cd[12] << 8 | cd[13] << 14 | cd[14] << 20 | cd[15] << 26;
+    if ((threadIdx.x & 1) == 0) e[r * lde + (c16 >> 1)] = (u8)(s + 127);
+}
+
+extern "C" int scail_quant_mxfp6_rows(const scail_bf16* x, int64_t ldx, uint8_t* q, int64_t ldq, uint8_t* e, int64_t lde, int64_t rows,
+                                      int64_t cols, void* stream) {
+    SCAIL_REQUIRE(x != nullptr && q != nullptr && e != nullptr, "null pointer");
+    SCAIL_REQUIRE(rows >= 0 && cols > 0 && cols % 32 == 0 && cols < (1ll << 30), "cols must be a positive multiple of 32");
+    SCAIL_REQUIRE(ldx >= cols && ldx % 8 == 0, "ldx must be >= cols and a multiple of 8");
+    SCAIL_REQUIRE(ldq >= cols / 4 * 3 && ldq % 4 == 0, "ldq (bytes) must be >= 3 * cols / 4 and a multiple of 4");
+    SCAIL_REQUIRE(lde >= cols / 32, "lde must be >= cols / 32");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(q) & 3) == 0, "pointer alignment (x 16 B, q 4 B)");
+    SCAIL_REQUIRE(rows < (1ll << 31), "too many rows");
+    const int64_t cpr = cols / 16, chunks = rows * cpr, wgs = (chunks + QF6_THREADS - 1) / QF6_THREADS;
+    SCAIL_REQUIRE(wgs < (1ll << 31), "too many elements (rows * cols / 4096 must stay below 2^31)");
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(scail_quant_mxfp6_rows_kernel, dim3((unsigned)wgs), dim3(QF6_THREADS), 0, (hipStream_t)stream,
+                       reinterpret_cast<const u16*>(x), ldx, q, ldq, e, lde, chunks, (int)cpr);
+    return scail_check_launch("scail_quant_mxfp6_rows");
 }
 
 // ---- relative error of two bf16 matrices (the executor's fp8 probe, include/scail_hip.h scail_rel_err_rows) -------------------------
@@ -497,6 +568,198 @@ extern "C" int scail_gemm_mxfp8(const uint8_t* x, int64_t lda, const uint8_t* ex
         case SCAIL_EPI_RESID: return launch_gemm_fp8<SCAIL_EPI_RESID, true>(P, s);
         default:
             scail_set_error("scail_gemm_mxfp8: epilogue must be SCAIL_EPI_BIAS, SCAIL_EPI_GELU_TANH or SCAIL_EPI_RESID");
+            return 1;
+    }
+}
+
+// ---- MXFP6 GEMM (include/scail_hip.h scail_gemm_mxfp6) ---------------------------------------------------------------------------------
+// The MX kernel above on packed e2m3 operands (cbsz = blgp = 2: the MFMA reads 6 registers per operand and takes half the e4m3 form's
+// cycles).  Same 256 x 256 tile, 8 waves, wave tile 128(m) x 64(n), LDS-DMA two k-tiles deep, one barrier per k-tile, the same scale
+// stage (a k-tile of 128 elements is still one aligned scale dword per row) and the same epilogue.  What differs:
+//   Rows of a k-tile are 96 bytes = 6 chunks of 16.  A tile is 24 KB = 24 DMA pieces of 1 KB (3 per wave and operand): lane l of piece p
+//   fills the 16-byte slot 64 p + l of the tile = chunk slot % 6 of row slot / 6 (the LDS image stays lane-linear; rows are 96 bytes
+//   apart, unpadded).  LDS: 2 x 2 x 24 KB of tiles + 4 KB of scale dwords = 100 KB.
+//   Operand layout, found on the device (one code and one raised scale byte at a time): code j of a lane's 32 sits in bits [6 j, 6 j + 6)
+//   of its 6 registers, lane (r, g) holds 32 consecutive k of row r, A and B alike, and its scale operand applies to exactly those 32
+//   codes.  So a lane's fragment is one whole block, the 24 bytes at 24 b of the row's 96, and its scale is that block's byte: no
+//   dealing of halves as in the e4m3 form.
+//   24 bytes at a 24-byte pitch are not 16-byte aligned for odd b.  Step ks of lane half g takes block b = ks + 2 g (not 2 ks + g): the
+//   parity of b is then the same in every lane of an instruction, even blocks are read as ds_read_b128 (chunk 3 g) + ds_read_b64 (first
+//   half of chunk 3 g + 1), odd blocks as ds_read_b64 (second half of chunk 3 g + 1) + ds_read_b128 (chunk 3 g + 2): every read is
+//   naturally aligned and the register order is fixed at compile time.  A and B use the same assignment, and each block meets its own
+//   scale byte.
+//   Bank conflicts: 16-byte slot 6 r + c of the tile, so the rows of a ds_read_b128 lane group ({0-3, 12-15, 20-27} or {4-11, 16-19,
+//   28-31}) fall on the 8 even or the 8 odd slots of the 256-byte bank row twice over.  Storing chunk c of row r at c ^ ((r >> 4) & 1)
+//   (on the DMA's per-lane source address and on the reads) moves the rows 16 .. 31 to the other parity: conflict-free.  The 8-byte
+//   reads stay 2-way (rows r and r + 8 share a bank and 16-byte granularity leaves the half fixed): 4 LDS cycles like a b128, 8 per
+//   fragment, what the e4m3 form spends on its 32 bytes.
+//   The k-tile is 128 elements.  A 256-element k-tile (the MFMA cycles per barrier of the e4m3 kernel) was not built or measured.
+#define F6_BKB 96      // bytes of a row's k-tile
+template <int EPI>
+__global__ __launch_bounds__(512) void scail_gemm_fp6_kernel(GemmFp8Params P) {
+    constexpr int BM = 256, BN = 256, WN = 4, NT = 512;
+    constexpr int WTM = 128, WTN = 64, MI = WTM / 32, NI = WTN / 32;
+    extern __shared__ __attribute__((aligned(16))) u8 smem8[];
+    u8* Xs = smem8;                    // [2][BM][F6_BKB]
+    u8* Ws = smem8 + 2 * BM * F6_BKB;  // [2][BN][F6_BKB]
+    uint32_t* Ss = reinterpret_cast<uint32_t*>(smem8 + 2 * (BM + BN) * F6_BKB);   // [2][BM + BN] scale dwords of the k-tile
+    const GemmParams& p = P.e;
+
+    // ---- tile mapping: as scail_gemm_fp8_kernel ----
+    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
+    const int nb = tiles_m * tiles_n;
+    int wg;
+    {
+        const int id = blockIdx.x;
+        const int q = nb >> 3, r = nb & 7, xcd = id & 7, loc = id >> 3;
+        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+    }
+    const int in_group = F8_GROUP_M * tiles_n;
+    const int gid = wg / in_group;
+    const int first_m = gid * F8_GROUP_M;
+    const int gsz = min(tiles_m - first_m, F8_GROUP_M);
+    const int pid_m = first_m + (wg % in_group) % gsz;
+    const int pid_n = (wg % in_group) / gsz;
+    const int m0 = pid_m * BM, n0 = pid_n * BN;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / WN, wn = wave % WN;
+    const int l31 = lane & 31, g = lane >> 5;
+
+    // LDS-DMA pieces: piece j of an operand = slots 64 j .. 64 j + 63 of the tile.  Rows past M / N read the last row.
+    static_assert(BM * F6_BKB % (1024 * (NT / 64)) == 0 && BM == BN, "whole pieces per wave");
+    constexpr int PC = BM * F6_BKB / 1024 / (NT / 64);     // 3
+    const int64_t ldw = (int64_t)p.K / 4 * 3;
+    const u8* srcx[PC];
+    const u8* srcw[PC];
+#pragma unroll
+    for (int i = 0; i < PC; ++i) {
+        const int slot = 64 * (wave * PC + i) + lane, r = slot / 6, c = (slot - 6 * r) ^ ((r >> 4) & 1);
+        srcx[i] = P.x + (int64_t)min(m0 + r, p.M - 1) * p.lda + (c << 4);
+        srcw[i] = P.w + (int64_t)min(n0 + r, p.N - 1) * ldw + (c << 4);
+    }
+#define F6_DMA(kb_, buf_)                                                                                                     \
+    {                                                                                                                         \
+        _Pragma("unroll") for (int i_ = 0; i_ < PC; ++i_) {                                                                   \
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcx[i_] + (kb_)),              \
+                (__attribute__((address_space(3))) void*)(Xs + (buf_) * BM * F6_BKB + 1024 * (wave * PC + i_)), 16, 0, 0);     \
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcw[i_] + (kb_)),              \
+                (__attribute__((address_space(3))) void*)(Ws + (buf_) * BN * F6_BKB + 1024 * (wave * PC + i_)), 16, 0, 0);     \
+        }                                                                                                                     \
+    }
+    // fragment-read byte offsets in this lane's row: step 0 reads block 2 g as chunk 3 g + the first half of chunk 3 g + 1, step 1
+    // block 2 g + 1 as the second half of chunk 3 g + 1 + chunk 3 g + 2; chunks swizzled by the row's bit 4 (= l31's: fragment rows
+    // start at multiples of 32)
+    const int fsw = (l31 >> 4) & 1;
+    const int off_q0 = ((3 * g) ^ fsw) << 4, off_d = ((3 * g + 1) ^ fsw) << 4, off_q1 = ((3 * g + 2) ^ fsw) << 4;
+
+    f32x16 acc[NI][MI];
+#pragma unroll
+    for (int a = 0; a < NI; ++a)
+#pragma unroll
+        for (int b = 0; b < MI; ++b)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+
+    const int nk = p.K / F8_BK;
+    static_assert(BM == 256 && BN == 256 && NT == 512, "one scale row per thread");
+    const u8* srcs;
+    {
+        const int r = (wave & 3) * 64 + lane;
+        srcs = wave < 4 ? P.ex + (int64_t)min(m0 + r, p.M - 1) * P.ldex : P.ew + (int64_t)min(n0 + r, p.N - 1) * (p.K / 32);
+    }
+#define F6_SCALE_DMA(t_, buf_)                                                                                             \
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcs + 4 * (t_)),                    \
+        (__attribute__((address_space(3))) void*)(Ss + (buf_) * (BM + BN) + 64 * wave), 4, 0, 0);
+    F6_SCALE_DMA(0, 0)
+    F6_DMA(0, 0)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int t = 0; t < nk; ++t) {
+        const int cur = t & 1;
+        if (t + 1 < nk) {
+            F6_DMA((t + 1) * F6_BKB, cur ^ 1)
+            F6_SCALE_DMA(t + 1, cur ^ 1)
+        }
+        uint32_t sc[NI + MI];          // the scale dwords of this lane's fragment rows, W then x
+#pragma unroll
+        for (int i = 0; i < NI; ++i) sc[i] = Ss[cur * (BM + BN) + BM + wn * WTN + i * 32 + l31];
+#pragma unroll
+        for (int i = 0; i < MI; ++i) sc[NI + i] = Ss[cur * (BM + BN) + wm * WTM + i * 32 + l31];
+        const u8* xs = Xs + (cur * BM + wm * WTM + l31) * F6_BKB;
+        const u8* ws = Ws + (cur * BN + wn * WTN + l31) * F6_BKB;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            i32x8 wf[NI], xf[MI];
+#pragma unroll
+            for (int i = 0; i < NI + MI; ++i) {
+                const u8* row = i < NI ? ws + i * 32 * F6_BKB : xs + (i - NI) * 32 * F6_BKB;
+                const uint4 q4 = *reinterpret_cast<const uint4*>(row + (ks == 0 ? off_q0 : off_q1));
+                const uint2 d2 = *reinterpret_cast<const uint2*>(row + off_d + 8 * ks);
+                const i32x8 fr = ks == 0 ? i32x8{(int)q4.x, (int)q4.y, (int)q4.z, (int)q4.w, (int)d2.x, (int)d2.y, 0, 0}
+                                         : i32x8{(int)d2.x, (int)d2.y, (int)q4.x, (int)q4.y, (int)q4.z, (int)q4.w, 0, 0};
+                if (i < NI) wf[i] = fr; else xf[i - NI] = fr;
+            }
+#pragma unroll
+            for (int ni = 0; ni < NI; ++ni)
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi)
+                    acc[ni][mi] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[ni], xf[mi], acc[ni][mi], 2, 2, 0,
+                                                                                 (int)((sc[ni] >> (8 * ks + 16 * g)) & 0xffu), 0,
+                                                                                 (int)((sc[NI + mi] >> (8 * ks + 16 * g)) & 0xffu));
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+#undef F6_DMA
+#undef F6_SCALE_DMA
+    gemm_epilogue<EPI, MI, NI, WTM, WTN>(acc, p, m0, n0, wm, wn, l31, g);
+}
+
+template <int EPI>
+static int launch_gemm_fp6(const GemmFp8Params& P, hipStream_t stream) {
+    constexpr int lds = 2 * (256 + 256) * F6_BKB + 2 * (256 + 256) * 4;   // 96 KB + 4 KB of staged block scales
+    const int tiles = ((P.e.M + 255) / 256) * ((P.e.N + 255) / 256);
+    return scail_launch_lds<scail_gemm_fp6_kernel<EPI>>("scail_gemm_mxfp6", lds, dim3((unsigned)tiles), dim3(512), lds, stream, P);
+}
+
+extern "C" int scail_gemm_mxfp6(const uint8_t* x, int64_t lda, const uint8_t* ex, int64_t ldex, const uint8_t* w, const uint8_t* ew,
+                                const float* bias, scail_bf16* y, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
+                                const scail_bf16* resid, int64_t ldr, const float* gate, int64_t gate_stride, int64_t rows_per_batch,
+                                void* stream) {
+    SCAIL_REQUIRE(x != nullptr && ex != nullptr && w != nullptr && ew != nullptr && y != nullptr, "null pointer");
+    SCAIL_REQUIRE(M >= 1 && M < (1ll << 31), "M must be >= 1");
+    SCAIL_REQUIRE(N > 0 && N % 128 == 0 && N < (1ll << 31), "N must be a positive multiple of 128");
+    SCAIL_REQUIRE(K > 0 && K % 128 == 0 && K < (1ll << 31), "K must be a positive multiple of 128");
+    SCAIL_REQUIRE(lda >= K / 4 * 3 && lda % 16 == 0 && ldc >= N && ldc % 4 == 0,
+                  "lda (bytes) must be >= 3 * K / 4 and a multiple of 16, ldc >= N and a multiple of 4");
+    SCAIL_REQUIRE(ldex >= K / 32 && ldex % 4 == 0, "ldex must be >= K / 32 and a multiple of 4");
+    SCAIL_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0 &&
+                      (reinterpret_cast<uintptr_t>(ex) & 3) == 0 && (reinterpret_cast<uintptr_t>(ew) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(y) & 7) == 0 && (reinterpret_cast<uintptr_t>(bias) & 15) == 0,
+                  "pointer alignment (x, w, bias 16 B; y 8 B; ex, ew 4 B)");
+    if (epilogue == SCAIL_EPI_RESID) {
+        SCAIL_REQUIRE(resid != nullptr && ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(resid) & 7) == 0, "RESID epilogue needs resid with ldr % 4 == 0");
+        SCAIL_REQUIRE(gate == nullptr || (rows_per_batch > 0 && gate_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(gate) & 15) == 0),
+                      "gate needs rows_per_batch > 0, gate_stride % 4 == 0");
+    }
+    GemmFp8Params P;
+    GemmParams& p = P.e;
+    p.x = nullptr; p.lda = lda; p.w = nullptr; p.bias = bias;
+    p.y = reinterpret_cast<u16*>(y); p.ldc = ldc;
+    p.M = (int)M; p.N = (int)N; p.K = (int)K;
+    p.resid = reinterpret_cast<const u16*>(resid); p.ldr = ldr; p.gate = gate; p.gate_stride = gate_stride; p.rows_per_batch = rows_per_batch;
+    p.group_m = F8_GROUP_M;
+    P.x = x; P.w = w; P.sx = nullptr; P.sw = nullptr;
+    P.ex = ex; P.ew = ew; P.ldex = ldex;
+    hipStream_t s = (hipStream_t)stream;
+    switch (epilogue) {
+        case SCAIL_EPI_BIAS: return launch_gemm_fp6<SCAIL_EPI_BIAS>(P, s);
+        case SCAIL_EPI_GELU_TANH: return launch_gemm_fp6<SCAIL_EPI_GELU_TANH>(P, s);
+        case SCAIL_EPI_RESID: return launch_gemm_fp6<SCAIL_EPI_RESID>(P, s);
+        default:
+            scail_set_error("scail_gemm_mxfp6: epilogue must be SCAIL_EPI_BIAS, SCAIL_EPI_GELU_TANH or SCAIL_EPI_RESID");
             return 1;
     }
 }

@@ -84,7 +84,10 @@ class CStep:
         self.num_layers = net.num_layers
         self.fp8_scaling = getattr(net, "fp8_scaling", "row")   # lib.FP8_SCALINGS key that enable_fp8 uses when none is given
         if getattr(net, "fp8_mask", 0):
-            self.enable_fp8(net.fp8_mask, W["patch_w"].device)
+            if getattr(net, "gemm_precision", "fp8") == "fp6":
+                self.enable_fp6(net.fp8_mask, W["patch_w"].device)
+            else:
+                self.enable_fp8(net.fp8_mask, W["patch_w"].device)
             if getattr(net, "fp8_layer_masks", None) is not None:
                 self.select_fp8_layers(net.fp8_layer_masks)
 
@@ -108,6 +111,23 @@ class CStep:
         L.call("scail_dit_enable_fp8_scaled", self._h, which, sc, buf.data_ptr(), nbytes, torch.cuda.current_stream(device).cuda_stream)
         self._fp8_buf = buf
         self.fp8_scaling = scaling
+
+    def enable_fp6(self, which: int, device) -> None:
+        """scail_dit_enable_fp6: quantize the selected per-token GEMM weights (lib.FP8_GEMMS bits) to packed MXFP6 e2m3 into a buffer this
+        object owns, replacing an fp8 form; which = 0 returns to bf16."""
+        lib = L.load()
+        self._probe = None                               # the executor turns the probe off and forgets the per-layer selection
+        stream = torch.cuda.current_stream(device).cuda_stream
+        if not which:
+            L.call("scail_dit_enable_fp6", self._h, 0, None, 0, stream)
+            self._fp8_buf = None
+            return
+        nbytes = lib.scail_dit_fp6_weight_bytes(self._h, which)
+        if nbytes < 0:
+            raise L.ScailHipError(f"scail_dit_fp6_weight_bytes: bad mask {which}")
+        buf = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        L.call("scail_dit_enable_fp6", self._h, which, buf.data_ptr(), nbytes, stream)
+        self._fp8_buf = buf
 
     def select_fp8_layers(self, masks) -> None:
         """scail_dit_fp8_select_layers: ``masks`` = one lib.FP8_GEMMS mask per layer, each a subset of the enabled mask (the GEMMs that

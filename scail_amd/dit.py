@@ -64,16 +64,16 @@ def _as_bf16(t: torch.Tensor, dev) -> torch.Tensor:
 
 
 def _fp8_options(gemm_precision, fp8_gemms):
-    """("bf16" | "fp8", SCAIL_DIT_FP8_* mask) from the constructor options: fp8_gemms = None (all six per-token GEMMs), an iterable of
-    names from lib.FP8_GEMMS, or the mask itself."""
-    if gemm_precision not in ("bf16", "fp8"):
-        raise ValueError(f"gemm_precision must be 'bf16' or 'fp8', got {gemm_precision!r}")
+    """("bf16" | "fp8" | "fp6", SCAIL_DIT_FP8_* mask) from the constructor options: fp8_gemms = None (all six per-token GEMMs), an iterable
+    of names from lib.FP8_GEMMS, or the mask itself.  fp8_gemms keeps its name under "fp6": it selects the quantised GEMMs."""
+    if gemm_precision != "bf16" and gemm_precision not in L.GEMM_PRECISIONS:
+        raise ValueError(f"gemm_precision must be 'bf16', 'fp8' or 'fp6', got {gemm_precision!r}")
     if gemm_precision == "bf16":
         if fp8_gemms is not None:
             raise ValueError("fp8_gemms needs gemm_precision='fp8'")
         return "bf16", 0
     if fp8_gemms is None:
-        return "fp8", L.FP8_ALL
+        return gemm_precision, L.FP8_ALL
     if isinstance(fp8_gemms, int) and not isinstance(fp8_gemms, bool):
         mask = fp8_gemms
     else:
@@ -85,12 +85,13 @@ def _fp8_options(gemm_precision, fp8_gemms):
         mask = sum(L.FP8_GEMMS[g] for g in set(fp8_gemms))
     if not 0 < mask <= L.FP8_ALL:
         raise ValueError(f"fp8_gemms must select at least one of {sorted(L.FP8_GEMMS)} (mask 1..{L.FP8_ALL}), got {fp8_gemms!r}")
-    return "fp8", mask
+    return gemm_precision, mask
 
 
 def _fp8_scaling_option(fp8_scaling, gemm_precision):
     """The constructor option ``fp8_scaling``: "row" (one fp32 scale per row, the default) or "mx" (OCP MX: one E8M0 scale per block of
-    32 along K; include/scail_dit.h SCAIL_DIT_FP8_SCALE_*).  "mx" needs gemm_precision='fp8'."""
+    32 along K; include/scail_dit.h SCAIL_DIT_FP8_SCALE_*).  "mx" needs gemm_precision='fp8': the option scales the fp8 GEMMs only (fp6 is
+    block-scaled by its format)."""
     if fp8_scaling not in L.FP8_SCALINGS:
         raise ValueError(f"fp8_scaling must be one of {sorted(L.FP8_SCALINGS)}, got {fp8_scaling!r}")
     if fp8_scaling != "row" and gemm_precision != "fp8":
@@ -223,7 +224,8 @@ class DiffusionTransformer(nn.Module):
         for nm, mult in (("hidden_size", 64), ("inner_hidden_size", 64), ("text_dim", 64)):
             if getattr(self, nm) % mult:
                 raise NotImplementedError(f"{nm} must be a multiple of {mult}")
-        # opt-in fp8 (e4m3) per-token GEMMs (include/scail_dit.h scail_dit_enable_fp8); a yaml sets them through network_config.params
+        # opt-in fp8 (e4m3) or fp6 (MXFP6 e2m3) per-token GEMMs (include/scail_dit.h scail_dit_enable_fp8 / _fp6); a yaml sets them through
+        # network_config.params
         self.gemm_precision, self.fp8_mask = _fp8_options(gemm_precision, fp8_gemms)
         self.fp8_scaling = _fp8_scaling_option(fp8_scaling, self.gemm_precision)
         # fp8_layers: which of those GEMMs stay fp8 in each layer (scail_dit_fp8_select_layers); None = all of them in every layer
@@ -233,7 +235,7 @@ class DiffusionTransformer(nn.Module):
             D, FF = self.hidden_size, self.inner_hidden_size
             for name, (n, k) in (("qkv", (3 * D, D)), ("o", (D, D)), ("cq", (D, D)), ("co", (D, D)), ("w1", (FF, D)), ("w2", (D, FF))):
                 if self.fp8_mask & L.FP8_GEMMS[name] and (n % 128 or k % 128):
-                    raise NotImplementedError(f"fp8 GEMM {name} ({n} x {k}): the fp8 kernel needs N and K multiples of 128")
+                    raise NotImplementedError(f"{self.gemm_precision} GEMM {name} ({n} x {k}): the {self.gemm_precision} kernel needs N and K multiples of 128")
         self._build_params(device, init_seed)
         self._prepared: Optional[Dict] = None
         self._cond_cache = None
@@ -662,7 +664,7 @@ class DiffusionTransformer(nn.Module):
         sp = self.sp if (self.sp is not None and self.sp.size > 1) else None
         use_c = self.executor_ok()
         if self.fp8_mask and (sp is not None or not use_c):
-            raise NotImplementedError("gemm_precision='fp8' runs in the C executor on a single rank only: not on sequence-parallel ranks, "
+            raise NotImplementedError(f"gemm_precision='{self.gemm_precision}' runs in the C executor on a single rank only: not on sequence-parallel ranks, "
                                       "not on the per-op path (SCAIL_C_STEP=0, _tap, kernel_timer)")
         ex = self._executor() if use_c else None
         xch = sp.c_exchange(nh, D, B, Ltok, dev) if (use_c and sp is not None) else None

@@ -110,7 +110,8 @@ class SATVideoDiffusionEngine(nn.Module):
         through the executor's probe, and every (layer, GEMM) whose fp8 result is further than ``max_rel_err`` (relative, Frobenius) from
         its bf16 twin stays in bf16 from then on.  shape = (T, C, H, W); the noise comes from a generator of its own (``seed``), so the
         request's random stream is not consumed.  With ``smpl_tiled`` in ``cond`` (temporal tiles) the first window is probed.
-        Returns dict(rel_err (layers, 6), worst (layers, 6), masks [layers], enabled = the quantised mask, scaling = the network's fp8_scaling, which the probe measured); columns in lib.FP8_GEMMS order."""
+        Returns dict(rel_err (layers, 6), worst (layers, 6), masks [layers], enabled = the quantised mask, scaling = the network's fp8_scaling, which the probe measured); columns in lib.FP8_GEMMS order;
+        precision = "fp8" | "fp6", the quantised form the probe measured (the call works under either)."""
         from .dit import choose_fp8_layers
         net = self.network
         if self.sp is not None and self.sp.size > 1:
@@ -129,7 +130,8 @@ class SATVideoDiffusionEngine(nn.Module):
         rel, worst = net.fp8_probe(torch.cat([x, x], 0), t, ctx, None, cond_key=("sample_hip", id(cond)), cfg_pair=True, **shared)
         masks = choose_fp8_layers(rel, max_rel_err, net.fp8_mask)
         net.select_fp8_layers(masks)
-        return dict(rel_err=rel, worst=worst, masks=masks, enabled=net.fp8_mask, scaling=getattr(net, "fp8_scaling", "row"))
+        return dict(rel_err=rel, worst=worst, masks=masks, enabled=net.fp8_mask, scaling=getattr(net, "fp8_scaling", "row"),
+                    precision=getattr(net, "gemm_precision", "fp8"))
 
     @torch.no_grad()
     def decode_first_stage(self, z, chunk_frames=None):

@@ -83,6 +83,9 @@ SIGNATURES = {
     # MX block scaling: E8M0 bytes [rows, cols / 32] beside the e4m3 codes
     "scail_quant_mxfp8_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p],
     "scail_gemm_mxfp8": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _i64, _p, _i64, _i64, _p],
+    # MXFP6: packed e2m3 codes [rows, 3 cols / 4 bytes] + E8M0 bytes; leading dimensions of packed matrices in bytes
+    "scail_quant_mxfp6_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p],
+    "scail_gemm_mxfp6": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _i64, _p, _i64, _i64, _p],
     "scail_resize_crop_aa": [_p, _i, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
     "scail_pose_half": [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p],
     # include/scail_dit.h (structs are passed by pointer; scail_amd/cstep.py builds them)
@@ -115,6 +118,9 @@ SIGNATURES = {
     # the same two with the scaling (FP8_SCALINGS) named
     "scail_dit_fp8_weight_bytes_scaled": [_p, C.c_uint32, _i],
     "scail_dit_enable_fp8_scaled": [_p, C.c_uint32, _i, _p, _i64, _p],
+    # the 6-bit form (packed e2m3 + E8M0): its own pair of entries, not a third FP8_SCALINGS value
+    "scail_dit_fp6_weight_bytes": [_p, C.c_uint32],
+    "scail_dit_enable_fp6": [_p, C.c_uint32, _p, _i64, _p],
     # per-layer fp8 selection (host uint32 masks [num_layers]) and the on-device GEMM error probe (device fp64 table [layers][6][4])
     "scail_dit_fp8_select_layers": [_p, _p],
     "scail_dit_fp8_probe_bytes": [_p, _i64, _i64],
@@ -158,6 +164,8 @@ FP8_GEMMS = {"qkv": 1, "o": 2, "cq": 4, "co": 8, "w1": 16, "w2": 32}
 FP8_ALL = 63
 # include/scail_dit.h SCAIL_DIT_FP8_SCALE_*: one fp32 scale per row, or OCP MX (one E8M0 scale per block of 32 along K)
 FP8_SCALINGS = {"row": 0, "mx": 1}
+# DiffusionTransformer(gemm_precision=...): what the selected per-token GEMMs run in ("fp6": scail_dit_enable_fp6, OCP MXFP6 e2m3)
+GEMM_PRECISIONS = ("fp8", "fp6")
 # include/scail_dit.h SCAIL_DIT_CACHE_*: the modes of scail_dit_step_cached; the signals of scail_dit_time_distances
 CACHE_MODES = {"fill": 1, "reuse": 2}
 CACHE_SIGNALS = {"time": 0, "modulation": 1}
@@ -174,7 +182,8 @@ ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- sc
                          # scail_dit_fp8_select_layers / scail_dit_fp8_probe / scail_dit_fp8_probe_bytes, and MX block scaling,
                          # scail_quant_mxfp8_rows / scail_gemm_mxfp8 / scail_dit_fp8_weight_bytes_scaled / scail_dit_enable_fp8_scaled,
                          # and the step cache, scail_resid_store / scail_resid_apply / scail_abs_diff_sums / scail_dit_step_cache_bytes /
-                         # scail_dit_step_cached / scail_dit_sample_cached / scail_dit_time_distances / scail_dit_time_distances_bytes)
+                         # scail_dit_step_cached / scail_dit_sample_cached / scail_dit_time_distances / scail_dit_time_distances_bytes,
+                         # and the 6-bit GEMMs, scail_quant_mxfp6_rows / scail_gemm_mxfp6 / scail_dit_fp6_weight_bytes / scail_dit_enable_fp6)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);

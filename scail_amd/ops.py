@@ -248,6 +248,61 @@ def gemm_mxfp8(xq, ex, wq, ew, bias=None, out=None, epilogue=L.EPI_BIAS, resid=N
     return out
 
 
+def quant_mxfp6_rows(x, out=None, scale=None):
+    """MXFP6 block quantization (include/scail_hip.h scail_quant_mxfp6_rows): x (..., C) bf16, C % 32 == 0 -> (packed e2m3 codes uint8
+    (rows, 3 C / 4): code j of a block in bits [6 j, 6 j + 6) of its 24 bytes; E8M0 scales uint8 (rows, C / 32))."""
+    _chk(x, bf16, "quant_mxfp6_rows.x")
+    R, C, ldx = _rowmajor2d(x, "quant_mxfp6_rows.x")
+    if out is None:
+        out = torch.empty(R, C // 4 * 3, device=x.device, dtype=torch.uint8)
+    if scale is None:
+        scale = torch.empty(R, C // 32, device=x.device, dtype=torch.uint8)
+    _chk(out, torch.uint8, "quant_mxfp6_rows.out"); _chk(scale, torch.uint8, "quant_mxfp6_rows.scale")
+    Ro, Co, ldq = _rowmajor2d(out, "quant_mxfp6_rows.out")
+    Rs, Cs, lde = _rowmajor2d(scale, "quant_mxfp6_rows.scale")
+    assert Ro == R and Co * 4 == C * 3 and Rs == R and Cs * 32 == C, (R, C, Ro, Co, Rs, Cs)
+    L.call("scail_quant_mxfp6_rows", x.data_ptr(), ldx, out.data_ptr(), ldq, scale.data_ptr(), lde, R, C, _stream())
+    return out, scale
+
+
+def gemm_mxfp6(xq, ex, wq, ew, bias=None, out=None, epilogue=L.EPI_BIAS, resid=None, gate=None, rows_per_batch=0):
+    """gemm_mxfp8 on packed e2m3 operands (include/scail_hip.h scail_gemm_mxfp6): xq (M, 3 K / 4) / wq (N, 3 K / 4) packed codes and ex
+    (M, K / 32) / ew (N, K / 32) E8M0 bytes (uint8, from quant_mxfp6_rows; wq and ew contiguous); bias, out, resid, gate as for gemm()."""
+    _chk(xq, torch.uint8, "gemm_mxfp6.xq"); _chk(wq, torch.uint8, "gemm_mxfp6.wq")
+    _chk(ex, torch.uint8, "gemm_mxfp6.ex"); _chk(ew, torch.uint8, "gemm_mxfp6.ew")
+    M, Kb, lda = _rowmajor2d(xq, "gemm_mxfp6.xq")
+    if Kb % 3 != 0:
+        raise L.ScailHipError(f"gemm_mxfp6: xq rows are 3 K / 4 bytes, got {Kb}")
+    K = Kb // 3 * 4
+    N = wq.shape[0]
+    if wq.shape[1] != Kb or not wq.is_contiguous():
+        raise L.ScailHipError("gemm_mxfp6: wq must be contiguous (N, 3 K / 4)")
+    Me, Ke, ldex = _rowmajor2d(ex, "gemm_mxfp6.ex")
+    if tuple(ew.shape) != (N, K // 32) or not ew.is_contiguous():
+        raise L.ScailHipError("gemm_mxfp6: ew must be contiguous (N, K / 32)")
+    assert Me == M and Ke * 32 == K, (M, K, Me, Ke)
+    if out is None:
+        out = torch.empty(M, N, device=xq.device, dtype=bf16)
+    _chk(out, bf16, "gemm_mxfp6.out")
+    Mo, No, ldc = _rowmajor2d(out, "gemm_mxfp6.out")
+    assert Mo == M and No == N, (Mo, M, No, N)
+    ldr = 0
+    if resid is not None:
+        _chk(resid, bf16, "gemm_mxfp6.resid")
+        Mr, Nr, ldr = _rowmajor2d(resid, "gemm_mxfp6.resid")
+        assert Mr == M and Nr == N
+    gs = 0
+    if gate is not None:
+        _chk(gate, f32, "gemm_mxfp6.gate")
+        assert gate.dim() == 2 and gate.shape[1] == N and gate.stride(1) == 1
+        gs = gate.stride(0)
+    if bias is not None:
+        _chk(bias, f32, "gemm_mxfp6.bias")
+    L.call("scail_gemm_mxfp6", xq.data_ptr(), lda, ex.data_ptr(), ldex, wq.data_ptr(), ew.data_ptr(), _ptr(bias), out.data_ptr(), ldc,
+           M, N, K, epilogue, _ptr(resid), ldr, _ptr(gate), gs, rows_per_batch, _stream())
+    return out
+
+
 def ln_modulate(x, shift, scale, out=None, eps=1e-6, rows_out=None, src_rows_per_batch=None, src_row_offset=0):
     """x (B, Ls, D) bf16; shift/scale fp32 (B, D) views (same row stride).  Output (B, rows_out, D)."""
     _chk(x, bf16, "ln_modulate.x"); _chk(shift, f32, "shift"); _chk(scale, f32, "scale")

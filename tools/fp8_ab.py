@@ -12,7 +12,9 @@
 (scail_quant_mxfp8_rows + scail_gemm_mxfp8, E8M0 per 32 along K), or both, alternating with bf16 in the same rounds; every leg follows it,
 and with both the MX figures are also given relative to the per-row arm of the same process (ratio of medians, and its min - max range
 from max / min and min / max of the two arms).
-Usage: python tools/fp8_ab.py [--reps 10] [--layers 40] [--no-step] [--no-gemm] [--mask 63] [--probe] [--scaling row|mx|both]
+--fp6 adds the 6-bit arm (scail_quant_mxfp6_rows + scail_gemm_mxfp6, scail_dit_enable_fp6: packed OCP e2m3 with E8M0 block scales) to every
+leg, alternating with the others in the same rounds; its times are also given relative to the per-row and the MX fp8 arms of the run.
+Usage: python tools/fp8_ab.py [--reps 10] [--layers 40] [--no-step] [--no-gemm] [--mask 63] [--probe] [--scaling row|mx|both] [--fp6]
 Prints one line per measurement and a JSON summary line last."""
 from __future__ import annotations
 
@@ -65,7 +67,7 @@ def _vs_row(row, mx):
     return {"median": mx["median_ms"] / row["median_ms"], "range": [mx["min_ms"] / row["max_ms"], mx["max_ms"] / row["min_ms"]]}
 
 
-def gemm_leg(reps, dev, scalings=("row",)):
+def gemm_leg(reps, dev, scalings=("row",), fp6=False):
     res = []
     g = torch.Generator(device=dev).manual_seed(0)
     for N, K in SHAPES:
@@ -84,16 +86,21 @@ def gemm_leg(reps, dev, scalings=("row",)):
             wm, ew = ops.quant_mxfp8_rows(w)
             arms["mx"] = lambda: ops.gemm_mxfp8(xm, ex, wm, ew, b, out=y)
             arms["quant_mx"] = lambda: ops.quant_mxfp8_rows(x, out=xm, scale=ex)
+        if fp6:
+            x6, e6 = ops.quant_mxfp6_rows(x)
+            w6, f6 = ops.quant_mxfp6_rows(w)
+            arms["fp6"] = lambda: ops.gemm_mxfp6(x6, e6, w6, f6, b, out=y)
+            arms["quant_fp6"] = lambda: ops.quant_mxfp6_rows(x, out=x6, scale=e6)
         ts = ab(arms, reps)
         flop = 2.0 * M14B * N * K
         r = {"N": N, "K": K, "M": M14B, "kernel_bf16": L.load().scail_gemm_kernel_for(K, N, 0, M14B, N, K, 0)}
-        for k in ("bf16", "fp8", "mx"):
+        for k in ("bf16", "fp8", "mx", "fp6"):
             if k in ts:
                 s = _summ(ts[k])
                 r[k] = dict(s, tflops=flop / s["median_ms"] / 1e9, tflops_range=[flop / s["max_ms"] / 1e9, flop / s["min_ms"] / 1e9])
         line = f"GEMM {N:5d} x {K:5d} (M {M14B}): bf16 {r['bf16']['tflops']:7.1f} TF ({r['bf16']['median_ms']:.3f} ms)"
-        # bytes of a quantization pass: bf16 read + e4m3 write + the scales (4 per row, or 1 per 32 columns)
-        for k, qk, sbytes in (("fp8", "quant", M14B * 4), ("mx", "quant_mx", M14B * K // 32)):
+        # bytes of a quantization pass: bf16 read + e4m3 write + the scales (4 per row, or 1 per 32 columns); fp6 writes 3/4 byte per code
+        for k, qk, sbytes in (("fp8", "quant", M14B * 4), ("mx", "quant_mx", M14B * K // 32), ("fp6", "quant_fp6", M14B * K // 32 - M14B * K // 4)):
             if k not in ts:
                 continue
             r[k]["frac_mxfp8_peak"] = r[k]["tflops"] / PEAK_FP8_TF
@@ -107,15 +114,21 @@ def gemm_leg(reps, dev, scalings=("row",)):
             v = r["mx_time_over_row"]
             line += (f";  mx / row time: GEMM {v['gemm']['median']:.3f} [{v['gemm']['range'][0]:.3f}, {v['gemm']['range'][1]:.3f}], "
                      f"quant {v['quant']['median']:.3f} [{v['quant']['range'][0]:.3f}, {v['quant']['range'][1]:.3f}]")
+        if "fp6" in ts:
+            r["fp6_time_over"] = {o: {"gemm": _vs_row(r[o], r["fp6"]), "quant": _vs_row(r[q], r["quant_fp6"])}
+                                  for o, q in (("fp8", "quant"), ("mx", "quant_mx")) if o in ts}
+            for o, v in r["fp6_time_over"].items():
+                line += (f";  fp6 / {o} time: GEMM {v['gemm']['median']:.3f} [{v['gemm']['range'][0]:.3f}, {v['gemm']['range'][1]:.3f}], "
+                         f"quant {v['quant']['median']:.3f} [{v['quant']['range'][0]:.3f}, {v['quant']['range'][1]:.3f}]")
         print(line, flush=True)
         res.append(r)
         del x, w, y, arms
-        xq = wq = xm = wm = None
+        xq = wq = xm = wm = x6 = w6 = None
         torch.cuda.empty_cache()
     return res
 
 
-def step_leg(reps, layers, mask, dev, scalings=("row",)):
+def step_leg(reps, layers, mask, dev, scalings=("row",), fp6=False):
     from scail_amd.cstep import CStep
     from scail_amd.dit import DiffusionTransformer
     from scail_amd.sampler import make_flow_timesteps
@@ -137,13 +150,16 @@ def step_leg(reps, layers, mask, dev, scalings=("row",)):
 
     def run(mode):
         if state.get("mode") != mode:
-            net._cstep.enable_fp8(0 if mode == "bf16" else mask, dev, scaling="mx" if mode == "mx" else "row")
+            if mode == "fp6":
+                net._cstep.enable_fp6(mask, dev)
+            else:
+                net._cstep.enable_fp8(0 if mode == "bf16" else mask, dev, scaling="mx" if mode == "mx" else "row")
             torch.cuda.synchronize()
             state["mode"] = mode
         return net.forward_f32(xin, t, ctx, None, concat_images=dummy, ref_concat=ref, concat_smpl_render=pose, image_clip_features=clip,
                                cfg_pair=True)
 
-    modes = ["bf16"] + [{"row": "fp8", "mx": "mx"}[s] for s in scalings]
+    modes = ["bf16"] + [{"row": "fp8", "mx": "mx"}[s] for s in scalings] + (["fp6"] if fp6 else [])
     ref16 = run("bf16").float().flatten().double()
     cos = {m: float(torch.nn.functional.cosine_similarity(ref16, run(m).float().flatten().double(), dim=0)) for m in modes[1:]}
     del ref16
@@ -170,19 +186,25 @@ def step_leg(reps, layers, mask, dev, scalings=("row",)):
     if "fp8" in r and "mx" in r:
         r["mx_time_over_row"] = v = _vs_row(r["fp8"], r["mx"])
         line += f";  mx / row step time {v['median']:.3f} [{v['range'][0]:.3f}, {v['range'][1]:.3f}]"
+    if "fp6" in r:
+        r["fp6_time_over"] = {o: _vs_row(r[o], r["fp6"]) for o in ("fp8", "mx") if o in r}
+        for o, v in r["fp6_time_over"].items():
+            line += f";  fp6 / {o} step time {v['median']:.3f} [{v['range'][0]:.3f}, {v['range'][1]:.3f}]"
     print(line, flush=True)
     net._cstep.close()
     return r
 
 
 def probe_leg(layers, mask, dev, scaling="row"):
+    """scaling: "row" | "mx" (fp8) or "fp6" (the 6-bit form)"""
+    precision = "fp6" if scaling == "fp6" else "fp8"
     from scail_amd import cli
     from scail_amd.dit import DiffusionTransformer
     from scail_amd.sampler import make_flow_timesteps
     T, H, W, Lt, Lc = 21, 64, 112, 512, 257
     net = DiffusionTransformer(transformer_args=dict(model_parallel_size=1), num_frames=81, latent_width=300, latent_height=300,
-                               share_adaln=True, use_i2v_clip=True, device=dev, init_seed=1234, num_layers=layers, gemm_precision="fp8",
-                               fp8_gemms=mask, fp8_scaling=scaling, **P14B)
+                               share_adaln=True, use_i2v_clip=True, device=dev, init_seed=1234, num_layers=layers, gemm_precision=precision,
+                               fp8_gemms=mask, fp8_scaling="row" if precision == "fp6" else scaling, **P14B)
     g = torch.Generator().manual_seed(1234)
     x = torch.randn(1, T, 16, H, W, generator=g).to(dev)
     ref = torch.randn(1, 1, 16, H, W, generator=g).to(dev).to(torch.bfloat16)
@@ -198,7 +220,7 @@ def probe_leg(layers, mask, dev, scaling="row"):
     res = {}
     probe_ms = _time(lambda: res.update(zip(("rel_err", "worst"), net.fp8_probe(xin, t, ctx, None, **kw))))
     rel, worst = res["rel_err"], res["worst"]
-    print(cli.format_fp8_table(dict(rel_err=rel, masks=[mask] * layers, enabled=mask, scaling=scaling), float("inf")))
+    print(cli.format_fp8_table(dict(rel_err=rel, masks=[mask] * layers, enabled=mask, scaling=scaling, precision=precision), float("inf")))
     print("worst token row of each GEMM (same layout):")
     for i in range(layers):
         print(f"{i:5d} " + " ".join(f"{float(worst[i, k]):8.2e}" for k in range(6)))
@@ -208,7 +230,7 @@ def probe_leg(layers, mask, dev, scaling="row"):
          "rows_per_gemm": net.fp8_probe_table[:, :, 3].tolist()}
     print(f"probe at config-2 size ({layers} layers, mask {mask}, {scaling} scaling, random-init weights): relative error {r['rel_err_min']:.4f} .. {r['rel_err_max']:.4f}, "
           f"worst token row {r['worst_row_max']:.4f}; probed evaluation {probe_ms:.1f} ms (with the host read of the table) against "
-          f"{plain_ms:.1f} ms for a plain fp8 step", flush=True)
+          f"{plain_ms:.1f} ms for a plain {precision} step", flush=True)
     net._cstep.close()
     return r
 
@@ -224,17 +246,19 @@ def main():
     ap.add_argument("--probe", action="store_true", help="also print the GEMM error probe's table at config-2 size")
     ap.add_argument("--scaling", choices=("row", "mx", "both"), default="row",
                     help="fp8 arm(s): per-row fp32 scales, MX block scales (E8M0 per 32 along K), or both alternating with bf16")
+    ap.add_argument("--fp6", action="store_true", help="add the 6-bit (MXFP6 e2m3) arm to every leg")
     a = ap.parse_args()
     scalings = ("row", "mx") if a.scaling == "both" else (a.scaling,)
     dev = "cuda"
     L.load()
     out = {"device": torch.cuda.get_device_name(0)}
     if not a.no_gemm:
-        out["gemm"] = gemm_leg(a.reps, dev, scalings)
+        out["gemm"] = gemm_leg(a.reps, dev, scalings, a.fp6)
     if not a.no_step:
-        out["step"] = step_leg(a.step_reps, a.layers, a.mask, dev, scalings)
+        out["step"] = step_leg(a.step_reps, a.layers, a.mask, dev, scalings, a.fp6)
     if a.probe:
-        out["probe"] = {s: probe_leg(a.layers, a.mask, dev, s) for s in scalings} if a.scaling == "both" else probe_leg(a.layers, a.mask, dev, a.scaling)
+        legs = scalings + (("fp6",) if a.fp6 else ())
+        out["probe"] = {s: probe_leg(a.layers, a.mask, dev, s) for s in legs} if len(legs) > 1 else probe_leg(a.layers, a.mask, dev, legs[0])
     print(json.dumps(out))
 
 
