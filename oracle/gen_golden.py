@@ -17,6 +17,9 @@ parity tests use are outputs of the reference's own classes on seeded inputs:
                     (2-layer / 128-dim, 4x8x8 latent): final latent + the latents after steps 2 / 10 / 25 (the drift curve
                     of a bf16 network is measured against these)
   sampler_long_tiny.npz  RFSamplerLong (sampling.py:986-1085): 6-frame latent, three overlapping 4-frame tiles, 2 steps
+  dit_planted.npz   DiffusionTransformer.forward on the PLANTED network and inputs of tests/dit_wiring.py (the wiring tests: biases, gammas
+                    and tables at the scale of the activations, 456 tokens on an 8 x 12 patch grid); the hidden states are stored for
+                    every third token (rows 0, 3, 6, ...) to keep the file small.  `python oracle/gen_golden.py dit_planted` writes it alone
 """
 from __future__ import annotations
 
@@ -283,9 +286,44 @@ def gen_dit_shapes():
     return gen_dit_tiny("dit_shapes", O.TINY, tiny_inputs(seed=21, B=2, T=3, H=12, W=8, Lt=77, n_clip=129, n_cond=2))
 
 
+def gen_dit_planted():
+    """The real reference on the planted network of the wiring tests (tests/dit_wiring.py: weights and inputs are that module's seeded
+    draws, nothing of the reference's).  Hidden states: every third token."""
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import dit_wiring as DW
+    cfg = DW.planted_config()
+    sd = DW.planted_state_dict(cfg)
+    inp = DW.planted_inputs()
+    net = ref_shims.build_reference_dit(cfg, sd)
+    hidden = []
+    mix = net.mixins["adaln_layer"]
+    orig = mix.layer_forward
+
+    def tap(*a, **k):
+        o = orig(*a, **k)
+        hidden.append(o.detach().clone())
+        return o
+
+    mix.layer_forward = tap
+    net.collect_hooks_()
+    with torch.no_grad():
+        out = net(inp["x"], timesteps=inp["t"], context=inp["ctx"], concat_images=torch.zeros(1, *inp["x"].shape[1:]),
+                  ref_concat=inp["ref"], concat_smpl_render=inp["pose"], image_clip_features=inp["clip"])
+    del mix.layer_forward
+    net.collect_hooks_()
+    assert len(hidden) == cfg.num_layers
+    np.savez_compressed(os.path.join(OUT, "dit_planted.npz"), seed=DW.SEED, token_stride=DW.GOLDEN_TOKEN_STRIDE,
+                        **{k: v.numpy() for k, v in inp.items()}, out=out.numpy(),
+                        **{f"hidden{i + 1}": h[:, ::DW.GOLDEN_TOKEN_STRIDE].contiguous().numpy() for i, h in enumerate(hidden)})
+    print("dit_planted: out", tuple(out.shape), "abs-mean", float(out.abs().mean()))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
+    if sys.argv[1:] == ["dit_planted"]:
+        return gen_dit_planted()
+    gen_dit_planted()
     gen_dit_shapes()
     gen_rope_sp_w()
     gen_dit_tiny("dit_config1", O.CONFIG1)

@@ -34,6 +34,26 @@ def test_dit_forward_matches_reference(golden_dir, name, cfgd):
     torch.testing.assert_close(out, g["out"], rtol=2e-5, atol=2e-5)
 
 
+def test_dit_forward_matches_reference_on_the_planted_network(golden_dir):
+    """dit_planted.npz (oracle/gen_golden.py gen_dit_planted): the real reference on the planted network and inputs of the wiring tests
+    (tests/dit_wiring.py), where every bias, gamma, table and RoPE offset carries weight.  Recorded inputs and outputs only; the hidden
+    states are stored for every third token."""
+    import dit_wiring as DW
+    g = _load(golden_dir, "dit_planted.npz")
+    assert int(g["seed"]) == DW.SEED and int(g["token_stride"]) == DW.GOLDEN_TOKEN_STRIDE
+    cfg = DW.planted_config()
+    sd = DW.planted_state_dict(cfg)
+    inp = DW.planted_inputs()
+    for k in ("x", "t", "ctx", "ref", "pose", "clip"):
+        assert torch.equal(inp[k], g[k]), k                    # the seeded draw is the recorded one
+    out, hidden = O.dit_forward(cfg, sd, g["x"], g["t"], g["ctx"], g["ref"], g["pose"], g["clip"], return_hidden=True)
+    for i in range(cfg.num_layers):
+        torch.testing.assert_close(hidden[i + 1][:, ::DW.GOLDEN_TOKEN_STRIDE], g[f"hidden{i + 1}"], rtol=2e-5, atol=2e-5)
+    torch.testing.assert_close(out, g["out"], rtol=2e-5, atol=2e-5)
+    assert max(DW.e(hidden[i + 1][:, ::DW.GOLDEN_TOKEN_STRIDE], g[f"hidden{i + 1}"]) for i in range(cfg.num_layers)) < 2e-6
+    assert DW.e(out, g["out"]) < 2e-6
+
+
 def test_rope_tables_match_reference(golden_dir):
     g = _load(golden_dir, "rope_tiny.npz")
     cfg = O.DiTConfig(**O.TINY)
