@@ -408,9 +408,24 @@ int scail_dit_sample_tiled(scail_dit* h, float* x, const float* timesteps, const
  *   enqueues, nothing synchronises, and it is capturable on the same terms as scail_dit_sample.  An all-zero mask gives the bits of
  *   scail_dit_sample_chars.
  *
+ * scail_dit_sample_tiled_cached: scail_dit_sample_tiled + (reuse, cache, cache_bytes): the step cache for clips longer than one window.
+ *   The loop is scail_dit_sample_tiled's, exactly as stated there (gather, evaluation with SCAIL_DIT_CFG_PAIR, blend-accumulate in
+ *   ascending tile order, one scail_tile_finish per step), except that the evaluation of tile k at step i is scail_dit_step_cached on
+ *   tile k's OWN residual: in REUSE mode where reuse[i] == 1, else in FILL mode.  reuse = HOST uint8 [n_steps], read during the call, one
+ *   plan for every tile (it depends on the sigma schedule and the weights alone).  An all-zero mask gives the bits of
+ *   scail_dit_sample_tiled.  The workspace is that of scail_dit_sample_tiled (scail_dit_sample_tiled_workspace_bytes); nothing
+ *   synchronises, the call is capturable on the same terms, and quantised GEMMs work as under scail_dit_step_cached.
+ * scail_dit_sample_tiled_cache_bytes: bytes of its caller-owned, 256-byte aligned cache (-1: null handle, n_tiles outside 2..32767, Tt
+ *   outside 1..64, bad H / W).  With R and E the two regions of the step cache of a (2, Tt, H, W) evaluation above -- R = E =
+ *   2 * Lnoise * D * 2 bytes rounded up to 256, Lnoise = Tt (H/2) (W/2) -- it is NOT n_tiles step caches: FILL's copy of the embedded
+ *   noise rows is dead once scail_resid_store has run, so all tiles share one.  Layout: slabs of r [n_tiles][R] from offset 0 -- slab k
+ *   holds tile k's r bf16 [2][Lnoise][D] as its last FILL left it; callers may read it --, then one embedding region E:
+ *       scail_dit_sample_tiled_cache_bytes = n_tiles * R + E        (against n_tiles * (R + E) for stacked step caches)
+ *
  * Refused before anything is enqueued, with an error that names the value: a mode other than the two; a null cache, one smaller than
- * scail_dit_step_cache_bytes, one that is not 256-byte aligned; reuse == NULL with n_steps > 0; reuse[0] != 0 (the first step has nothing
- * to reuse); an entry other than 0 or 1.  The checks that need no handle come first.
+ * scail_dit_step_cache_bytes (tiled: scail_dit_sample_tiled_cache_bytes), one that is not 256-byte aligned; reuse == NULL with
+ * n_steps > 0; reuse[0] != 0 (the first step has nothing to reuse); an entry other than 0 or 1.  The checks that need no handle come
+ * first.  scail_dit_sample_tiled_cached also refuses everything scail_dit_sample_tiled refuses, in its wording, and n_tiles >= 32768.
  *
  * scail_dit_time_distances: for the DEVICE fp32 timesteps [n_steps] (= 1000 sigma_i) the handle's own time embedding of every step, by
  *   the very calls of a step (scail_timestep_embedding, scail_small_linear; scail_small_linear takes at most 8 rows, so in chunks of 8
@@ -421,8 +436,8 @@ int scail_dit_sample_tiled(scail_dit* h, float* x, const float* timesteps, const
  *   synchronises: the host reads the table after the stream has finished.  Refused before anything is enqueued: an unknown signal, n_steps
  *   outside 0 .. 2^20 - 1 (both named), a null handle / pointer, a scratch that is too small or misaligned.
  *
- * Out of scope, each because no *_cached entry point exists for it: the tiled loop (scail_dit_sample_tiled; a follow-up can give it one
- * cache per tile), the sequence-parallel calls (scail_dit_step_sp*), and the per-block seam (scail_dit_block*).
+ * Out of scope, each because no *_cached entry point exists for it: the sequence-parallel calls (scail_dit_step_sp*), the per-block
+ * seam (scail_dit_block*), and tiles with several characters (scail_dit_sample_tiled takes one character per request).
  */
 #define SCAIL_DIT_CACHE_FILL 1
 #define SCAIL_DIT_CACHE_REUSE 2
@@ -436,6 +451,12 @@ int scail_dit_sample_cached(scail_dit* h, float* x, const float* timesteps, cons
                             const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose, int64_t n_char, int64_t pose_frames,
                             const float* rope_cos, const float* rope_sin, int64_t T, int64_t H, int64_t W,
                             void* workspace, int64_t workspace_bytes, const uint8_t* reuse, void* cache, int64_t cache_bytes, void* stream);
+int64_t scail_dit_sample_tiled_cache_bytes(const scail_dit* h, int64_t n_tiles, int64_t Tt, int64_t H, int64_t W);
+int scail_dit_sample_tiled_cached(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                                  const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose_tiles,
+                                  const int32_t* tile_frames, const float* tile_w, const float* inv_wsum, int64_t n_tiles, int64_t T, int64_t Tt,
+                                  const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
+                                  const uint8_t* reuse, void* cache, int64_t cache_bytes, void* stream);
 int64_t scail_dit_time_distances_bytes(const scail_dit* h, int signal);
 int scail_dit_time_distances(scail_dit* h, const float* timesteps, int64_t n_steps, int signal, double* out, void* scratch,
                              int64_t scratch_bytes, void* stream);

@@ -319,7 +319,8 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     """``fp8_max_error`` (fp8 networks only): probe the request's first evaluation and keep in bf16 every (layer, GEMM) whose fp8 result is
     further than this from bf16 (engine.calibrate_fp8).
     ``step_cache``: None, or the step-cache option (step_cache_args; RFSampler.sample_hip): steps whose time embedding moved little reuse the
-    block residual of the last computed step.  One window, one rank; the plan is printed.
+    block residual of the last computed step.  One rank; a clip longer than one window keeps one residual per temporal tile under one
+    plan.  The plan is printed.
     ``postprocess``: "torch" (default) returns the video as fp32 (B, 3, T, H, W) in [0, 1]; "hip" returns it as the file writers' pixels,
     uint8 (B, T, H, W, 3) on the device, written by the VAE decoder's last kernel (engine.decode_first_stage_u8; needs a GPU)."""
     if postprocess not in POSTPROCESS_ROUTES:
@@ -341,12 +342,9 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     if n_pix > (net.num_frames if tile_frames is None else tile_frames):      # longer than one window: temporal tiles (an extension)
         if (n_pix - 1) % 4:
             raise ValueError(f"a pose clip longer than one window needs 4n + 1 frames (the causal VAE's frame groups), got {n_pix}")
-        if step_cache is not None:
-            raise NotImplementedError("--step-cache-threshold is not combined with temporal tiles (a pose clip longer than one window): the tiled "
-                                      "loop has no cached form")
         Tt, overlap = tile_args(tile_frames, tile_overlap, net.num_frames)
         tiles = plan_tiles((n_pix - 1) // 4 + 1, Tt, overlap)
-        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames, postprocess, fp8_max_error)
+        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames, postprocess, fp8_max_error, step_cache)
     pose_lat = engine.encode_first_stage(req["pose"].unsqueeze(0), None, force_encode=True)   # already half resolution (:350-351)
     ref_concat = ref_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)      # B C T H W -> B T C H W
     pose_latent = pose_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)
@@ -382,10 +380,12 @@ def _finish(engine, z, t0, vae_chunk_frames=None, postprocess="torch"):
     return video, z, time.perf_counter() - t0
 
 
-def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames=None, postprocess="torch", fp8_max_error=None):
+def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames=None, postprocess="torch", fp8_max_error=None,
+               step_cache=None):
     """A pose clip longer than one window (an extension, see the module docstring): RFSamplerLong with the configured sampler's
     parameters over ``tiles``; every window's pose frames [4 start, 4 (start + Tt - 1)] are VAE-encoded on their own (the causal VAE treats
-    a window's first frame as a clip's first frame, which is how ``smpl_tiled[:, k]`` is used); noise and decode for the whole latent."""
+    a window's first frame as a clip's first frame, which is how ``smpl_tiled[:, k]`` is used); noise and decode for the whole latent.
+    ``step_cache``: as for ``run`` -- one plan shared by the tiles, one residual per tile (RFSamplerLong.sample_hip); the plan is printed."""
     from . import sampler as S
     Tt = len(tiles[0])
     ref_concat = ref_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)
@@ -405,7 +405,11 @@ def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_ch
     try:
         _calibrate(engine, c, uc, (T, C, h, w), steps, fp8_max_error)       # the first window
         torch.manual_seed(seed)
-        z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, tile_indices=tiles)
+        if step_cache is None:
+            z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, tile_indices=tiles)
+        else:
+            z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, tile_indices=tiles, step_cache=step_cache)
+            print(format_step_cache_plan(engine.sampler.last_step_cache_plan))
     finally:
         engine.sampler = plain
     return _finish(engine, z, t0, vae_chunk_frames, postprocess)
@@ -452,7 +456,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "computed step, and runs only the patch embedding and the final layer, while the accumulated relative change of the "
                          "time embedding since that step stays below this number; 0 computes every step.  The plan is printed.  No value is "
                          "recommended: nothing has been measured on real weights, and random-init weights say nothing about quality.  "
-                         "Single GPU, one window")
+                         "Single GPU.  A pose clip longer than one window (--tile-frames) keeps one such change per temporal window under "
+                         "one plan for all of them")
     ap.add_argument("--step-cache-coefficients", default=None,
                     help="with --step-cache-threshold: polynomial applied to each step's relative change before it is accumulated, "
                          "comma-separated, highest degree first (default 1,0: the identity).  No fitted values are shipped")

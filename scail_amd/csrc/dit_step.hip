@@ -299,6 +299,14 @@ static CacheWs cache_ws(const scail_dit_config& c, int64_t B, int64_t Lnoise) {
     s.total = cv.off;
     return s;
 }
+// the two regions of one step cache, as dit_step_impl takes them
+struct CachePtrs {
+    scail_bf16 *r, *emb;
+};
+static CachePtrs cache_ptrs(const scail_dit_config& c, int64_t B, int64_t Lnoise, void* cache) {
+    const CacheWs cw = cache_ws(c, B, Lnoise);
+    return {reinterpret_cast<scail_bf16*>(static_cast<char*>(cache) + cw.r), reinterpret_cast<scail_bf16*>(static_cast<char*>(cache) + cw.emb)};
+}
 
 // x quantised into the block's scratch and multiplied with the quantised weight f, under the handle's scaling
 static int fp8_quant_gemm(const scail_dit* h, const scail_dit::Fp8W& f, const BlockBufs& bf, const scail_bf16* x, int64_t lda, const float* bias,
@@ -905,7 +913,7 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
                          const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
                          const float* rope_cos, const float* rope_sin, float* out,
                          int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace, int64_t workspace_bytes,
-                         void* stream, int mode = CACHE_NONE, void* cache = nullptr) {
+                         void* stream, int mode = CACHE_NONE, scail_bf16* cache_r = nullptr, scail_bf16* cache_emb = nullptr) {
     DIT_TRY(chars_check("scail_dit_step", n_char, pose_frames, T));
     const bool reuse = mode == SCAIL_DIT_CACHE_REUSE;      // no block runs: the conditioning is not read
     SCAIL_REQUIRE(h != nullptr && (cond != nullptr || reuse), "null handle / conditioning");
@@ -964,11 +972,9 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
     } else {
         DIT_TRY(scail_patchify_chars(x, ref, pose, tok, Be, n_ref, n_pose, n_char, T, H, W, KPAD, stream));
     }
-    // the step cache (include/scail_dit.h "step cache"): r = what the blocks added to the noise rows at the last FILL, and FILL's copy of
-    // the embedded noise rows (the blocks work in place on hid)
-    const CacheWs cw = cache_ws(c, B, Lnoise);
-    scail_bf16* cache_r = mode == CACHE_NONE ? nullptr : reinterpret_cast<scail_bf16*>(static_cast<char*>(cache) + cw.r);
-    scail_bf16* cache_emb = mode == CACHE_NONE ? nullptr : reinterpret_cast<scail_bf16*>(static_cast<char*>(cache) + cw.emb);
+    // the step cache (include/scail_dit.h "step cache"): cache_r = what the blocks added to the noise rows at the last FILL, cache_emb =
+    // FILL's copy of the embedded noise rows (the blocks work in place on hid), dead once scail_resid_store has run; the caller places
+    // the two (cache_ptrs: one cache; scail_dit_sample_tiled_cached: a slab of r per tile and one shared embedding region)
     scail_bf16* hid_noise = hid + Lref * D;
     if (reuse) {
         // the noise rows of the patch embedding only (every GEMM row comes from its own input row: the bits of the full embedding), plus
@@ -1088,6 +1094,7 @@ static int sample_impl(scail_dit* h, float* x, const float* timesteps, const flo
     float *xin = reinterpret_cast<float*>(base + ws.xin), *v = reinterpret_cast<float*>(base + ws.v);
     const int64_t n = T * 16 * H * W;
     hipStream_t s = (hipStream_t)stream;
+    const CachePtrs cp = reuse == nullptr ? CachePtrs{nullptr, nullptr} : cache_ptrs(h->cfg, 2, tok_lens(1, T, H, W).Lnoise, cache);
     for (int64_t i = 0; i < n_steps; ++i) {
         // torch.cat([x] * 2) of VanillaCFG.prepare_inputs (guiders.py:56)
         if (hipMemcpyAsync(xin, x, n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
@@ -1097,7 +1104,7 @@ static int sample_impl(scail_dit* h, float* x, const float* timesteps, const flo
         }
         const int mode = reuse == nullptr ? CACHE_NONE : reuse[i] ? SCAIL_DIT_CACHE_REUSE : SCAIL_DIT_CACHE_FILL;
         DIT_TRY(dit_step_impl(h, xin, timesteps + 2 * i, cond, ref, 1, pose, 1, n_char, pose_frames, rope_cos, rope_sin, v, 2, T, H, W, nullptr,
-                              SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream, mode, cache));
+                              SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream, mode, cp.r, cp.emb));
         DIT_TRY(scail_cfg_euler(x, v, n, cfg_scale, dsigma[i], stream));
     }
     return 0;
@@ -1115,23 +1122,48 @@ extern "C" int64_t scail_dit_step_cache_bytes(const scail_dit* h, int64_t B, int
     if (h == nullptr || shape_fault(B, T, H, W, 1, 1) != 0) return -1;
     return cache_ws(h->cfg, B, tok_lens(1, T, H, W).Lnoise).total;
 }
-// mode and cache of a *_cached call, before anything is enqueued: what needs no handle first (the message names the value)
+extern "C" int64_t scail_dit_sample_tiled_cache_bytes(const scail_dit* h, int64_t n_tiles, int64_t Tt, int64_t H, int64_t W) {
+    if (h == nullptr || n_tiles < 2 || n_tiles >= (1 << 15) || Tt > 64 || shape_fault(2, Tt, H, W, 1, 1) != 0) return -1;
+    const CacheWs cw = cache_ws(h->cfg, 2, tok_lens(1, Tt, H, W).Lnoise);
+    return n_tiles * cw.emb + (cw.total - cw.emb);      // [n_tiles][R] slabs of r, then one embedding region E
+}
+// mode and cache of a *_cached call, before anything is enqueued: what needs no handle first (the message names the value).
+// n_tiles = 0: the cache of one (B, T, H, W) evaluation, else the tiled sampler's (n_tiles slabs of r + one embedding region, B = 2)
 static int cache_check(const char* who, const scail_dit* h, int mode, bool need_mode, const void* cache, int64_t cache_bytes, int64_t B, int64_t T,
-                       int64_t H, int64_t W) {
+                       int64_t H, int64_t W, int64_t n_tiles = 0) {
+    const char* query = n_tiles ? "scail_dit_sample_tiled_cache_bytes" : "scail_dit_step_cache_bytes";
     auto fail = [&](const std::string& msg) {
         scail_set_error(std::string(who) + ": " + msg);
         return 1;
     };
     if (need_mode && mode != SCAIL_DIT_CACHE_FILL && mode != SCAIL_DIT_CACHE_REUSE)
         return fail("unknown cache mode " + std::to_string(mode) + " (SCAIL_DIT_CACHE_FILL = 1 or SCAIL_DIT_CACHE_REUSE = 2)");
-    if (cache == nullptr) return fail("null cache (cache_bytes " + std::to_string(cache_bytes) + "; scail_dit_step_cache_bytes)");
+    if (cache == nullptr) return fail("null cache (cache_bytes " + std::to_string(cache_bytes) + "; " + query + ")");
     if ((reinterpret_cast<uintptr_t>(cache) & 255) != 0)
         return fail("the cache must be 256-byte aligned, got an address that is " + std::to_string(reinterpret_cast<uintptr_t>(cache) & 255) + " past a multiple of 256");
     if (h == nullptr) return fail("null handle");
-    const int64_t need = scail_dit_step_cache_bytes(h, B, T, H, W);
+    const int64_t need = n_tiles ? scail_dit_sample_tiled_cache_bytes(h, n_tiles, T, H, W) : scail_dit_step_cache_bytes(h, B, T, H, W);
     if (need < 0) return fail("bad latent shape (B " + std::to_string(B) + ", T " + std::to_string(T) + ", H " + std::to_string(H) + ", W " + std::to_string(W) + ")");
     if (cache_bytes < need)
-        return fail("cache too small: " + std::to_string(cache_bytes) + " bytes, needs " + std::to_string(need) + " (scail_dit_step_cache_bytes)");
+        return fail("cache too small: " + std::to_string(cache_bytes) + " bytes, needs " + std::to_string(need) + " (" + query + ")");
+    return 0;
+}
+// the plan of a sampler loop with a step cache: host uint8 [n_steps], 0 = compute (FILL) or 1 = REUSE, the first step computes
+static int reuse_check(const char* who, const uint8_t* reuse, int64_t n_steps) {
+    if (n_steps <= 0) return 0;
+    if (reuse == nullptr) {
+        scail_set_error(std::string(who) + ": null reuse mask with n_steps = " + std::to_string(n_steps));
+        return 1;
+    }
+    for (int64_t i = 0; i < n_steps; ++i)
+        if (reuse[i] > 1) {
+            scail_set_error(std::string(who) + ": reuse[" + std::to_string(i) + "] = " + std::to_string((int)reuse[i]) + " (an entry is 0 = compute or 1 = reuse)");
+            return 1;
+        }
+    if (reuse[0] != 0) {
+        scail_set_error(std::string(who) + ": reuse[0] = " + std::to_string((int)reuse[0]) + ": the first step has nothing to reuse, it must compute");
+        return 1;
+    }
     return 0;
 }
 extern "C" int scail_dit_step_cached(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond,
@@ -1140,8 +1172,9 @@ extern "C" int scail_dit_step_cached(scail_dit* h, const float* x, const float* 
                                      int64_t B, int64_t T, int64_t H, int64_t W, uint32_t flags, void* workspace, int64_t workspace_bytes,
                                      int mode, void* cache, int64_t cache_bytes, void* stream) {
     DIT_TRY(cache_check("scail_dit_step_cached", h, mode, true, cache, cache_bytes, B, T, H, W));
+    const CachePtrs cp = cache_ptrs(h->cfg, B, tok_lens(1, T, H, W).Lnoise, cache);
     return dit_step_impl(h, x, timesteps, cond, ref, n_ref, pose, n_pose, n_char, pose_frames, rope_cos, rope_sin, out, B, T, H, W, nullptr, flags,
-                         workspace, workspace_bytes, stream, mode, cache);
+                         workspace, workspace_bytes, stream, mode, cp.r, cp.emb);
 }
 extern "C" int scail_dit_sample_cached(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps,
                                        float cfg_scale, const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose,
@@ -1149,21 +1182,7 @@ extern "C" int scail_dit_sample_cached(scail_dit* h, float* x, const float* time
                                        int64_t T, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
                                        const uint8_t* reuse, void* cache, int64_t cache_bytes, void* stream) {
     const char* who = "scail_dit_sample_cached";
-    if (n_steps > 0) {
-        if (reuse == nullptr) {
-            scail_set_error(std::string(who) + ": null reuse mask with n_steps = " + std::to_string(n_steps));
-            return 1;
-        }
-        for (int64_t i = 0; i < n_steps; ++i)
-            if (reuse[i] > 1) {
-                scail_set_error(std::string(who) + ": reuse[" + std::to_string(i) + "] = " + std::to_string((int)reuse[i]) + " (an entry is 0 = compute or 1 = reuse)");
-                return 1;
-            }
-        if (reuse[0] != 0) {
-            scail_set_error(std::string(who) + ": reuse[0] = " + std::to_string((int)reuse[0]) + ": the first step has nothing to reuse, it must compute");
-            return 1;
-        }
-    }
+    DIT_TRY(reuse_check(who, reuse, n_steps));
     DIT_TRY(cache_check(who, h, 0, false, cache, cache_bytes, 2, T, H, W));
     return sample_impl(h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose, n_char, pose_frames, rope_cos, rope_sin, T, H, W, workspace,
                        workspace_bytes, stream, reuse, cache);
@@ -1242,12 +1261,14 @@ extern "C" int64_t scail_dit_sample_tiled_workspace_bytes(const scail_dit* h, in
     return step < 0 ? -1 : sample_ws(step, Tt, H, W, T).total;
 }
 
-extern "C" int scail_dit_sample_tiled(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
-                                      const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose_tiles,
-                                      const int32_t* tile_frames, const float* tile_w, const float* inv_wsum, int64_t n_tiles, int64_t T, int64_t Tt,
-                                      const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
-                                      void* stream) {
-    const char* who = "scail_dit_sample_tiled";
+// the tiled loop; cached = false: every evaluation a plain one (scail_dit_sample_tiled), else tile k's evaluation of step i in
+// SCAIL_DIT_CACHE_REUSE mode where reuse[i] != 0 and in SCAIL_DIT_CACHE_FILL mode otherwise, on slab k of the cache
+// (scail_dit_sample_tiled_cached)
+static int sample_tiled_impl(const char* who, scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                             const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose_tiles,
+                             const int32_t* tile_frames, const float* tile_w, const float* inv_wsum, int64_t n_tiles, int64_t T, int64_t Tt,
+                             const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
+                             void* stream, bool cached, const uint8_t* reuse, void* cache, int64_t cache_bytes) {
     auto fail = [&](const std::string& msg) {
         scail_set_error(std::string(who) + ": " + msg);
         return 1;
@@ -1277,6 +1298,11 @@ extern "C" int scail_dit_sample_tiled(scail_dit* h, float* x, const float* times
     if (workspace_bytes < own)
         return fail("workspace too small: " + std::to_string(workspace_bytes) + " bytes cannot hold the tile pair buffers and den (" +
                     std::to_string(own) + " bytes) next to the step workspace (scail_dit_sample_tiled_workspace_bytes)");
+    if (cached) {
+        if (n_tiles >= (1 << 15)) return fail("a cached tiled loop takes fewer than 32768 tiles, got n_tiles = " + std::to_string(n_tiles));
+        DIT_TRY(reuse_check(who, reuse, n_steps));
+        DIT_TRY(cache_check(who, h, 0, false, cache, cache_bytes, 2, Tt, H, W, n_tiles));
+    }
     const void* ptrs[] = {h, x, timesteps, dsigma, cond, ref, pose_tiles, rope_cos, rope_sin, workspace};
     const char* names[] = {"handle", "x", "timesteps", "dsigma", "cond", "ref", "pose_tiles", "rope_cos", "rope_sin", "workspace"};
     for (int i = 0; i < 10; ++i)
@@ -1293,17 +1319,39 @@ extern "C" int scail_dit_sample_tiled(scail_dit* h, float* x, const float* times
     char* base = static_cast<char*>(workspace);
     float *xin = reinterpret_cast<float*>(base + ws.xin), *v = reinterpret_cast<float*>(base + ws.v), *den = reinterpret_cast<float*>(base + ws.den);
     const int64_t F = 16 * H * W, pose_tile = Tt * 16 * (H / 2) * (W / 2);
+    // the cache (include/scail_dit.h): tile k's residual in slab k of R bytes, then the one embedding region every FILL uses in turn
+    const int64_t R = cache_ws(h->cfg, 2, tok_lens(1, Tt, H, W).Lnoise).emb;
+    char* slabs = static_cast<char*>(cache);
+    scail_bf16* cache_emb = cached ? reinterpret_cast<scail_bf16*>(slabs + n_tiles * R) : nullptr;
     // den starts at zero; scail_tile_finish leaves it zeroed for the next step
     if (n_steps > 0) DIT_TRY(scail_zero_f32(den, T * F, stream));
     for (int64_t i = 0; i < n_steps; ++i) {
+        const int mode = !cached ? CACHE_NONE : reuse[i] ? SCAIL_DIT_CACHE_REUSE : SCAIL_DIT_CACHE_FILL;
         for (int64_t k = 0; k < n_tiles; ++k) {      // ascending, the order of the host loop: the accumulation order is part of the result
             const int32_t* fr = tile_frames + k * Tt;
             DIT_TRY(scail_tile_gather(x, xin, fr, Tt, T, F, stream));
-            DIT_TRY(scail_dit_step_chars(h, xin, timesteps + 2 * i, cond, ref, 1, pose_tiles + k * pose_tile, 1, 1, Tt, rope_cos, rope_sin, v, 2, Tt, H,
-                                         W, SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream));
+            DIT_TRY(dit_step_impl(h, xin, timesteps + 2 * i, cond, ref, 1, pose_tiles + k * pose_tile, 1, 1, Tt, rope_cos, rope_sin, v, 2, Tt, H, W,
+                                  nullptr, SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream, mode,
+                                  cached ? reinterpret_cast<scail_bf16*>(slabs + k * R) : nullptr, cache_emb));
             DIT_TRY(scail_tile_blend_acc(den, v, fr, tile_w + k * Tt, Tt, T, F, cfg_scale, stream));
         }
         DIT_TRY(scail_tile_finish(x, den, inv_wsum, T, F, dsigma[i], stream));
     }
     return 0;
+}
+extern "C" int scail_dit_sample_tiled(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                                      const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose_tiles,
+                                      const int32_t* tile_frames, const float* tile_w, const float* inv_wsum, int64_t n_tiles, int64_t T, int64_t Tt,
+                                      const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
+                                      void* stream) {
+    return sample_tiled_impl("scail_dit_sample_tiled", h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose_tiles, tile_frames, tile_w, inv_wsum,
+                             n_tiles, T, Tt, rope_cos, rope_sin, H, W, workspace, workspace_bytes, stream, false, nullptr, nullptr, 0);
+}
+extern "C" int scail_dit_sample_tiled_cached(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                                             const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose_tiles,
+                                             const int32_t* tile_frames, const float* tile_w, const float* inv_wsum, int64_t n_tiles, int64_t T,
+                                             int64_t Tt, const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace,
+                                             int64_t workspace_bytes, const uint8_t* reuse, void* cache, int64_t cache_bytes, void* stream) {
+    return sample_tiled_impl("scail_dit_sample_tiled_cached", h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose_tiles, tile_frames, tile_w,
+                             inv_wsum, n_tiles, T, Tt, rope_cos, rope_sin, H, W, workspace, workspace_bytes, stream, true, reuse, cache, cache_bytes);
 }

@@ -79,6 +79,7 @@ class CStep:
         self._h = h
         self._ws = None
         self._cache = None                               # ((B, T, H, W, device), buffer) of the step cache, once a FILL has run
+        self._tile_cache = None                          # ((n_tiles, Tt, H, W, device), buffer) of the tiled sampler's cache (sample_tiled_cached)
         self._fp8_buf = None
         self._probe = None                               # (table, scratch) while the fp8 probe is on
         self.num_layers = net.num_layers
@@ -264,13 +265,19 @@ class CStep:
         n = B * T * (H // 2) * (W // 2) * D
         return self._cache[1][:2 * n].view(torch.bfloat16).view(B, -1, D)
 
-    def step_cached(self, x32, t32, cond, ref, pose, cos, sin, mode: str, cfg_pair: bool = False, n_char: int = 1) -> torch.Tensor:
+    def step_cached(self, x32, t32, cond, ref, pose, cos, sin, mode: str, cfg_pair: bool = False, n_char: int = 1, cache=None) -> torch.Tensor:
         """``step`` in a cache mode (scail_dit_step_cached): "fill" = the full evaluation, which also leaves the blocks' residual on the
-        noise rows in the cache; "reuse" = patch embedding of the noise rows + that residual + the final layer (``cond`` may be None)."""
+        noise rows in the cache; "reuse" = patch embedding of the noise rows + that residual + the final layer (``cond`` may be None).
+        ``cache``: None = the cache this object keeps (``_cache_for``), or a caller-owned uint8 tensor of at least ``step_cache_bytes`` on
+        the latent's device, 256-byte aligned, which this object neither keeps nor checks against an earlier "fill"."""
         if mode not in L.CACHE_MODES:
             raise L.ScailHipError(f"step_cached: mode must be one of {sorted(L.CACHE_MODES)}, got {mode!r}")
         B, T, _, H, W = x32.shape
-        cache = self._cache_for(B, T, H, W, x32.device, mode == "fill")
+        if cache is None:
+            cache = self._cache_for(B, T, H, W, x32.device, mode == "fill")
+        elif cache.dtype != torch.uint8 or cache.dim() != 1 or not cache.is_contiguous() or cache.device != x32.device:
+            raise L.ScailHipError(f"step_cached: a caller-owned cache is a contiguous 1-d uint8 tensor on {x32.device}, got {cache.dtype} "
+                                  f"{tuple(cache.shape)} on {cache.device}")
         ws = self._ws_for(self.workspace_bytes(B, T, H, W, n_char), x32.device, "scail_dit_chars_workspace_bytes")
         cc = None if cond is None else _cond_struct(cond)
         out = torch.empty(B, T, 16, H, W, device=x32.device, dtype=torch.float32)
@@ -348,6 +355,65 @@ class CStep:
         L.call("scail_dit_sample_tiled", self._h, x32.data_ptr(), ts.data_ptr(), C.cast(dsa, C.c_void_p), n, float(cfg_scale), C.byref(cc),
                ref.data_ptr(), pose_tiles.data_ptr(), fr, tw, iw, n_tiles, T, Tt, cos.data_ptr(), sin.data_ptr(), H, W,
                ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+        return x32
+
+    def sample_tiled_cache_bytes(self, n_tiles, Tt, H, W) -> int:
+        n = L.load().scail_dit_sample_tiled_cache_bytes(self._h, n_tiles, Tt, H, W)
+        if n < 0:
+            raise L.ScailHipError(f"scail_dit_sample_tiled_cache_bytes: bad shape (n_tiles {n_tiles}, Tt {Tt}, H {H}, W {W})")
+        return n
+
+    def _tile_cache_for(self, n_tiles, Tt, H, W, device) -> torch.Tensor:
+        """The cache of sample_tiled_cached -- one residual slab per tile and one shared embedding region --, a new one when the tiling,
+        the shape or the device changed.  Handed out by ``_ws_for`` and kept beside the workspace, as ``_cache_for`` does."""
+        key = (n_tiles, Tt, H, W, torch.device(device))
+        if self._tile_cache is None or self._tile_cache[0] != key:
+            ws, self._ws = self._ws, None
+            try:
+                buf = self._ws_for(self.sample_tiled_cache_bytes(n_tiles, Tt, H, W), device,
+                                   f"scail_dit_sample_tiled_cache_bytes (n_tiles {n_tiles}, Tt {Tt}, H {H}, W {W})")
+            finally:
+                self._ws = ws
+            self._tile_cache = (key, buf)
+        return self._tile_cache[1]
+
+    def tile_cache_residual(self, k, n_tiles, Tt, H, W, D) -> torch.Tensor:
+        """tile k's r (2, Lnoise, D) bf16 as the last computed step of sample_tiled_cached left it: a view of slab k of the cache (slabs
+        of 2 * Lnoise * D * 2 bytes rounded up to 256, from offset 0)"""
+        assert self._tile_cache is not None and self._tile_cache[0][:4] == (n_tiles, Tt, H, W), "no tiled cache of this shape"
+        assert 0 <= k < n_tiles
+        n = 2 * Tt * (H // 2) * (W // 2) * D
+        slab = (2 * n + 255) // 256 * 256
+        return self._tile_cache[1][k * slab:k * slab + 2 * n].view(torch.bfloat16).view(2, -1, D)
+
+    def sample_tiled_cached(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose_tiles, tile_indices, tile_w, inv_wsum, cos, sin, reuse) -> torch.Tensor:
+        """``sample_tiled`` with a step cache (scail_dit_sample_tiled_cached): ``reuse`` = one 0 / 1 per step, shared by every tile; at a
+        step planned 1 every tile reuses its own residual of the last computed step.  Still ONE call that only enqueues.  A call the
+        library refuses leaves this object with the tiled cache it had before."""
+        _, T, _, H, W = x32.shape
+        n_tiles = len(tile_indices)
+        Tt = len(tile_indices[0]) if n_tiles else 0
+        ts, dsa, n = self._schedule(sigmas, x32.device)
+        reuse = [int(v) for v in reuse]
+        if len(reuse) != n:
+            raise L.ScailHipError(f"sample_tiled_cached: the reuse mask needs one entry per step ({n}), got {len(reuse)}")
+        if any(v < 0 or v > 255 for v in reuse):
+            raise L.ScailHipError(f"sample_tiled_cached: the reuse mask holds 0 / 1 entries, got {reuse}")
+        assert x32.is_contiguous() and x32.dtype == torch.float32 and ref.shape[0] == 1 and pose_tiles.is_contiguous()
+        assert pose_tiles.shape == (1, n_tiles, Tt, 16, H // 2, W // 2) and pose_tiles.dtype == torch.bfloat16
+        held = self._tile_cache
+        try:
+            cache = self._tile_cache_for(n_tiles, Tt, H, W, x32.device)
+            ws = self._ws_for(self.sample_tiled_workspace_bytes(T, Tt, H, W), x32.device, "scail_dit_sample_tiled_workspace_bytes")
+            fr, tw, iw = self.tile_tables(tile_indices, tile_w, inv_wsum)
+            cc = _cond_struct(cond)
+            L.call("scail_dit_sample_tiled_cached", self._h, x32.data_ptr(), ts.data_ptr(), C.cast(dsa, C.c_void_p), n, float(cfg_scale),
+                   C.byref(cc), ref.data_ptr(), pose_tiles.data_ptr(), fr, tw, iw, n_tiles, T, Tt, cos.data_ptr(), sin.data_ptr(), H, W,
+                   ws.data_ptr(), ws.numel(), (C.c_uint8 * max(n, 1))(*reuse), cache.data_ptr(), cache.numel(),
+                   torch.cuda.current_stream().cuda_stream)
+        except L.ScailHipError:
+            self._tile_cache = held
+            raise
         return x32
 
     def block(self, layer: int, hidden: torch.Tensor, mod: torch.Tensor, cond: Dict, cos, sin) -> torch.Tensor:

@@ -546,7 +546,7 @@ class DiffusionTransformer(nn.Module):
 
     def _step_cache_ok(self, what="step_cache"):
         """The step cache lives in the one-call C executor on one rank (include/scail_dit.h "step cache": no *_cached form of the
-        sequence-parallel calls or of the per-block seam): everything else is refused by name"""
+        sequence-parallel calls or of the per-block seam; the tiled loop has one, sample_tiled_c): everything else is refused by name"""
         if not self.executor_ok(whole_loop=True) or self._c_blocks:
             raise NotImplementedError(f"{what} runs in the C executor's one-call step on a single rank only: not on sequence-parallel ranks, not "
                                       "with SCAIL_C_STEP=0, _tap, kernel_timer or the per-block seam")
@@ -628,17 +628,24 @@ class DiffusionTransformer(nn.Module):
             return ex.sample_cached(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, reuse, n_char=n_char)
         return ex.sample(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, n_char=n_char)
 
-    def sample_tiled_c(self, x32, sigmas, cfg_scale, ctx, ref, pose_tiles, clip, tile_indices, tile_w, inv_wsum, cond_key=None):
+    def sample_tiled_c(self, x32, sigmas, cfg_scale, ctx, ref, pose_tiles, clip, tile_indices, tile_w, inv_wsum, cond_key=None, reuse=None):
         """The whole RFSamplerLong loop (temporal tiling) as ONE C call (scail_dit_sample_tiled, include/scail_dit.h): x32 (1,T,16,H,W) fp32,
         ctx (2, Lt, text_dim) = [uncond; cond], ref (1,1,16,H,W), pose_tiles (1, n_tiles, Tt, 16, H/2, W/2), clip (1,Lc,1280);
-        tile_w (n_tiles, Tt) = m_k * tile_weight and inv_wsum (T) as RFSamplerLong.sample_hip forms them.  Single rank, one character."""
+        tile_w (n_tiles, Tt) = m_k * tile_weight and inv_wsum (T) as RFSamplerLong.sample_hip forms them.  Single rank, one character.
+        ``reuse``: None, or the step cache's plan -- one 0 / 1 per step, shared by every tile; 1 = every tile reuses its own block
+        residual of the last computed step (scail_dit_sample_tiled_cached)."""
         dev, Tt = x32.device, len(tile_indices[0])
+        if reuse is not None:
+            self._step_cache_ok()
         if ref.shape[1] != 1:
             raise L.ScailHipError(f"temporal tiles take one reference frame (tiles and several characters are not combined), got {ref.shape[1]}")
         if pose_tiles.dim() != 6 or pose_tiles.shape[1] != len(tile_indices) or pose_tiles.shape[2] != Tt:
             raise L.ScailHipError(f"smpl_tiled must be (1, n_tiles = {len(tile_indices)}, Tt = {Tt}, 16, H/2, W/2), got "
                                   f"{tuple(pose_tiles.shape)}")
         ex, cond, cos, sin, x = self._sample_prelude(x32, ctx, clip, cond_key, Tt, 1)
+        if reuse is not None:
+            return ex.sample_tiled_cached(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose_tiles, dev), tile_indices, tile_w, inv_wsum,
+                                          cos, sin, reuse)
         return ex.sample_tiled(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose_tiles, dev), tile_indices, tile_w, inv_wsum, cos, sin)
 
     def _run(self, x32, t32, ctx, ref, pose, clip, H_shift=0, W_shift=0, cond_key=None, cfg_pair=False, step_cache=None):

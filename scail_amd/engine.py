@@ -62,7 +62,9 @@ class SATVideoDiffusionEngine(nn.Module):
         """diffusion_video.py:456-587.  shape = (T, C, H, W).  Noise is drawn in fp32 on the host RNG
         stream of ``generator`` like ``torch.randn(batch, *shape)`` (:470), broadcast inside the
         sequence-parallel group (:486-493) and H/W-chunked (:495-552); result gathered to SP rank 0 (:571-585).
-        ``step_cache``: None, or the step-cache option of RFSampler.sample_hip (an extension, opt-in; fused HIP network, one rank, no tiles)."""
+        ``step_cache``: None, or the step-cache option of RFSampler.sample_hip (an extension, opt-in; fused HIP network, one rank).  With
+        ``tile_indices`` it reaches RFSamplerLong.sample_hip: one plan for every tile and one block residual per tile, for the requests
+        that take the one-call tiled loop; the sampler refuses the others (a callback, several characters, tiles above 64 frames)."""
         if step_cache is not None:
             if not (fused and isinstance(self.network, DiffusionTransformer)):
                 raise NotImplementedError("step_cache needs the fused path of the HIP network (RFSampler.sample_hip)")

@@ -130,6 +130,10 @@ SIGNATURES = {
     "scail_dit_step_cached": [_p, _p, _p, _p, _p, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, C.c_uint32, _p, _i64,
                               _i, _p, _i64, _p],
     "scail_dit_sample_cached": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64, _p],
+    # the tiled sampler with one residual slab per tile: scail_dit_sample_tiled's arguments up to the workspace + (reuse, cache, cache bytes)
+    "scail_dit_sample_tiled_cache_bytes": [_p, _i64, _i64, _i64, _i64],
+    "scail_dit_sample_tiled_cached": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i64,
+                                      _p, _p, _i64, _p],
     "scail_dit_time_distances_bytes": [_p, _i],
     "scail_dit_time_distances": [_p, _p, _i64, _i, _p, _p, _i64, _p],
     # include/scail_vae.h (scail_amd/cvae.py builds the structs)
@@ -183,7 +187,8 @@ ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- sc
                          # scail_quant_mxfp8_rows / scail_gemm_mxfp8 / scail_dit_fp8_weight_bytes_scaled / scail_dit_enable_fp8_scaled,
                          # and the step cache, scail_resid_store / scail_resid_apply / scail_abs_diff_sums / scail_dit_step_cache_bytes /
                          # scail_dit_step_cached / scail_dit_sample_cached / scail_dit_time_distances / scail_dit_time_distances_bytes,
-                         # and the 6-bit GEMMs, scail_quant_mxfp6_rows / scail_gemm_mxfp6 / scail_dit_fp6_weight_bytes / scail_dit_enable_fp6)
+                         # and the 6-bit GEMMs, scail_quant_mxfp6_rows / scail_gemm_mxfp6 / scail_dit_fp6_weight_bytes / scail_dit_enable_fp6,
+                         # and the tiled step cache, scail_dit_sample_tiled_cache_bytes / scail_dit_sample_tiled_cached)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);

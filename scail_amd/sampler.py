@@ -374,22 +374,39 @@ class RFSamplerLong(RFSampler):
     def sample_hip(self, network, x, cond: Dict, uc: Dict, num_steps=None, scale=None, chunk_dim=None,
                    step_callback=None, tile_indices=None, step_cache=None):
         """Fused path for the HIP network: per step and tile one batch-2 DiT forward (fp32 out); the text / CLIP
-        conditioning (step- AND tile-invariant) is computed once per request."""
-        if step_cache is not None:
-            raise NotImplementedError("step_cache is not combined with temporal tiles (RFSamplerLong): the tiled loop has no cached form "
-                                      "(include/scail_dit.h \"step cache\", out of scope)")
+        conditioning (step- AND tile-invariant) is computed once per request.
+        ``step_cache`` (opt-in; None = this method as it was): RFSampler.sample_hip's option.  One plan for every tile -- it depends on the
+        schedule and the weights alone -- and one block residual per tile (scail_dit_sample_tiled_cached).  Only requests that take the
+        one-call route below have a cached form (``_one_call_ok``); every other one is refused before the network is touched: there is no
+        cached host loop.  ``self.last_step_cache_plan`` keeps the plan."""
         self._check(tile_indices)
+        smpl_tiled = cond.get("smpl_tiled")
+        if step_cache is not None:
+            ref = cond.get("ref_concat")
+            if not (torch.is_tensor(smpl_tiled) and torch.is_tensor(ref)
+                    and self._one_call_ok(network, x, ref, smpl_tiled, tile_indices, step_callback, chunk_dim)):
+                raise NotImplementedError("step_cache with temporal tiles (RFSamplerLong) runs in the one-call tiled loop of the C executor only "
+                                          "(scail_dit_sample_tiled_cached): one rank, no chunk_dim, no step_callback, not with SCAIL_C_STEP=0, _tap or "
+                                          "kernel_timer, one character, tiles of at most 64 latent frames and smpl_tiled of shape "
+                                          "(1, n_tiles, Tt, 16, H/2, W/2); the host loop has no cached form")
         n = len(tile_indices)
         sig = self.sigmas(num_steps)
         cfg = float(self.guider.scale if scale is None else scale)
         ctx = torch.cat((uc["crossattn"], cond["crossattn"]), 0)
         shared = {k: v for k, v in cond.items() if k not in ("crossattn", "smpl_tiled", "concat_smpl_render")}
         smpl_tiled = cond["smpl_tiled"]
+        plan = None
+        if step_cache is not None:
+            plan = self.last_step_cache_plan = self.step_cache_plan(network, sig, step_cache)
         idxs, tile_w, inv_wsum = self._tile_table(tile_indices, x.shape[1], x.device)
         if self._one_call_ok(network, x, shared["ref_concat"], smpl_tiled, tile_indices, step_callback, chunk_dim):
             # the whole loop enqueued by ONE call into the library (scail_dit_sample_tiled): same network kernels, the gather / blend /
             # Euler arithmetic below as HIP row kernels that round every operation on its own -- the same bits.  The weights are handed
             # over as host values once per request.
+            if plan is not None:
+                return network.sample_tiled_c(x, sig, cfg, ctx, shared["ref_concat"], smpl_tiled, shared["image_clip_features"],
+                                              [list(map(int, t)) for t in tile_indices], tile_w.cpu(), inv_wsum.cpu(),
+                                              cond_key=("sample_hip", id(cond)), reuse=plan)
             return network.sample_tiled_c(x, sig, cfg, ctx, shared["ref_concat"], smpl_tiled, shared["image_clip_features"],
                                           [list(map(int, t)) for t in tile_indices], tile_w.cpu(), inv_wsum.cpu(),
                                           cond_key=("sample_hip", id(cond)))

@@ -8,9 +8,15 @@ after a warm-up, on the random-init 14B network at config-2 size (512x896x81f: l
     --ratios x the median relative distance of the schedule's time embeddings (thresholds chosen to spread the plans, NOT recommendations:
     on random-init weights they say nothing about quality), and the cosine of each final latent against the uncached one;
   * tiny leg: the same plans' cosine against the fp32 reference trajectory tests/golden/sampler_tiny_50.npz on BASELINE config 1's
-    network (recorded, not gated).
+    network (recorded, not gated);
+  * tiled leg (--tiled: this leg alone): a latent of --tiled-frames frames in the windows of cli.plan_tiles(frames, 21, 10) -- 41 frames
+    in three 21-frame windows, the shape of profiles/longclip_onecall.log --, --tiled-steps steps: scail_dit_sample_tiled against
+    scail_dit_sample_tiled_cached under the all-zero plan (the same evaluations: the two should differ by no more than the spread of the
+    repetitions) and under two explicit plans in which about 60 % and 40 % of the steps compute, evenly spread, first and last step
+    computing (plans chosen to spread the cost, NOT recommendations).  --reps may be 2 here: one round is minutes.
 Usage: python tools/step_cache_ab.py [--reps 3] [--layers 40] [--sample-steps 50] [--ratios 1.5,3] [--signal time] [--no-step] [--no-rows]
        [--no-sample] [--no-tiny]
+       python tools/step_cache_ab.py --tiled [--reps 2] [--layers 40] [--tiled-frames 41] [--tiled-steps 5]
 Prints one line per measurement (median and [min, max] of the repetitions) and a JSON summary line last."""
 from __future__ import annotations
 
@@ -198,6 +204,72 @@ def tiny_leg(ratios, signal, dev):
     return res
 
 
+def spread_plan(steps, fraction):
+    """a plan in which round(fraction * steps) steps compute (at least the first; the last too from two on), evenly spread"""
+    k = min(steps, max(1, round(fraction * steps)))
+    computed = {0} if k == 1 else {round(j * (steps - 1) / (k - 1)) for j in range(k)}
+    return [0 if i in computed else 1 for i in range(steps)]
+
+
+def tiled_leg(net, reps, steps, frames, dev):
+    from scail_amd.cli import plan_tiles
+    from scail_amd.sampler import RFSamplerLong
+    Tt = T
+    tiles = plan_tiles(frames, Tt, 10)
+    if tiles is None:
+        raise SystemExit(f"--tiled-frames must exceed one window of {Tt} latent frames, got {frames}")
+    g = torch.Generator().manual_seed(4321)
+    x = torch.randn(1, frames, 16, H, W, generator=g).to(dev)
+    ref = torch.randn(1, 1, 16, H, W, generator=g).to(dev).to(torch.bfloat16)
+    pose = torch.randn(1, len(tiles), Tt, 16, H // 2, W // 2, generator=g).to(dev).to(torch.bfloat16)
+    ctx = torch.randn(2, LT, P14B["text_dim"], generator=g).to(dev).to(torch.bfloat16)
+    clip = torch.randn(1, LC, 1280, generator=g).to(dev).to(torch.bfloat16)
+    sig = make_flow_timesteps(0, steps, shift_scale=5, mode="normal")
+    _, tile_w, inv_wsum = RFSamplerLong(hunyuan_schedule=True)._tile_table(tiles, frames, dev)
+    tile_w, inv_wsum = tile_w.cpu(), inv_wsum.cpu()
+    run = lambda s, **kw: net.sample_tiled_c(x, s, 4.0, ctx, ref, pose, clip, tiles, tile_w, inv_wsum, **kw)
+    plans = {"all-zero": [0] * steps, "60 %": spread_plan(steps, 0.6), "40 %": spread_plan(steps, 0.4)}
+    # warm-up: one uncached step, then one computed and one reused step (every kernel, table and buffer of both modes)
+    run(sig[:2])
+    run(sig[:3], reuse=[0, 1])
+    torch.cuda.synchronize()
+    ex = net._executor()
+    res = {"frames": frames, "tiles": [t[0] for t in tiles], "tile_frames": Tt, "steps": steps,
+           "cache_bytes": ex.sample_tiled_cache_bytes(len(tiles), Tt, H, W), "stacked_step_caches_bytes": len(tiles) * ex.step_cache_bytes(2, Tt, H, W),
+           "plans": {}}
+    print(f"tiled: {frames}-frame latent {H}x{W}, {len(tiles)} windows of {Tt} (starts {res['tiles']}), {steps} steps, {net.num_layers} layers; cache "
+          f"{res['cache_bytes'] / 1e9:.3f} GB (stacked step caches would be {res['stacked_step_caches_bytes'] / 1e9:.3f} GB)", flush=True)
+    arms = {"uncached": lambda: run(sig)}
+    for label, plan in plans.items():
+        arms[label] = (lambda plan=plan: run(sig, reuse=plan))
+        print(f"  (plan {label}: {plan.count(0)} of {steps} steps compute: {plan})", flush=True)
+    outs = {}
+    ts = {k: [] for k in arms}
+    for i in range(reps):
+        for k, fn in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            o = fn()
+            e1.record()
+            e1.synchronize()
+            ts[k].append(e0.elapsed_time(e1))
+            if i == 0:
+                outs[k] = o.clone()
+            print(f"  (round {i + 1} of {reps}: {k} {ts[k][-1]:.0f} ms)", flush=True)
+    ts = {k: _summ(v) for k, v in ts.items()}
+    res["uncached"] = ts["uncached"]
+    print(f"{steps}-step tiled sampler: uncached (scail_dit_sample_tiled) {_fmt(ts['uncached'])}", flush=True)
+    for label, plan in plans.items():
+        p = res["plans"][label] = dict(ts[label], plan=plan, computed=plan.count(0), cosine_vs_uncached=_cos(outs[label], outs["uncached"]),
+                                       bit_equal_to_uncached=bool(torch.equal(outs[label], outs["uncached"])))
+        p["time_over_uncached"] = v = {"median": p["median_ms"] / ts["uncached"]["median_ms"],
+                                       "range": [p["min_ms"] / ts["uncached"]["max_ms"], p["max_ms"] / ts["uncached"]["min_ms"]]}
+        print(f"  plan {label:8s}: {p['computed']} of {steps} steps compute; {_fmt(p)}; time / uncached {v['median']:.3f} "
+              f"[{v['range'][0]:.3f}, {v['range'][1]:.3f}]; final latent cosine vs uncached {p['cosine_vs_uncached']:.6f}"
+              f"{' (bit-equal)' if p['bit_equal_to_uncached'] else ''}", flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
@@ -207,9 +279,20 @@ def main():
     ap.add_argument("--signal", choices=tuple(L.CACHE_SIGNALS), default="time")
     for leg in ("step", "rows", "sample", "tiny"):
         ap.add_argument(f"--no-{leg}", action="store_true")
+    ap.add_argument("--tiled", action="store_true", help="run the tiled leg alone (scail_dit_sample_tiled against scail_dit_sample_tiled_cached)")
+    ap.add_argument("--tiled-frames", type=int, default=41, help="latent frames of the tiled leg's clip (windows of 21, overlap 10)")
+    ap.add_argument("--tiled-steps", type=int, default=5)
     a = ap.parse_args()
-    if a.reps < 3:
-        ap.error("--reps must be at least 3 (ranges are reported)")
+    if a.reps < (2 if a.tiled else 3):
+        ap.error("--reps must be at least 3 (2 with --tiled): ranges are reported")
+    if a.tiled:
+        if a.tiled_steps < 3:
+            ap.error("--tiled-steps must be at least 3 (the plans need a step to skip)")
+        L.load()
+        net = _net14b(a.layers, "cuda")[0]
+        out = {"device": torch.cuda.get_device_name(0), "reps": a.reps, "tiled": tiled_leg(net, a.reps, a.tiled_steps, a.tiled_frames, "cuda")}
+        print(json.dumps(out))
+        return
     ratios = [float(v) for v in a.ratios.split(",")]
     dev = "cuda"
     L.load()
