@@ -461,6 +461,66 @@ int64_t scail_dit_time_distances_bytes(const scail_dit* h, int signal);
 int scail_dit_time_distances(scail_dit* h, const float* timesteps, int64_t n_steps, int signal, double* out, void* scratch,
                              int64_t scratch_bytes, void* stream);
 
+/*
+ * ---- guidance plan (an EXTENSION, opt-in: cond-only steps and a cached CFG delta) --------------------------------------------------------
+ * A sampler step is one batch-2 evaluation, [x; x] under the uncond and the cond conditioning.  Two training-free schemes skip the uncond
+ * half of a step: a guidance INTERVAL (guide only inside a sigma interval, run the cond branch alone outside it) and a cached CFG DELTA
+ * (reuse v_c - v_u of the last guided step).  Which step does what is the caller's plan, known before the loop starts -- it depends on
+ * the sigma schedule alone --, so the sampler stays ONE call with no host synchronisation.  Nothing here changes an existing entry point,
+ * its launches, its workspace query or its result.  No plan is recommended: nothing has been measured on real weights.
+ *
+ * scail_dit_step_branch: ONE branch of the pair as an evaluation: scail_dit_step_chars with B = 1 and n_ref = n_pose = 1, whose
+ *   conditioning is element `elem` of a `cond` that holds cond_batch elements (k_text [layers][cond_batch][Lt][D] and so on; a CLIP
+ *   conditioning with Bc == 1 is shared as ever).  timesteps = ONE device float.  `out` has the bits of scail_dit_step_chars with B = 1 on a
+ *   scail_dit_cond that holds that element's slices alone: quantised GEMMs and the last-layer row pruning included (every kernel computes
+ *   a row from that row alone, and the conditioning is only addressed differently).  workspace >= scail_dit_chars_workspace_bytes(h, 1, T,
+ *   H, W, n_char).  mode: 0 (no cache; cache may be NULL), SCAIL_DIT_CACHE_FILL or SCAIL_DIT_CACHE_REUSE on the step cache of the PAIR,
+ *   scail_dit_step_cache_bytes(h, 2, T, H, W): the branch reads and writes slot `elem` of r ([2][Lnoise][D] at offset 0) and nothing of the
+ *   other slot; FILL parks its copy of the embedded noise rows in slot `elem` of the embedding region, which is dead after the store.
+ *   Refused before anything is enqueued, naming the value: cond_batch outside 1..8, elem outside [0, cond_batch), a mode other than the
+ *   three, with a cache mode an elem above 1 and everything scail_dit_step_cached refuses about the cache.
+ *
+ * scail_dit_guidance_bytes: bytes of the caller-owned, 256-byte aligned delta buffer: fp32 [T * 16 * H * W], rounded up to 256 (-1: a bad
+ *   shape, as the workspace queries answer).
+ *
+ * scail_dit_sample_guided: scail_dit_sample_chars + (guide, delta, delta_bytes) + optionally the step cache's (reuse, cache, cache_bytes);
+ *   reuse == NULL: no step cache (cache is not read).  guide = HOST uint8 [n_steps], read during the call; step i does
+ *     SCAIL_DIT_GUIDE_PAIR   today's step -- the batch-2 evaluation with SCAIL_DIT_CFG_PAIR and scail_cfg_euler (scail_hip.h) --, and
+ *                            additionally scail_cfg_delta_store of its [v_u; v_c] into delta;
+ *     SCAIL_DIT_GUIDE_DELTA  the cond branch alone, scail_dit_step_branch(elem 1 of 2) on x itself, then scail_cfg_euler_delta with the
+ *                            stored delta: x += dsigma (v_c + (cfg - 1) delta);
+ *     SCAIL_DIT_GUIDE_COND   the cond branch alone, then scail_cfg_euler_delta with delta == NULL: x += dsigma v_c, no guidance.
+ *   The workspace is scail_dit_sample_chars_workspace_bytes' (the B = 1 layout lies inside the B = 2 one).  With a mask, a PAIR step is
+ *   scail_dit_step_cached as in scail_dit_sample_cached, a DELTA or COND step scail_dit_step_branch(elem 1) in FILL mode (reuse[i] == 0)
+ *   or REUSE mode.  The call only enqueues, nothing synchronises, and it is capturable on the same terms as scail_dit_sample.
+ *   Bit for bit: an all-PAIR plan gives scail_dit_sample_chars' x (with a mask: scail_dit_sample_cached's); after a PAIR step delta holds
+ *   v_c - v_u of that step; a plan of COND entries alone neither reads nor writes delta (it may be NULL).
+ *   Refused before anything is enqueued, x and both buffers untouched, naming the value: an entry above 2 (index and value); a DELTA entry
+ *   with no PAIR entry before it (index); while the plan holds a PAIR or DELTA entry, a delta buffer that is null, not 256-byte aligned
+ *   or smaller than scail_dit_guidance_bytes; with a mask, everything scail_dit_sample_cached refuses, in its wording, and a step with
+ *   reuse[i] == 1 whose entry does not evaluate the same elements as the last computing step j (PAIR goes with PAIR, DELTA or COND with
+ *   DELTA or COND; both indices are named): a reusing step must find the residual slots its last FILL wrote.
+ *
+ * Cost: by executed FLOPs a branch evaluation is about half a pair evaluation; it does not share layer 0 with a twin as
+ * SCAIL_DIT_CFG_PAIR does.  That is an expectation from the FLOP count, NOT a measurement (README "guidance plan" has what was measured).
+ *
+ * Out of scope, each refused by name in the Python layers: temporal tiles (scail_dit_sample_tiled*: a delta per tile is the natural
+ * follow-up), the sequence-parallel calls, the per-block seam, dynamic thresholding and other guiders.
+ */
+#define SCAIL_DIT_GUIDE_PAIR 0
+#define SCAIL_DIT_GUIDE_DELTA 1
+#define SCAIL_DIT_GUIDE_COND 2
+int scail_dit_step_branch(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond, int64_t cond_batch, int64_t elem,
+                          const scail_bf16* ref, const scail_bf16* pose, int64_t n_char, int64_t pose_frames,
+                          const float* rope_cos, const float* rope_sin, float* out, int64_t T, int64_t H, int64_t W,
+                          void* workspace, int64_t workspace_bytes, int mode, void* cache, int64_t cache_bytes, void* stream);
+int64_t scail_dit_guidance_bytes(int64_t T, int64_t H, int64_t W);
+int scail_dit_sample_guided(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                            const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose, int64_t n_char, int64_t pose_frames,
+                            const float* rope_cos, const float* rope_sin, int64_t T, int64_t H, int64_t W,
+                            void* workspace, int64_t workspace_bytes, const uint8_t* guide, void* delta, int64_t delta_bytes,
+                            const uint8_t* reuse, void* cache, int64_t cache_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,7 +47,8 @@ const char* scail_last_error(void);
  * scail_dit.h's scail_dit_fp8_weight_bytes_scaled / scail_dit_enable_fp8_scaled, and for the step cache, scail_resid_store /
  * scail_resid_apply / scail_abs_diff_sums and scail_dit.h's scail_dit_step_cache_bytes / scail_dit_step_cached / scail_dit_sample_cached /
  * scail_dit_time_distances / scail_dit_time_distances_bytes, and for the 6-bit GEMMs, scail_quant_mxfp6_rows / scail_gemm_mxfp6 and
- * scail_dit.h's scail_dit_fp6_weight_bytes / scail_dit_enable_fp6.) */
+ * scail_dit.h's scail_dit_fp6_weight_bytes / scail_dit_enable_fp6, and for the guidance plan, scail_cfg_delta_store / scail_cfg_euler_delta
+ * and scail_dit.h's scail_dit_step_branch / scail_dit_guidance_bytes / scail_dit_sample_guided.) */
 int scail_abi_version(void);
 
 /* ---- epilogues of scail_gemm_bf16 ---------------------------------------------------------- */
@@ -369,6 +370,20 @@ int scail_unpatchify(const scail_bf16* tok, float* out, int64_t n_batch, int64_t
  * (guiders.py:41-45 + sampling_utils.py:7-10 + Euler update sampling.py:960-963), all fp32.  Its two multiply-adds may contract: an element is
  * one of the four results with each of them fused or rounded separately.  Errors: n < 0 or 2^31 workgroups or more, a null pointer with n > 0. */
 int scail_cfg_euler(float* x, const float* v, int64_t n, float cfg_scale, float dsigma, void* stream);
+
+/*
+ * The two fp32 passes of the guidance plan (scail_dit.h "guidance plan"): classifier-free guidance around a STORED v_c - v_u.
+ *   scail_cfg_delta_store:  delta[i] = v_c[i] - v_u[i]                                 v = [v_u; v_c] fp32 [2, n], only read
+ *   scail_cfg_euler_delta:  x[i] = x[i] + dsigma * (v_c[i] + g * delta[i])             g = cfg_scale - 1, formed once on the host in fp32
+ *                           x[i] = x[i] + dsigma * v_c[i]                              with delta == NULL: no guidance
+ * v_c + (s - 1) (v_c - v_u) is v_u + s (v_c - v_u) rewritten around the difference.  EVERY operation is rounded on its own (no fused
+ * multiply-add), so each call gives the bits of the torch fp32 expression, one tensor operation per arithmetic operation -- unlike
+ * scail_cfg_euler, whose multiply-adds contract.  v_c and delta are only read.
+ * Errors (host side, naming the value): n < 0 or 2^31 workgroups or more; a null v / delta (store) or x / v_c (euler).  n == 0 launches
+ * nothing.
+ */
+int scail_cfg_delta_store(const float* v, float* delta, int64_t n, void* stream);
+int scail_cfg_euler_delta(float* x, const float* v_c, const float* delta, int64_t n, float cfg_scale, float dsigma, void* stream);
 
 /*
  * Temporal tiling of RFSamplerLong (sampling.py:986-1085): the three elementwise fp32 passes of one sampler step around the network

@@ -29,6 +29,7 @@ from __future__ import annotations
 
 import argparse
 import copy
+import math
 import os
 import time
 
@@ -284,6 +285,43 @@ def step_cache_args(threshold, coefficients=None, keep=None, signal=None):
     return opt
 
 
+def guidance_args(interval=None, every=None, plan=None, tile_frames=None):
+    """``--cfg-interval LO HI`` / ``--cfg-delta-every K`` / ``--cfg-plan 0,2,1,...`` -> the ``guidance`` option of RFSampler.sample_hip, or None
+    when none of the three is given.  An explicit plan stands alone; none of them goes with ``--tile-frames``."""
+    if interval is None and every is None and plan is None:
+        return None
+    if tile_frames is not None:
+        raise ValueError("--cfg-interval / --cfg-delta-every / --cfg-plan do not go with --tile-frames: the tiled loops keep no delta per temporal window")
+    if plan is not None:
+        if interval is not None or every is not None:
+            raise ValueError("--cfg-plan stands alone: --cfg-interval and --cfg-delta-every make a plan from the schedule")
+        try:
+            modes = [int(v) for v in str(plan).split(",")]
+        except ValueError:
+            raise ValueError(f"--cfg-plan must be entries 0 / 1 / 2 separated by commas, one per step, got {plan!r}")
+        from .sampler import check_guidance_plan
+        return {"modes": check_guidance_plan(modes, what="--cfg-plan")}
+    opt = {}
+    if interval is not None:
+        lo, hi = (float(v) for v in interval)
+        if not (math.isfinite(lo) and math.isfinite(hi)) or lo > hi:
+            raise ValueError(f"--cfg-interval needs finite LO <= HI (sigma runs from 1 down to 0), got {lo} {hi}")
+        opt["interval"] = (lo, hi)
+    if every is not None:
+        if int(every) < 1:
+            raise ValueError(f"--cfg-delta-every must be an integer >= 1, got {every}")
+        opt["every"] = int(every)
+    return opt
+
+
+def format_guidance_plan(plan):
+    """The plan as text: which steps run the pair, and k of n"""
+    pair = [i for i, v in enumerate(plan) if v == 0]
+    n_delta, n_cond = sum(1 for v in plan if v == 1), sum(1 for v in plan if v == 2)
+    return (f"guidance plan: {len(pair)} of {len(plan)} steps run the uncond / cond pair ({', '.join(map(str, pair))}); {n_delta} run the cond "
+            f"branch with the last stored delta, {n_cond} the cond branch without guidance")
+
+
 def format_step_cache_plan(plan):
     """The plan as text: which steps compute, and k of n"""
     computed = [i for i, v in enumerate(plan) if not v]
@@ -315,8 +353,10 @@ def _calibrate(engine, c, uc, shape, steps, fp8_max_error):
 
 
 def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frames=None, engine=None, tile_frames=None, tile_overlap=None,
-        vae_chunk_frames=None, postprocess="torch", fp8_max_error=None, step_cache=None):
-    """``fp8_max_error`` (fp8 networks only): probe the request's first evaluation and keep in bf16 every (layer, GEMM) whose fp8 result is
+        vae_chunk_frames=None, postprocess="torch", fp8_max_error=None, step_cache=None, guidance=None):
+    """``guidance``: None, or the guidance option (guidance_args; RFSampler.sample_hip): which steps run the CFG pair, the cond branch with
+    the stored delta, or the cond branch alone.  One rank, one window.  The plan is printed.
+    ``fp8_max_error`` (fp8 networks only): probe the request's first evaluation and keep in bf16 every (layer, GEMM) whose fp8 result is
     further than this from bf16 (engine.calibrate_fp8).
     ``step_cache``: None, or the step-cache option (step_cache_args; RFSampler.sample_hip): steps whose time embedding moved little reuse the
     block residual of the last computed step.  One rank; a clip longer than one window keeps one residual per temporal tile under one
@@ -344,6 +384,9 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
             raise ValueError(f"a pose clip longer than one window needs 4n + 1 frames (the causal VAE's frame groups), got {n_pix}")
         Tt, overlap = tile_args(tile_frames, tile_overlap, net.num_frames)
         tiles = plan_tiles((n_pix - 1) // 4 + 1, Tt, overlap)
+        if guidance is not None:
+            raise NotImplementedError("guidance with temporal tiles is out of scope: this pose clip is longer than one window and the tiled loops "
+                                      "keep no delta per temporal window")
         return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames, postprocess, fp8_max_error, step_cache)
     pose_lat = engine.encode_first_stage(req["pose"].unsqueeze(0), None, force_encode=True)   # already half resolution (:350-351)
     ref_concat = ref_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)      # B C T H W -> B T C H W
@@ -355,11 +398,12 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     uc = dict(crossattn=req["uncond_context"], **shared)
     _calibrate(engine, c, uc, (T, C, h, w), steps, fp8_max_error)
     torch.manual_seed(seed)
-    if step_cache is None:
-        z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps)
-    else:
-        z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, step_cache=step_cache)
+    opts = {k: v for k, v in (("step_cache", step_cache), ("guidance", guidance)) if v is not None}
+    z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, **opts)
+    if step_cache is not None:
         print(format_step_cache_plan(engine.sampler.last_step_cache_plan))
+    if guidance is not None:
+        print(format_guidance_plan(engine.sampler.last_guidance_plan))
     return _finish(engine, z, t0, vae_chunk_frames, postprocess)
 
 
@@ -466,6 +510,17 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--step-cache-signal", choices=tuple(lib.CACHE_SIGNALS), default=None,
                     help="with --step-cache-threshold: what is compared between steps: time = the timestep embedding (default), "
                          "modulation = its AdaLN projection, the 6 D values every block is modulated with")
+    ap.add_argument("--cfg-interval", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                    help="opt-in guidance plan (an extension): classifier-free guidance only on the steps whose starting sigma lies in "
+                         "[LO, HI] (sigma runs from 1 down to 0); the other steps run the cond branch alone, about half the work of a step "
+                         "by FLOP count.  The plan is printed.  No interval is recommended: nothing has been measured on real weights.  "
+                         "One GPU and a clip of one window (not with --tile-frames); combines with --step-cache-threshold")
+    ap.add_argument("--cfg-delta-every", type=int, metavar="K", default=None,
+                    help="opt-in guidance plan: inside the interval (every step without --cfg-interval) only every K-th step runs the uncond / "
+                         "cond pair; the steps between run the cond branch alone and reuse v_c - v_u of the last pair step.  No K is recommended")
+    ap.add_argument("--cfg-plan", default=None,
+                    help="opt-in guidance plan, spelled out: one entry per step, comma-separated: 0 = the pair, 1 = cond branch + stored delta, "
+                         "2 = cond branch without guidance.  Stands alone; with --step-cache-threshold it must agree with that plan as it stands")
     ap.add_argument("--tile-frames", type=int, default=None,
                     help="pixel frames per temporal window, 4n + 1 (default: the network's num_frames); a pose clip with more frames is sampled "
                          "in overlapping windows (RFSamplerLong), an extension of the reference CLI; such a clip needs 4n + 1 frames")
@@ -519,6 +574,9 @@ def main(argv=None):
         sc = step_cache_args(a.step_cache_threshold, a.step_cache_coefficients, a.step_cache_keep, a.step_cache_signal)
         if sc is not None:
             tk["step_cache"] = sc
+        gd = guidance_args(a.cfg_interval, a.cfg_delta_every, a.cfg_plan, a.tile_frames)
+        if gd is not None:
+            tk["guidance"] = gd
     except ValueError as e:
         ap.error(str(e))
     lines = [(r, i) for i, r in enumerate(a.request)] + (list(read_from_file(a.input_file)) if a.input_file else [])

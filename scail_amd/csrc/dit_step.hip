@@ -389,11 +389,16 @@ static int block_cross_mlp(scail_dit* h, int64_t i, scail_bf16* hid, scail_bf16*
     DIT_PROF(SCAIL_DIT_PROF_GEMM, dit_gemm(h, i, G_W2, bf, ff, FF, lw.b2, hid, D, M, D, FF, SCAIL_EPI_RESID, hid, D, m + 5 * D, 6 * D, rpb, stream));
     return 0;
 }
+// Where the conditioning of a call's elements lies in `cond`: cond holds Btot elements and element b of the call reads element b0 + b.
+// Every call but scail_dit_step_branch reads its own batch from element 0 on: {B, 0}.
+struct CondAt {
+    int64_t Btot, b0;
+};
 // Everything after the self-attention of the rows [row0, row0 + rows) of every element (rows == Ltok: the whole block in one set of
 // launches; fewer: per element, the wanted rows only).  pair: hid / att / m of element 1 do not exist yet -- the out-projection runs
 // for element 0 and its result (the hidden states after the self-attention residual) is copied to element 1 before the elements part.
 static int block_tail(scail_dit* h, int64_t i, scail_bf16* hid, const float* m, const scail_dit_cond* cond, int64_t B, int64_t Ltok,
-                      const BlockBufs& bf, int64_t row0, int64_t rows, bool pair, void* stream) {
+                      const BlockBufs& bf, int64_t row0, int64_t rows, bool pair, void* stream, CondAt ca) {
     const int64_t D = h->cfg.hidden_size;
     scail_bf16 *att = bf.att, *q = bf.qkv, *xn = bf.xn, *ff = bf.ff;
     if (pair) {
@@ -405,12 +410,12 @@ static int block_tail(scail_dit* h, int64_t i, scail_bf16* hid, const float* m, 
     }
     if (rows == Ltok) {
         if (!pair) DIT_TRY(block_attn_out(h, i, hid, att, m, B, Ltok, bf, stream));
-        return block_cross_mlp(h, i, hid, att, q, xn, ff, m, cond, B, 0, B, Ltok, bf, stream);
+        return block_cross_mlp(h, i, hid, att, q, xn, ff, m, cond, ca.Btot, ca.b0, B, Ltok, bf, stream);
     }
     for (int64_t b = 0; b < B; ++b) {
         const int64_t r = b * Ltok + row0;
         if (!pair) DIT_TRY(block_attn_out(h, i, hid + r * D, att + r * D, m + b * 6 * D, 1, rows, bf, stream));
-        DIT_TRY(block_cross_mlp(h, i, hid + r * D, att + r * D, q + r * 3 * D, xn, ff, m + b * 6 * D, cond, B, b, 1, rows, bf, stream));
+        DIT_TRY(block_cross_mlp(h, i, hid + r * D, att + r * D, q + r * 3 * D, xn, ff, m + b * 6 * D, cond, ca.Btot, ca.b0 + b, 1, rows, bf, stream));
     }
     return 0;
 }
@@ -425,7 +430,7 @@ static int block_tail(scail_dit* h, int64_t i, scail_bf16* hid, const float* m, 
 //   of a sampler step): the self-attention part runs for element 0 only.
 static int dit_block(scail_dit* h, int64_t i, scail_bf16* hid, const float* m, const scail_dit_cond* cond,
                      const float* rope_cos, const float* rope_sin, int64_t B, int64_t Ltok, const BlockBufs& bf,
-                     int64_t row0, int64_t rows, bool pair, void* stream) {
+                     int64_t row0, int64_t rows, bool pair, void* stream, CondAt ca) {
     const scail_dit_config& c = h->cfg;
     const int64_t D = c.hidden_size, nh = c.num_heads;
     const float eps = c.layernorm_epsilon;
@@ -447,11 +452,11 @@ static int dit_block(scail_dit* h, int64_t i, scail_bf16* hid, const float* m, c
     if (vrows) {
         DIT_PROF(SCAIL_DIT_PROF_SELF_ATTN, scail_flash_attn_vrows_bf16(q + row0 * 3 * D, Ltok * 3 * D, 3 * D, k, Ltok * 3 * D, 3 * D, v, Ltok * 3 * D, 3 * D,
                                                                        bf.att + row0 * D, Ltok * D, D, Bs, nh, rows, Ltok, SCAIL_ATTN_Q_PRESCALED, stream));
-        return block_tail(h, i, hid, m, cond, B, Ltok, bf, row0, rows, pair, stream);
+        return block_tail(h, i, hid, m, cond, B, Ltok, bf, row0, rows, pair, stream, ca);
     }
     DIT_PROF(SCAIL_DIT_PROF_SELF_ATTN, scail_flash_attn_bf16(q + row0 * 3 * D, Ltok * 3 * D, 3 * D, k, 0, Ltok * 3 * D, 3 * D, bf.vt, 0, nh * 128 * Lp,
                                                              bf.att + row0 * D, Ltok * D, D, Bs, nh, rows, Ltok, 1, SCAIL_ATTN_Q_PRESCALED, 0, stream));
-    return block_tail(h, i, hid, m, cond, B, Ltok, bf, row0, rows, pair, stream);
+    return block_tail(h, i, hid, m, cond, B, Ltok, bf, row0, rows, pair, stream, ca);
 }
 
 // ---- the sequence-parallel block (include/scail_dit.h "sequence-parallel execution") ----
@@ -618,7 +623,7 @@ static int dit_block_sp(scail_dit* h, int64_t i, scail_bf16* hid, const float* m
                                                                      1, nh, rows, Lf, 1, SCAIL_ATTN_Q_PRESCALED, 0, stream));
         }
     }
-    return block_tail(h, i, hid, m, cond, Btot, Ltok, bf, row0, rows, pair, stream);
+    return block_tail(h, i, hid, m, cond, Btot, Ltok, bf, row0, rows, pair, stream, CondAt{Btot, 0});
 }
 
 // Seam B2 (SAT hook layer_forward): one block on caller-owned hidden states.  Workspace: scail_dit_block_workspace_bytes.
@@ -650,7 +655,7 @@ extern "C" int scail_dit_block(scail_dit* h, int64_t layer, scail_bf16* hidden, 
     SCAIL_REQUIRE(workspace != nullptr && workspace_bytes >= s.end && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                   "workspace too small or not 256-byte aligned (scail_dit_block_workspace_bytes)");
     DIT_TRY(probe_check(h, B * Ltok));
-    return dit_block(h, layer, hidden, mod, cond, rope_cos, rope_sin, B, Ltok, s.bufs(workspace), 0, Ltok, false, stream);
+    return dit_block(h, layer, hidden, mod, cond, rope_cos, rope_sin, B, Ltok, s.bufs(workspace), 0, Ltok, false, stream, CondAt{B, 0});
 }
 
 extern "C" int scail_dit_create(const scail_dit_config* cfg, const scail_dit_weights* w, scail_dit** out) {
@@ -913,7 +918,10 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
                          const scail_bf16* ref, int64_t n_ref, const scail_bf16* pose, int64_t n_pose, int64_t n_char, int64_t pose_frames,
                          const float* rope_cos, const float* rope_sin, float* out,
                          int64_t B, int64_t T, int64_t H, int64_t W, const scail_dit_sp* sp, uint32_t flags, void* workspace, int64_t workspace_bytes,
-                         void* stream, int mode = CACHE_NONE, scail_bf16* cache_r = nullptr, scail_bf16* cache_emb = nullptr) {
+                         void* stream, int mode = CACHE_NONE, scail_bf16* cache_r = nullptr, scail_bf16* cache_emb = nullptr,
+                         int64_t cond_batch = 0, int64_t cond_elem = 0) {
+    // cond_batch > 0 (scail_dit_step_branch): the call's elements read elements cond_elem .. of a conditioning that holds cond_batch
+    const CondAt ca = cond_batch > 0 ? CondAt{cond_batch, cond_elem} : CondAt{B, 0};
     DIT_TRY(chars_check("scail_dit_step", n_char, pose_frames, T));
     const bool reuse = mode == SCAIL_DIT_CACHE_REUSE;      // no block runs: the conditioning is not read
     SCAIL_REQUIRE(h != nullptr && (cond != nullptr || reuse), "null handle / conditioning");
@@ -929,7 +937,7 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
         return 1;
     }
     SCAIL_REQUIRE((n_ref == 1 || n_ref == B) && (n_pose == 1 || n_pose == B), "ref / pose batch must be 1 or B");
-    SCAIL_REQUIRE(reuse || cond->Bc == 1 || cond->Bc == B, "clip batch must be 1 or B");
+    SCAIL_REQUIRE(reuse || cond->Bc == 1 || cond->Bc == ca.Btot, "clip batch must be 1 or B");
     const scail_dit_config& c = h->cfg;
     const Ws s = sp ? layout(h, B, T, H, W, n_char, sp->mode, sp->ranks) : layout(h, B, T, H, W, n_char);
     SCAIL_REQUIRE(c.time_embed_dim == c.hidden_size, "final-layer table add needs time_embed_dim == hidden_size");
@@ -1008,7 +1016,7 @@ static int dit_step_impl(scail_dit* h, const float* x, const float* timesteps, c
         if (sp != nullptr) {
             DIT_TRY(dit_block_sp(h, i, hid, mod + i * B * 6 * D, cond, rope_cos, rope_sin, B, Ltok, bf, sp, row0, rows, pair && i == 0, stream));
         } else {
-            DIT_TRY(dit_block(h, i, hid, mod + i * B * 6 * D, cond, rope_cos, rope_sin, B, Ltok, bf, row0, rows, pair && i == 0, stream));
+            DIT_TRY(dit_block(h, i, hid, mod + i * B * 6 * D, cond, rope_cos, rope_sin, B, Ltok, bf, row0, rows, pair && i == 0, stream, ca));
         }
     }
 
@@ -1076,11 +1084,14 @@ extern "C" int scail_dit_sample(scail_dit* h, float* x, const float* timesteps, 
 }
 
 // the Euler loop; reuse == nullptr: every step a plain evaluation (scail_dit_sample_chars), else step i in SCAIL_DIT_CACHE_REUSE mode
-// where reuse[i] != 0 and in SCAIL_DIT_CACHE_FILL mode otherwise (scail_dit_sample_cached, which has checked reuse and the cache)
+// where reuse[i] != 0 and in SCAIL_DIT_CACHE_FILL mode otherwise (scail_dit_sample_cached, which has checked reuse and the cache).
+// guide == nullptr: every step the batch-2 pair, else step i as its SCAIL_DIT_GUIDE_* entry says (scail_dit_sample_guided, which has
+// checked the plan and the delta buffer)
 static int sample_impl(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps,
                        float cfg_scale, const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose,
                        int64_t n_char, int64_t pose_frames, const float* rope_cos, const float* rope_sin,
-                       int64_t T, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes, void* stream, const uint8_t* reuse, void* cache) {
+                       int64_t T, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes, void* stream, const uint8_t* reuse, void* cache,
+                       const uint8_t* guide = nullptr, float* delta = nullptr) {
     DIT_TRY(chars_check("scail_dit_sample", n_char, pose_frames, T));
     SCAIL_REQUIRE(h != nullptr && x != nullptr && timesteps != nullptr && dsigma != nullptr && n_steps >= 0, "null argument");
     const int64_t step_bytes = scail_dit_chars_workspace_bytes(h, 2, T, H, W, n_char);
@@ -1095,16 +1106,26 @@ static int sample_impl(scail_dit* h, float* x, const float* timesteps, const flo
     const int64_t n = T * 16 * H * W;
     hipStream_t s = (hipStream_t)stream;
     const CachePtrs cp = reuse == nullptr ? CachePtrs{nullptr, nullptr} : cache_ptrs(h->cfg, 2, tok_lens(1, T, H, W).Lnoise, cache);
+    const int64_t slot1 = tok_lens(1, T, H, W).Lnoise * h->cfg.hidden_size;      // element 1's slot of either cache region, in elements
     for (int64_t i = 0; i < n_steps; ++i) {
+        const int mode = reuse == nullptr ? CACHE_NONE : reuse[i] ? SCAIL_DIT_CACHE_REUSE : SCAIL_DIT_CACHE_FILL;
+        if (guide != nullptr && guide[i] != SCAIL_DIT_GUIDE_PAIR) {
+            // the cond branch alone (scail_dit_step_branch, elem 1 of 2): B = 1 on x itself, which the evaluation only reads, in the
+            // B = 1 layout of the same workspace; v_c lands where the pair's v_u does
+            DIT_TRY(dit_step_impl(h, x, timesteps + 2 * i, cond, ref, 1, pose, 1, n_char, pose_frames, rope_cos, rope_sin, v, 1, T, H, W, nullptr, 0,
+                                  workspace, step_bytes, stream, mode, mode ? cp.r + slot1 : nullptr, mode ? cp.emb + slot1 : nullptr, 2, 1));
+            DIT_TRY(scail_cfg_euler_delta(x, v, guide[i] == SCAIL_DIT_GUIDE_DELTA ? delta : nullptr, n, cfg_scale, dsigma[i], stream));
+            continue;
+        }
         // torch.cat([x] * 2) of VanillaCFG.prepare_inputs (guiders.py:56)
         if (hipMemcpyAsync(xin, x, n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
             hipMemcpyAsync(xin + n, x, n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) {
             scail_set_error("scail_dit_sample: hipMemcpyAsync failed");
             return 2;
         }
-        const int mode = reuse == nullptr ? CACHE_NONE : reuse[i] ? SCAIL_DIT_CACHE_REUSE : SCAIL_DIT_CACHE_FILL;
         DIT_TRY(dit_step_impl(h, xin, timesteps + 2 * i, cond, ref, 1, pose, 1, n_char, pose_frames, rope_cos, rope_sin, v, 2, T, H, W, nullptr,
                               SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream, mode, cp.r, cp.emb));
+        if (guide != nullptr) DIT_TRY(scail_cfg_delta_store(v, delta, n, stream));
         DIT_TRY(scail_cfg_euler(x, v, n, cfg_scale, dsigma[i], stream));
     }
     return 0;
@@ -1186,6 +1207,92 @@ extern "C" int scail_dit_sample_cached(scail_dit* h, float* x, const float* time
     DIT_TRY(cache_check(who, h, 0, false, cache, cache_bytes, 2, T, H, W));
     return sample_impl(h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose, n_char, pose_frames, rope_cos, rope_sin, T, H, W, workspace,
                        workspace_bytes, stream, reuse, cache);
+}
+
+// ---- the guidance plan (include/scail_dit.h "guidance plan") ----
+extern "C" int scail_dit_step_branch(scail_dit* h, const float* x, const float* timesteps, const scail_dit_cond* cond, int64_t cond_batch, int64_t elem,
+                                     const scail_bf16* ref, const scail_bf16* pose, int64_t n_char, int64_t pose_frames,
+                                     const float* rope_cos, const float* rope_sin, float* out, int64_t T, int64_t H, int64_t W,
+                                     void* workspace, int64_t workspace_bytes, int mode, void* cache, int64_t cache_bytes, void* stream) {
+    const char* who = "scail_dit_step_branch";
+    auto fail = [&](const std::string& msg) {
+        scail_set_error(std::string(who) + ": " + msg);
+        return 1;
+    };
+    if (cond_batch < 1 || cond_batch > 8) return fail("cond_batch must be 1..8, got " + std::to_string(cond_batch));
+    if (elem < 0 || elem >= cond_batch)
+        return fail("elem must lie in [0, cond_batch = " + std::to_string(cond_batch) + "), got " + std::to_string(elem));
+    if (mode != CACHE_NONE && mode != SCAIL_DIT_CACHE_FILL && mode != SCAIL_DIT_CACHE_REUSE)
+        return fail("unknown mode " + std::to_string(mode) + " (0 = no cache, SCAIL_DIT_CACHE_FILL = 1 or SCAIL_DIT_CACHE_REUSE = 2)");
+    CachePtrs cp{nullptr, nullptr};
+    if (mode != CACHE_NONE) {
+        // the cache is the (2, T, H, W) step cache of the pair: element `elem`'s slot of r, and of the embedding region for FILL's copy
+        if (elem > 1) return fail("a cache mode takes elem 0 or 1 (the step cache of the pair has two slots), got " + std::to_string(elem));
+        DIT_TRY(cache_check(who, h, mode, true, cache, cache_bytes, 2, T, H, W));
+        const int64_t slot = elem * tok_lens(1, T, H, W).Lnoise * h->cfg.hidden_size;
+        cp = cache_ptrs(h->cfg, 2, tok_lens(1, T, H, W).Lnoise, cache);
+        cp.r += slot;
+        cp.emb += slot;
+    }
+    return dit_step_impl(h, x, timesteps, cond, ref, 1, pose, 1, n_char, pose_frames, rope_cos, rope_sin, out, 1, T, H, W, nullptr, 0, workspace,
+                         workspace_bytes, stream, mode, cp.r, cp.emb, cond_batch, elem);
+}
+
+extern "C" int64_t scail_dit_guidance_bytes(int64_t T, int64_t H, int64_t W) {
+    if (shape_fault(1, T, H, W, 1, 1) != 0) return -1;
+    return align256(T * 16 * H * W * 4);
+}
+// whether an entry evaluates both elements (the pair) or element 1 alone
+static bool guide_is_pair(uint8_t g) { return g == SCAIL_DIT_GUIDE_PAIR; }
+extern "C" int scail_dit_sample_guided(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                                       const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose, int64_t n_char, int64_t pose_frames,
+                                       const float* rope_cos, const float* rope_sin, int64_t T, int64_t H, int64_t W,
+                                       void* workspace, int64_t workspace_bytes, const uint8_t* guide, void* delta, int64_t delta_bytes,
+                                       const uint8_t* reuse, void* cache, int64_t cache_bytes, void* stream) {
+    const char* who = "scail_dit_sample_guided";
+    auto fail = [&](const std::string& msg) {
+        scail_set_error(std::string(who) + ": " + msg);
+        return 1;
+    };
+    if (n_steps < 0) return fail("n_steps must be >= 0, got " + std::to_string(n_steps));
+    if (n_steps > 0 && guide == nullptr) return fail("null guide plan with n_steps = " + std::to_string(n_steps));
+    bool seen_pair = false, needs_delta = false;
+    for (int64_t i = 0; i < n_steps; ++i) {
+        if (guide[i] > SCAIL_DIT_GUIDE_COND)
+            return fail("guide[" + std::to_string(i) + "] = " + std::to_string((int)guide[i]) + " (an entry is 0 = pair, 1 = delta or 2 = cond)");
+        if (guide[i] == SCAIL_DIT_GUIDE_DELTA && !seen_pair)
+            return fail("guide[" + std::to_string(i) + "] = 1 (delta) has no pair step before it: there is no stored delta to use");
+        seen_pair = seen_pair || guide_is_pair(guide[i]);
+        needs_delta = needs_delta || guide[i] != SCAIL_DIT_GUIDE_COND;
+    }
+    if (needs_delta) {
+        if (delta == nullptr) return fail("null delta buffer (delta_bytes " + std::to_string(delta_bytes) + "; scail_dit_guidance_bytes)");
+        if ((reinterpret_cast<uintptr_t>(delta) & 255) != 0)
+            return fail("the delta buffer must be 256-byte aligned, got an address that is " + std::to_string(reinterpret_cast<uintptr_t>(delta) & 255) +
+                        " past a multiple of 256");
+        const int64_t need = scail_dit_guidance_bytes(T, H, W);
+        if (need < 0) return fail("bad latent shape (T " + std::to_string(T) + ", H " + std::to_string(H) + ", W " + std::to_string(W) + ")");
+        if (delta_bytes < need)
+            return fail("delta buffer too small: " + std::to_string(delta_bytes) + " bytes, needs " + std::to_string(need) + " (scail_dit_guidance_bytes)");
+    }
+    if (reuse != nullptr) {
+        DIT_TRY(reuse_check(who, reuse, n_steps));
+        // a reusing step finds the residual slots its last FILL wrote: the pair fills both, a branch step element 1's alone
+        for (int64_t i = 0, j = 0; i < n_steps; ++i) {
+            if (reuse[i] == 0) {
+                j = i;
+            } else if (guide_is_pair(guide[i]) != guide_is_pair(guide[j])) {
+                return fail("step " + std::to_string(i) + " reuses (guide " + std::to_string((int)guide[i]) + ") what step " + std::to_string(j) +
+                            ", the last computing step, left (guide " + std::to_string((int)guide[j]) +
+                            "): they do not evaluate the same elements (0 goes with 0; 1 or 2 with 1 or 2)");
+            }
+        }
+        DIT_TRY(cache_check(who, h, 0, false, cache, cache_bytes, 2, T, H, W));
+    }
+    // (n_steps == 0: guide may be null; the loop below does not run)
+    static const uint8_t none = 0;
+    return sample_impl(h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose, n_char, pose_frames, rope_cos, rope_sin, T, H, W, workspace,
+                       workspace_bytes, stream, reuse, cache, guide != nullptr ? guide : &none, static_cast<float*>(delta));
 }
 
 // ---- the decision signal of the step cache: distances of consecutive steps' time embeddings (include/scail_dit.h) ----

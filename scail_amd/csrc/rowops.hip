@@ -588,6 +588,31 @@ __global__ void tile_finish_kernel(float* __restrict__ x, float* __restrict__ de
     den[o] = 0.0f;
 }
 
+// ---- guidance plan (include/scail_dit.h "guidance plan"; include/scail_hip.h scail_cfg_delta_*) ----
+// Every operation is rounded on its own (contraction off), like the tile kernels above: each kernel gives the bits of the torch fp32
+// expression it stands for.
+// delta[i] = v_c[i] - v_u[i],  v = [v_u; v_c] fp32 [2, n]
+__global__ void cfg_delta_store_kernel(const float* __restrict__ v, float* __restrict__ delta, int64_t n) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    delta[i] = v[n + i] - v[i];
+}
+// x[i] = x[i] + dsigma * (v_c[i] + g * delta[i])   (delta == nullptr: x[i] = x[i] + dsigma * v_c[i])
+__global__ void cfg_euler_delta_kernel(float* __restrict__ x, const float* __restrict__ vc, const float* __restrict__ delta, int64_t n, float g,
+                                       float dsigma) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float d = vc[i];
+    if (delta != nullptr) {
+        const float gd = g * delta[i];
+        d = d + gd;
+    }
+    const float step = dsigma * d;
+    x[i] = x[i] + step;
+}
+
 __global__ void zero_f32_kernel(float* __restrict__ y, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) y[i] = 0.0f;
@@ -928,6 +953,36 @@ extern "C" int scail_cfg_euler(float* x, const float* v, int64_t n, float cfg_sc
     hipLaunchKernelGGL(cfg_euler_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        x, v, n, cfg_scale, dsigma);
     return scail_check_launch("cfg_euler");
+}
+
+// ---- guidance plan: host-side checks (the message names the value) + launches ----
+static int cfg_delta_n_check(const char* who, int64_t n) {
+    if (n < 0 || (n + 255) / 256 >= (1ll << 31)) {
+        scail_set_error(std::string(who) + ": n must be 0 .. 2^39 - 256 (one launch), got " + std::to_string(n));
+        return 1;
+    }
+    return 0;
+}
+extern "C" int scail_cfg_delta_store(const float* v, float* delta, int64_t n, void* stream) {
+    if (int rc = cfg_delta_n_check("scail_cfg_delta_store", n)) return rc;
+    if (v == nullptr || delta == nullptr) {
+        scail_set_error(std::string("scail_cfg_delta_store: null pointer: ") + (v == nullptr ? "v" : "delta") + " (n = " + std::to_string(n) + ")");
+        return 1;
+    }
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(cfg_delta_store_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, v, delta, n);
+    return scail_check_launch("cfg_delta_store");
+}
+extern "C" int scail_cfg_euler_delta(float* x, const float* v_c, const float* delta, int64_t n, float cfg_scale, float dsigma, void* stream) {
+    if (int rc = cfg_delta_n_check("scail_cfg_euler_delta", n)) return rc;
+    if (x == nullptr || v_c == nullptr) {
+        scail_set_error(std::string("scail_cfg_euler_delta: null pointer: ") + (x == nullptr ? "x" : "v_c") + " (n = " + std::to_string(n) + ")");
+        return 1;
+    }
+    if (n == 0) return 0;
+    const float g = cfg_scale - 1.0f;      // formed once, in fp32
+    hipLaunchKernelGGL(cfg_euler_delta_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, v_c, delta, n, g, dsigma);
+    return scail_check_launch("cfg_euler_delta");
 }
 
 // ---- temporal tiling: host-side checks (the message names the value) + launches ----

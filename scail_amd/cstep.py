@@ -80,6 +80,7 @@ class CStep:
         self._ws = None
         self._cache = None                               # ((B, T, H, W, device), buffer) of the step cache, once a FILL has run
         self._tile_cache = None                          # ((n_tiles, Tt, H, W, device), buffer) of the tiled sampler's cache (sample_tiled_cached)
+        self._delta = None                               # ((T, H, W, device), buffer) of the guidance plan's delta (sample_guided)
         self._fp8_buf = None
         self._probe = None                               # (table, scratch) while the fp8 probe is on
         self.num_layers = net.num_layers
@@ -305,6 +306,82 @@ class CStep:
         L.call("scail_dit_sample_cached", self._h, x32.data_ptr(), ts.data_ptr(), C.cast(dsa, C.c_void_p), n, float(cfg_scale),
                C.byref(cc), ref.data_ptr(), pose.data_ptr(), n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), T, H, W,
                ws.data_ptr(), ws.numel(), (C.c_uint8 * max(n, 1))(*reuse), cache.data_ptr(), cache.numel(), torch.cuda.current_stream().cuda_stream)
+        return x32
+
+    # ---- guidance plan (include/scail_dit.h "guidance plan") ----
+    def guidance_bytes(self, T, H, W) -> int:
+        n = L.load().scail_dit_guidance_bytes(T, H, W)
+        if n < 0:
+            raise L.ScailHipError(f"scail_dit_guidance_bytes: bad shape (T {T}, H {H}, W {W})")
+        return n
+
+    def _delta_for(self, T, H, W, device) -> torch.Tensor:
+        """The delta buffer of a (T, H, W) latent, a new one when the shape or the device changed.  Handed out by ``_ws_for`` and kept beside
+        the workspace, as ``_cache_for`` does."""
+        key = (T, H, W, torch.device(device))
+        if self._delta is None or self._delta[0] != key:
+            ws, self._ws = self._ws, None
+            try:
+                buf = self._ws_for(self.guidance_bytes(T, H, W), device, f"scail_dit_guidance_bytes (T {T}, H {H}, W {W})")
+            finally:
+                self._ws = ws
+            self._delta = (key, buf)
+        return self._delta[1]
+
+    def guidance_delta(self, T, H, W) -> torch.Tensor:
+        """v_c - v_u (1, T, 16, H, W) fp32 as the last PAIR step of sample_guided left it: a view of the delta buffer"""
+        assert self._delta is not None and self._delta[0][:3] == (T, H, W), "no delta buffer of this shape"
+        return self._delta[1][:4 * T * 16 * H * W].view(torch.float32).view(1, T, 16, H, W)
+
+    def step_branch(self, x32, t32, cond: Dict, elem: int, ref, pose, cos, sin, mode=None, n_char: int = 1, cache=None) -> torch.Tensor:
+        """One branch of the CFG pair as an evaluation (scail_dit_step_branch): x32 (1,T,16,H,W), t32 (1,), under element ``elem`` of the
+        conditioning ``cond`` (any batch).  ``mode``: None, or "fill" / "reuse" on slot ``elem`` of the step cache of the PAIR -- the one this
+        object keeps for (2, T, H, W), or a caller-owned uint8 tensor ``cache`` of at least step_cache_bytes(2, T, H, W)."""
+        if mode is not None and mode not in L.CACHE_MODES:
+            raise L.ScailHipError(f"step_branch: mode must be None or one of {sorted(L.CACHE_MODES)}, got {mode!r}")
+        B, T, _, H, W = x32.shape
+        if B != 1 or t32.numel() != 1:
+            raise L.ScailHipError(f"step_branch: a branch is ONE latent and ONE timestep, got batch {B} and {t32.numel()} timestep(s)")
+        if mode is not None and cache is None:
+            cache = self._cache_for(2, T, H, W, x32.device, mode == "fill")
+        ws = self._ws_for(self.workspace_bytes(1, T, H, W, n_char), x32.device, "scail_dit_chars_workspace_bytes")
+        cc = _cond_struct(cond)
+        out = torch.empty(1, T, 16, H, W, device=x32.device, dtype=torch.float32)
+        assert ref.shape[0] == 1 and pose.shape[0] == 1
+        L.call("scail_dit_step_branch", self._h, x32.data_ptr(), t32.data_ptr(), C.byref(cc), cond["k_text"].shape[1], int(elem), ref.data_ptr(),
+               pose.data_ptr(), n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), out.data_ptr(), T, H, W, ws.data_ptr(), ws.numel(),
+               0 if mode is None else L.CACHE_MODES[mode], None if cache is None else cache.data_ptr(), 0 if cache is None else cache.numel(),
+               torch.cuda.current_stream().cuda_stream)
+        return out
+
+    def sample_guided(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose, cos, sin, guide, reuse=None, n_char: int = 1) -> torch.Tensor:
+        """``sample`` under a guidance plan (scail_dit_sample_guided): ``guide`` = one entry per step out of lib.GUIDE_PAIR / _DELTA / _COND
+        (sampler.plan_guidance); ``reuse``: None, or the step cache's 0 / 1 plan (sampler.merge_guidance_with_step_cache makes the two
+        agree).  Still ONE call that only enqueues.  A plan of COND entries alone takes no delta buffer."""
+        _, T, _, H, W = x32.shape
+        ts, dsa, n = self._schedule(sigmas, x32.device)
+        guide = [int(v) for v in guide]
+        if len(guide) != n:
+            raise L.ScailHipError(f"sample_guided: the guidance plan needs one entry per step ({n}), got {len(guide)}")
+        if any(v < 0 or v > 255 for v in guide):
+            raise L.ScailHipError(f"sample_guided: the guidance plan holds entries 0 / 1 / 2, got {guide}")
+        if reuse is not None:
+            reuse = [int(v) for v in reuse]
+            if len(reuse) != n:
+                raise L.ScailHipError(f"sample_guided: the reuse mask needs one entry per step ({n}), got {len(reuse)}")
+            if any(v < 0 or v > 255 for v in reuse):
+                raise L.ScailHipError(f"sample_guided: the reuse mask holds 0 / 1 entries, got {reuse}")
+        delta = self._delta_for(T, H, W, x32.device) if any(v != L.GUIDE_COND for v in guide) else None
+        cache = self._cache_for(2, T, H, W, x32.device, True) if reuse is not None else None
+        ws = self._ws_for(L.load().scail_dit_sample_chars_workspace_bytes(self._h, T, H, W, n_char), x32.device,
+                          f"scail_dit_sample_chars_workspace_bytes (T {T}, H {H}, W {W}, n_char {n_char})")
+        cc = _cond_struct(cond)
+        assert x32.is_contiguous() and x32.dtype == torch.float32 and ref.shape[0] == 1 and pose.shape[0] == 1
+        L.call("scail_dit_sample_guided", self._h, x32.data_ptr(), ts.data_ptr(), C.cast(dsa, C.c_void_p), n, float(cfg_scale),
+               C.byref(cc), ref.data_ptr(), pose.data_ptr(), n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), T, H, W,
+               ws.data_ptr(), ws.numel(), (C.c_uint8 * max(n, 1))(*guide), None if delta is None else delta.data_ptr(),
+               0 if delta is None else delta.numel(), None if reuse is None else (C.c_uint8 * max(n, 1))(*reuse),
+               None if cache is None else cache.data_ptr(), 0 if cache is None else cache.numel(), torch.cuda.current_stream().cuda_stream)
         return x32
 
     def time_distances(self, timesteps, signal: str = "time") -> torch.Tensor:

@@ -614,16 +614,21 @@ class DiffusionTransformer(nn.Module):
         cos, sin = self._rope(T_rope, x32.shape[3] // 2, x32.shape[4] // 2, 0, 0, dev, n_char)
         return self._executor(), cond, cos, sin, x32.float().contiguous().clone()
 
-    def sample_c(self, x32, sigmas, cfg_scale, ctx, ref, pose, clip, cond_key=None, reuse=None):
+    def sample_c(self, x32, sigmas, cfg_scale, ctx, ref, pose, clip, cond_key=None, reuse=None, guide=None):
         """The whole RFSampler Euler loop as ONE C call (scail_dit_sample_chars, include/scail_dit.h): x32 (1,T,16,H,W) fp32,
         ctx (2, Lt, text_dim) = [uncond; cond], ref (1,C,16,H,W), pose (1,C*T,16,H/2,W/2) for C >= 1 characters (C = ref.shape[1]),
         clip (1,Lc,1280).  Single rank.  ``reuse``: None, or the step cache's plan -- one 0 / 1 per step, 1 = reuse the block residual
-        of the last computed step (scail_dit_sample_cached)."""
+        of the last computed step (scail_dit_sample_cached).  ``guide``: None, or the guidance plan -- one lib.GUIDE_* entry per step
+        (sampler.plan_guidance; scail_dit_sample_guided), alone or together with ``reuse``."""
         T, n_char, dev = x32.shape[1], ref.shape[1], x32.device
         self._check_chars(n_char, T, pose.shape[1])
         if reuse is not None:
             self._step_cache_ok()
+        if guide is not None:
+            self._step_cache_ok("guidance")
         ex, cond, cos, sin, x = self._sample_prelude(x32, ctx, clip, cond_key, T, n_char)
+        if guide is not None:
+            return ex.sample_guided(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, guide, reuse=reuse, n_char=n_char)
         if reuse is not None:
             return ex.sample_cached(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, reuse, n_char=n_char)
         return ex.sample(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, n_char=n_char)

@@ -58,13 +58,23 @@ class SATVideoDiffusionEngine(nn.Module):
     @torch.no_grad()
     def sample(self, cond: Dict, uc: Optional[Dict] = None, batch_size: int = 1, shape: Union[None, Tuple, List] = None,
                prefix=None, concat_images=None, ofs=None, fps=None, tile_indices=None,
-               generator: Optional[torch.Generator] = None, num_steps: Optional[int] = None, fused: bool = True, step_cache=None, **kwargs):
+               generator: Optional[torch.Generator] = None, num_steps: Optional[int] = None, fused: bool = True, step_cache=None, guidance=None,
+               **kwargs):
         """diffusion_video.py:456-587.  shape = (T, C, H, W).  Noise is drawn in fp32 on the host RNG
         stream of ``generator`` like ``torch.randn(batch, *shape)`` (:470), broadcast inside the
         sequence-parallel group (:486-493) and H/W-chunked (:495-552); result gathered to SP rank 0 (:571-585).
         ``step_cache``: None, or the step-cache option of RFSampler.sample_hip (an extension, opt-in; fused HIP network, one rank).  With
         ``tile_indices`` it reaches RFSamplerLong.sample_hip: one plan for every tile and one block residual per tile, for the requests
-        that take the one-call tiled loop; the sampler refuses the others (a callback, several characters, tiles above 64 frames)."""
+        that take the one-call tiled loop; the sampler refuses the others (a callback, several characters, tiles above 64 frames).
+        ``guidance``: None, or the guidance option of RFSampler.sample_hip (an extension, opt-in; fused HIP network, one rank, no temporal
+        tiles): which steps run the CFG pair, the cond branch with the stored delta, or the cond branch alone."""
+        if guidance is not None:
+            if not (fused and isinstance(self.network, DiffusionTransformer)):
+                raise NotImplementedError("guidance needs the fused path of the HIP network (RFSampler.sample_hip)")
+            if self.sp is not None and self.sp.size > 1:
+                raise NotImplementedError("guidance runs on a single rank only: the sequence-parallel calls have no guided form")
+            if tile_indices is not None:
+                raise NotImplementedError("guidance with temporal tiles (tile_indices, RFSamplerLong) is out of scope: the tiled loops keep no delta per tile")
         if step_cache is not None:
             if not (fused and isinstance(self.network, DiffusionTransformer)):
                 raise NotImplementedError("step_cache needs the fused path of the HIP network (RFSampler.sample_hip)")
@@ -94,6 +104,8 @@ class SATVideoDiffusionEngine(nn.Module):
             raise TypeError("tile_indices needs sampler_config.target = RFSamplerLong")
         if step_cache is not None:
             extra["step_cache"] = step_cache
+        if guidance is not None:
+            extra["guidance"] = guidance
         if fused and isinstance(self.network, DiffusionTransformer):
             samples = self.sampler.sample_hip(self.network, randn, cond, uc, num_steps=num_steps, chunk_dim=chunk_dim, **extra)
         else:

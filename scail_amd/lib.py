@@ -52,6 +52,9 @@ SIGNATURES = {
     "scail_patchify_chars": [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
     "scail_unpatchify": [_p, _p, _i64, _i64, _i64, _i64, _p],
     "scail_cfg_euler": [_p, _p, _i64, _f, _f, _p],
+    # the guidance plan's fp32 passes: v_c - v_u stored, and the Euler update around a stored delta (NULL: no guidance)
+    "scail_cfg_delta_store": [_p, _p, _i64, _p],
+    "scail_cfg_euler_delta": [_p, _p, _p, _i64, _f, _f, _p],
     "scail_tile_gather": [_p, _p, _p, _i64, _i64, _i64, _p],
     "scail_tile_blend_acc": [_p, _p, _p, _p, _i64, _i64, _i64, _f, _p],
     "scail_tile_finish": [_p, _p, _p, _i64, _i64, _f, _p],
@@ -134,6 +137,12 @@ SIGNATURES = {
     "scail_dit_sample_tiled_cache_bytes": [_p, _i64, _i64, _i64, _i64],
     "scail_dit_sample_tiled_cached": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i64,
                                       _p, _p, _i64, _p],
+    # the guidance plan: one branch of the pair (cond, cond_batch, elem; mode, cache, cache bytes) and the sampler loop with a plan
+    # (host uint8 guide, delta, delta bytes, host uint8 reuse or NULL, cache, cache bytes)
+    "scail_dit_step_branch": [_p, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _i64, _i, _p, _i64, _p],
+    "scail_dit_guidance_bytes": [_i64, _i64, _i64],
+    "scail_dit_sample_guided": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64,
+                                _p, _p, _i64, _p],
     "scail_dit_time_distances_bytes": [_p, _i],
     "scail_dit_time_distances": [_p, _p, _i64, _i, _p, _p, _i64, _p],
     # include/scail_vae.h (scail_amd/cvae.py builds the structs)
@@ -173,6 +182,8 @@ GEMM_PRECISIONS = ("fp8", "fp6")
 # include/scail_dit.h SCAIL_DIT_CACHE_*: the modes of scail_dit_step_cached; the signals of scail_dit_time_distances
 CACHE_MODES = {"fill": 1, "reuse": 2}
 CACHE_SIGNALS = {"time": 0, "modulation": 1}
+# include/scail_dit.h SCAIL_DIT_GUIDE_*: the entries of a guidance plan (scail_dit_sample_guided)
+GUIDE_PAIR, GUIDE_DELTA, GUIDE_COND = 0, 1, 2
 # include/scail_hip.h scail_resize_crop_aa: source layouts, and the largest in / out per axis its tap budget covers
 SRC_U8_NHWC, SRC_F32_NCHW = 0, 1
 RESIZE_MAX_SCALE = 16
@@ -188,7 +199,9 @@ ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- sc
                          # and the step cache, scail_resid_store / scail_resid_apply / scail_abs_diff_sums / scail_dit_step_cache_bytes /
                          # scail_dit_step_cached / scail_dit_sample_cached / scail_dit_time_distances / scail_dit_time_distances_bytes,
                          # and the 6-bit GEMMs, scail_quant_mxfp6_rows / scail_gemm_mxfp6 / scail_dit_fp6_weight_bytes / scail_dit_enable_fp6,
-                         # and the tiled step cache, scail_dit_sample_tiled_cache_bytes / scail_dit_sample_tiled_cached)
+                         # and the tiled step cache, scail_dit_sample_tiled_cache_bytes / scail_dit_sample_tiled_cached,
+                         # and the guidance plan, scail_cfg_delta_store / scail_cfg_euler_delta / scail_dit_step_branch /
+                         # scail_dit_guidance_bytes / scail_dit_sample_guided)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);

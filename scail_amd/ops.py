@@ -533,6 +533,31 @@ def cfg_euler_(x, v, cfg_scale, dsigma):
     return x
 
 
+def cfg_delta_store(v, out=None):
+    """delta = v[1] - v[0] (scail_cfg_delta_store): v fp32 (2, ...), only read; delta fp32 of v[0]'s shape (``out``, or a new tensor)."""
+    _chk(v, f32, "cfg_delta_store.v")
+    assert v.is_contiguous() and v.shape[0] == 2
+    if out is None:
+        out = torch.empty_like(v[0])
+    _chk(out, f32, "cfg_delta_store.out")
+    assert out.is_contiguous() and 2 * out.numel() == v.numel()
+    L.call("scail_cfg_delta_store", v.data_ptr(), out.data_ptr(), out.numel(), _stream())
+    return out
+
+
+def cfg_euler_delta_(x, v_c, delta, cfg_scale, dsigma):
+    """In place: x = x + dsigma * (v_c + (cfg - 1) * delta), every operation rounded on its own (scail_cfg_euler_delta); ``delta`` None:
+    x = x + dsigma * v_c.  x, v_c, delta fp32 of one size; cfg - 1 is formed in fp32 by the library."""
+    _chk(x, f32, "cfg_euler_delta.x"); _chk(v_c, f32, "cfg_euler_delta.v_c")
+    assert x.is_contiguous() and v_c.is_contiguous() and v_c.numel() == x.numel()
+    if delta is not None:
+        _chk(delta, f32, "cfg_euler_delta.delta")
+        assert delta.is_contiguous() and delta.numel() == x.numel()
+    L.call("scail_cfg_euler_delta", x.data_ptr(), v_c.data_ptr(), None if delta is None else delta.data_ptr(), x.numel(), float(cfg_scale),
+           float(dsigma), _stream())
+    return x
+
+
 # ---- temporal tiling (RFSamplerLong): the frame indices / weights are HOST values that travel in the kernel arguments ----
 def _tile_frames(frames):
     import ctypes as C

@@ -184,6 +184,104 @@ def plan_step_cache(dist, threshold, coefficients=(1.0, 0.0), keep_first=1, keep
     return mask
 
 
+GUIDE_PAIR, GUIDE_DELTA, GUIDE_COND = 0, 1, 2          # include/scail_dit.h SCAIL_DIT_GUIDE_*
+GUIDANCE_KEYS = ("interval", "every", "modes")
+
+
+def check_guidance_plan(guide, reuse=None, what="guidance plan"):
+    """The rules scail_dit_sample_guided checks a plan by (include/scail_dit.h "guidance plan"), on the host: entries 0 / 1 / 2; a DELTA entry
+    has a PAIR entry before it; with a step-cache mask ``reuse`` (0 / 1 entries, reuse[0] == 0) a reusing step evaluates the same elements
+    as the last computing step (PAIR with PAIR, DELTA or COND with DELTA or COND).  Raises ValueError naming the index; returns the plan
+    as a list of ints."""
+    guide = [int(v) for v in guide]
+    seen_pair = False
+    for i, g in enumerate(guide):
+        if g not in (GUIDE_PAIR, GUIDE_DELTA, GUIDE_COND):
+            raise ValueError(f"{what}: entry {i} is {g} (an entry is 0 = pair, 1 = delta or 2 = cond)")
+        if g == GUIDE_DELTA and not seen_pair:
+            raise ValueError(f"{what}: entry {i} is 1 (delta) with no pair step before it: there is no stored delta to use")
+        seen_pair = seen_pair or g == GUIDE_PAIR
+    if reuse is not None:
+        reuse = [int(v) for v in reuse]
+        if len(reuse) != len(guide):
+            raise ValueError(f"{what}: the reuse mask needs one entry per step ({len(guide)}), got {len(reuse)}")
+        if any(v not in (0, 1) for v in reuse) or (reuse and reuse[0] != 0):
+            raise ValueError(f"{what}: the reuse mask holds 0 / 1 entries and starts with 0 (the first step has nothing to reuse), got {reuse}")
+        j = 0
+        for i, r in enumerate(reuse):
+            if not r:
+                j = i
+            elif (guide[i] == GUIDE_PAIR) != (guide[j] == GUIDE_PAIR):
+                raise ValueError(f"{what}: step {i} reuses (entry {guide[i]}) what step {j}, the last computing step, left (entry {guide[j]}): "
+                                 "they do not evaluate the same elements")
+    return guide
+
+
+def plan_guidance(sigmas, interval=None, every=1, modes=None):
+    """The guidance plan (include/scail_dit.h "guidance plan"): one entry per sampler step -- 0 = the batch-2 pair (guided; stores
+    v_c - v_u), 1 = the cond branch alone with the stored delta, 2 = the cond branch alone, no guidance.  Pure host; needs no device.
+
+    ``sigmas``: the STARTING sigma of every step, one value per step (``RFSampler.sigmas()[:-1]``).  ``interval`` = (lo, hi): step i is
+    inside when lo <= sigmas[i] <= hi (None: every step is inside).  Steps outside get 2.  Inside each maximal run of inside steps,
+    position p gets 0 when p % every == 0, else 1.  Example: 10 steps, the interval covering steps 2..7, every = 3 ->
+    [2, 2, 0, 1, 1, 0, 1, 1, 2, 2].  Explicit ``modes`` stand alone (no interval, every left at 1) and are checked as the library checks them
+    (check_guidance_plan).  No default interval or ``every`` is recommended: nothing has been measured on real weights."""
+    sig = [float(v) for v in sigmas]
+    n = len(sig)
+    if modes is not None:
+        if interval is not None or every != 1:
+            raise ValueError("plan_guidance: explicit 'modes' stand alone (interval and every make a plan from the schedule)")
+        modes = check_guidance_plan(modes, what="plan_guidance: modes")
+        if len(modes) != n:
+            raise ValueError(f"plan_guidance: 'modes' needs one entry per step ({n}), got {len(modes)}")
+        return modes
+    if isinstance(every, bool) or int(every) != every or every < 1:
+        raise ValueError(f"plan_guidance: every must be an integer >= 1, got {every!r}")
+    every = int(every)
+    lo, hi = -np.inf, np.inf
+    if interval is not None:
+        if len(interval) != 2:
+            raise ValueError(f"plan_guidance: interval is (lo, hi), got {interval!r}")
+        lo, hi = float(interval[0]), float(interval[1])
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError(f"plan_guidance: the interval's bounds must be finite, got ({lo}, {hi})")
+        if lo > hi:
+            raise ValueError(f"plan_guidance: the interval needs lo <= hi, got ({lo}, {hi})")
+    plan, p = [], 0
+    for v in sig:
+        if lo <= v <= hi:
+            plan.append(GUIDE_PAIR if p % every == 0 else GUIDE_DELTA)
+            p += 1
+        else:
+            plan.append(GUIDE_COND)
+            p = 0
+    return plan
+
+
+def merge_guidance_with_step_cache(guide, reuse):
+    """A guidance plan made to agree with a step-cache plan ``reuse`` (plan_step_cache): a reusing step takes the entry of the last computing
+    step, since it must find the residual slots that step filled.  A computing DELTA step whose PAIR steps were all replaced that way
+    becomes a PAIR step: it has no stored delta to use.  The result always passes check_guidance_plan(result, reuse).  Both inputs are
+    checked first (the guide on its own, the mask for 0 / 1 entries starting with 0)."""
+    guide = check_guidance_plan(guide, what="merge_guidance_with_step_cache: guide")
+    reuse = [int(v) for v in reuse]
+    if len(reuse) != len(guide):
+        raise ValueError(f"merge_guidance_with_step_cache: the reuse mask needs one entry per step ({len(guide)}), got {len(reuse)}")
+    if any(v not in (0, 1) for v in reuse) or (reuse and reuse[0] != 0):
+        raise ValueError(f"merge_guidance_with_step_cache: the reuse mask holds 0 / 1 entries and starts with 0, got {reuse}")
+    out, j, seen_pair = [], 0, False
+    for i, r in enumerate(reuse):
+        if r:
+            g = out[j]
+        else:
+            j, g = i, guide[i]
+            if g == GUIDE_DELTA and not seen_pair:
+                g = GUIDE_PAIR
+        seen_pair = seen_pair or g == GUIDE_PAIR
+        out.append(g)
+    return out
+
+
 STEP_CACHE_KEYS = ("threshold", "coefficients", "keep_first", "keep_last", "signal", "mask")
 
 
@@ -247,14 +345,33 @@ class RFSampler:
         return plan_step_cache(dist, step_cache["threshold"], step_cache.get("coefficients", (1.0, 0.0)), step_cache.get("keep_first", 1),
                                step_cache.get("keep_last", 1))
 
+    def guidance_plan(self, sig, guidance, reuse=None) -> list:
+        """The plan of a ``guidance`` option (sample_hip) for the host schedule ``sig`` (n_steps + 1 values): plan_guidance on the steps'
+        starting sigmas, merged with the step cache's plan ``reuse`` when there is one (explicit ``modes`` are not rewritten: they must
+        agree with it as they stand)."""
+        if not isinstance(guidance, dict) or not guidance or any(k not in GUIDANCE_KEYS for k in guidance):
+            raise ValueError(f"guidance must be None or a dict with keys out of {GUIDANCE_KEYS}, got {guidance!r}")
+        plan = plan_guidance([float(v) for v in sig[:-1]], guidance.get("interval"), guidance.get("every", 1), guidance.get("modes"))
+        if reuse is None:
+            return plan
+        if guidance.get("modes") is not None:
+            return check_guidance_plan(plan, reuse, what="guidance: modes")
+        return merge_guidance_with_step_cache(plan, reuse)
+
     def sample_hip(self, network, x, cond: Dict, uc: Dict, num_steps=None, scale=None, chunk_dim=None,
-                   step_callback=None, step_cache=None):
+                   step_callback=None, step_cache=None, guidance=None):
         """x (1,T,16,H,W) fp32 on the GPU; cond/uc as the CLI builds them (sample_video.py:455-470).
         One step = one batch-2 DiT forward (uncond, cond) + scail_cfg_euler.
         ``step_cache`` (opt-in, an extension; None = this method as it was): a dict with ``threshold`` and optionally ``coefficients``,
         ``keep_first``, ``keep_last``, ``signal`` (plan_step_cache / step_cache_plan), or an explicit ``mask`` of one 0 / 1 per step.  A step
         planned 1 skips the blocks and adds the block residual of the last computed step to its own embedded tokens
-        (include/scail_dit.h "step cache").  Both routes below take the plan and give the same bits.  ``self.last_step_cache_plan`` keeps it."""
+        (include/scail_dit.h "step cache").  Both routes below take the plan and give the same bits.  ``self.last_step_cache_plan`` keeps it.
+        ``guidance`` (opt-in, an extension; None = this method as it was): a dict with ``interval`` = (lo, hi) and / or ``every``, or explicit
+        ``modes`` (plan_guidance): which steps run the batch-2 pair, which the cond branch alone with the stored v_c - v_u, which the cond
+        branch alone without guidance (include/scail_dit.h "guidance plan").  Combines with ``step_cache`` (merge_guidance_with_step_cache).
+        Both routes take the plan and give the same bits, provided the conditioning GEMMs compute a row of the cond prompt alone as they
+        compute it in the batch of two (they do wherever both sizes take one kernel: scail_gemm_kernel_name_for).
+        ``self.last_guidance_plan`` keeps it."""
         sig = self.sigmas(num_steps)                     # host fp32, like the reference
         cfg = float(self.guider.scale if scale is None else scale)
         ctx = torch.cat((uc["crossattn"], cond["crossattn"]), 0)
@@ -265,22 +382,44 @@ class RFSampler:
                 raise NotImplementedError("step_cache runs in the C executor on a single rank only: not on sequence-parallel ranks (chunk_dim), not "
                                           "with SCAIL_C_STEP=0, _tap or kernel_timer")
             plan = self.last_step_cache_plan = self.step_cache_plan(network, sig, step_cache)
+        gplan = None
+        if guidance is not None:
+            if chunk_dim is not None or not _executor_takes_loop(network):
+                raise NotImplementedError("guidance runs in the C executor on a single rank only: not on sequence-parallel ranks (chunk_dim), not "
+                                          "with SCAIL_C_STEP=0, _tap or kernel_timer")
+            if x.shape[0] != 1 or shared["ref_concat"].shape[0] != 1 or shared["concat_smpl_render"].shape[0] != 1:
+                raise NotImplementedError("guidance takes one latent with one shared ref / pose (the cond branch is a batch-1 evaluation)")
+            gplan = self.last_guidance_plan = self.guidance_plan(sig, guidance, plan)
         if (_executor_takes_loop(network) and step_callback is None and chunk_dim is None
                 and shared["ref_concat"].shape[0] == 1 and shared["concat_smpl_render"].shape[0] == 1):
             # the whole loop enqueued by ONE call into the library (scail_dit_sample_chars; any number of reference frames / pose
             # streams); same kernels, same order
+            if gplan is not None:
+                return network.sample_c(x, sig, cfg, ctx, shared["ref_concat"], shared["concat_smpl_render"],
+                                        shared["image_clip_features"], cond_key=("sample_hip", id(cond)), reuse=plan, guide=gplan)
             if plan is not None:
                 return network.sample_c(x, sig, cfg, ctx, shared["ref_concat"], shared["concat_smpl_render"],
                                         shared["image_clip_features"], cond_key=("sample_hip", id(cond)), reuse=plan)
             return network.sample_c(x, sig, cfg, ctx, shared["ref_concat"], shared["concat_smpl_render"],
                                     shared["image_clip_features"], cond_key=("sample_hip", id(cond)))
         x = x.float().contiguous().clone()
+        delta = torch.empty_like(x) if gplan is not None and any(g != GUIDE_COND for g in gplan) else None
         for i in range(len(sig) - 1):
-            xin = torch.cat([x, x], 0)
             t = (sig[i] * 1000.0).repeat(2).to(x.device)                 # c_noise = 1000 sigma (RFScaling)
             if plan is not None:
                 shared["step_cache"] = "reuse" if plan[i] else "fill"
+            if gplan is not None and gplan[i] != GUIDE_PAIR:
+                # the cond branch alone: a batch-1 evaluation under the cond prompt (the network keeps ONE conditioning: a change between
+                # pair and branch steps computes it again -- this is the instrumented route)
+                v = network.forward_f32(x, t[:1], ctx[1:2], None, cond_key=("sample_hip", id(cond), "cond"), chunk_dim=chunk_dim, **shared)
+                ops.cfg_euler_delta_(x, v, delta if gplan[i] == GUIDE_DELTA else None, cfg, float(sig[i + 1] - sig[i]))
+                if step_callback is not None:
+                    step_callback(i, x)
+                continue
+            xin = torch.cat([x, x], 0)
             v = network.forward_f32(xin, t, ctx, None, cond_key=("sample_hip", id(cond)), chunk_dim=chunk_dim, **shared)
+            if gplan is not None:
+                ops.cfg_delta_store(v, out=delta)
             ops.cfg_euler_(x, v, cfg, float(sig[i + 1] - sig[i]))
             if step_callback is not None:
                 step_callback(i, x)
@@ -372,7 +511,7 @@ class RFSamplerLong(RFSampler):
         return idxs, tile_w, 1.0 / wsum
 
     def sample_hip(self, network, x, cond: Dict, uc: Dict, num_steps=None, scale=None, chunk_dim=None,
-                   step_callback=None, tile_indices=None, step_cache=None):
+                   step_callback=None, tile_indices=None, step_cache=None, guidance=None):
         """Fused path for the HIP network: per step and tile one batch-2 DiT forward (fp32 out); the text / CLIP
         conditioning (step- AND tile-invariant) is computed once per request.
         ``step_cache`` (opt-in; None = this method as it was): RFSampler.sample_hip's option.  One plan for every tile -- it depends on the
@@ -380,6 +519,9 @@ class RFSamplerLong(RFSampler):
         one-call route below have a cached form (``_one_call_ok``); every other one is refused before the network is touched: there is no
         cached host loop.  ``self.last_step_cache_plan`` keeps the plan."""
         self._check(tile_indices)
+        if guidance is not None:
+            raise NotImplementedError("guidance with temporal tiles (RFSamplerLong) is out of scope: the tiled loops (scail_dit_sample_tiled*) keep "
+                                      "no delta per tile; sample the clip in one window or drop the option")
         smpl_tiled = cond.get("smpl_tiled")
         if step_cache is not None:
             ref = cond.get("ref_concat")
