@@ -521,6 +521,60 @@ int scail_dit_sample_guided(scail_dit* h, float* x, const float* timesteps, cons
                             void* workspace, int64_t workspace_bytes, const uint8_t* guide, void* delta, int64_t delta_bytes,
                             const uint8_t* reuse, void* cache, int64_t cache_bytes, void* stream);
 
+/*
+ * ---- solver plan (an EXTENSION, opt-in: a linear multistep solver in place of the Euler update) -------------------------------------------
+ * Every other extension shortens a step; this one is about the NUMBER of steps.  Rectified flow: x_sigma = (1 - sigma) x0 + sigma eps,
+ * the network gives v = eps - x0, the guided velocity is d = v_u + s (v_c - v_u) and Euler is x <- x + (sigma' - sigma) d.  The data
+ * prediction at step i is D_i = x_i - sigma_i d_i.  With alpha = 1 - sigma, lambda = log(alpha / sigma), h_i = lambda_{i+1} - lambda_i and
+ * r_i = h_{i-1} / h_i, DPM-Solver++(2M) for the step sigma_i -> sigma_{i+1} is
+ *     x_{i+1} = (sigma_{i+1} / sigma_i) x_i - alpha_{i+1} expm1(-h_i) [D_i + (1 / (2 r_i)) (D_i - D_{i-1})],
+ * and for this parametrisation -alpha_{i+1} expm1(-h_i) = 1 - sigma_{i+1} / sigma_i exactly.  So with rho = sigma_{i+1} / sigma_i every
+ * step is x_{i+1} = a x_i + b D_i + c D_{i-1}: first order (a, b, c) = (rho, 1 - rho, 0), second order
+ * (rho, (1 - rho)(1 + 1 / (2 r_i)), -(1 - rho) / (2 r_i)); a + b + c = 1.  First order is Euler mathematically, not in bits.  A step is
+ * second order only where i >= 1 and lambda_{i-1}, lambda_i, lambda_{i+1} are finite: a schedule from sigma = 1 to sigma = 0 has steps
+ * 0, 1 and the last one first order, and its last step is x = 0 x + 1 D.  A second-order step needs no further network evaluation: one
+ * fp32 pass over the latent (scail_cfg_multistep, scail_hip.h) and one fp32 latent of history.  The coefficients depend on the sigma
+ * schedule alone, so the plan exists before the loop and the sampler stays ONE call with no host synchronisation.  These entry points
+ * take a coefficient TABLE, not a solver's name: scail_amd/sampler.py plan_solver makes the table ("dpmpp2m", and "dpm1" = first-order
+ * rows everywhere); another solver of the form a x + b D_i + c D_{i-1} is host-only work.  Nothing here changes an existing entry point,
+ * its launches, its workspace query or its result.  No step count is recommended: nothing has been measured on real weights.
+ *
+ * scail_dit_solver_bytes: bytes of the caller-owned, 256-byte aligned history buffer: fp32 [T * 16 * H * W], rounded up to 256 (-1: a bad
+ *   shape: T, H or W outside 1..32767, H or W no multiple of 4).  For the tiled call T is the FULL latent's frame count.
+ *
+ * scail_dit_sample_solver: scail_dit_sample_chars + (sigma, coef, hist, hist_bytes).  sigma = HOST fp32 [n_steps], the steps' STARTING
+ *   sigmas; coef = HOST fp32 [n_steps][3] = (a, b, c) per step; both are read during the call.  Step i is scail_dit_sample_chars' [x; x]
+ *   copy and evaluation with SCAIL_DIT_CFG_PAIR, then scail_cfg_multistep(x, v, hist, n, cfg_scale, sigma[i], coef[i][0], coef[i][1],
+ *   coef[i][2], use_prev = coef[i][2] != 0) in place of scail_cfg_euler; dsigma is checked as there and not used.  The workspace is
+ *   scail_dit_sample_chars_workspace_bytes'.  hist need not be initialised: step 0 writes it before any step reads it; after the call it
+ *   holds the last step's D.  The call only enqueues, nothing synchronises, and it is capturable on the same terms as scail_dit_sample.
+ *
+ * scail_dit_sample_tiled_solver: scail_dit_sample_tiled + the same four, hist being that of the FULL latent [T * 16 * H * W].  The loop is
+ *   scail_dit_sample_tiled's, except that scail_tile_finish_multistep (scail_hip.h) finishes the step in place of scail_tile_finish: the
+ *   update happens once per step, after the blend, so one history serves every tile.
+ *
+ * Both refuse before anything is enqueued, x and hist untouched, naming the index and the value: a sigma or a coefficient that is not
+ * finite; coef[0][2] != 0 (step 0 has no history); a null sigma or coef with n_steps > 0; a hist that is null, not 256-byte aligned or
+ * smaller than scail_dit_solver_bytes; and everything their Euler twins refuse, in the twins' wording.
+ *
+ * Cost: the pass moves 5 to 6 floats per latent element next to a network evaluation of seconds; it does not matter to the time of a
+ * step.  What the feature is for is the step count (README "solver plan" has what was measured).
+ *
+ * Out of scope, each refused by name in the Python layers: a solver plan together with the step cache or the guidance plan (the natural
+ * follow-up; it needs the pass to take v_c + g delta in place of [v_u; v_c]), the sequence-parallel calls, UniPC and other correctors.
+ */
+int64_t scail_dit_solver_bytes(int64_t T, int64_t H, int64_t W);
+int scail_dit_sample_solver(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                            const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose, int64_t n_char, int64_t pose_frames,
+                            const float* rope_cos, const float* rope_sin, int64_t T, int64_t H, int64_t W,
+                            void* workspace, int64_t workspace_bytes, const float* sigma, const float* coef, void* hist, int64_t hist_bytes,
+                            void* stream);
+int scail_dit_sample_tiled_solver(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                                  const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose_tiles,
+                                  const int32_t* tile_frames, const float* tile_w, const float* inv_wsum, int64_t n_tiles, int64_t T, int64_t Tt,
+                                  const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
+                                  const float* sigma, const float* coef, void* hist, int64_t hist_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

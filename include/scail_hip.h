@@ -48,7 +48,9 @@ const char* scail_last_error(void);
  * scail_resid_apply / scail_abs_diff_sums and scail_dit.h's scail_dit_step_cache_bytes / scail_dit_step_cached / scail_dit_sample_cached /
  * scail_dit_time_distances / scail_dit_time_distances_bytes, and for the 6-bit GEMMs, scail_quant_mxfp6_rows / scail_gemm_mxfp6 and
  * scail_dit.h's scail_dit_fp6_weight_bytes / scail_dit_enable_fp6, and for the guidance plan, scail_cfg_delta_store / scail_cfg_euler_delta
- * and scail_dit.h's scail_dit_step_branch / scail_dit_guidance_bytes / scail_dit_sample_guided.) */
+ * and scail_dit.h's scail_dit_step_branch / scail_dit_guidance_bytes / scail_dit_sample_guided, and for the solver plan,
+ * scail_cfg_multistep / scail_tile_finish_multistep and scail_dit.h's scail_dit_solver_bytes / scail_dit_sample_solver /
+ * scail_dit_sample_tiled_solver.) */
 int scail_abi_version(void);
 
 /* ---- epilogues of scail_gemm_bf16 ---------------------------------------------------------- */
@@ -386,6 +388,24 @@ int scail_cfg_delta_store(const float* v, float* delta, int64_t n, void* stream)
 int scail_cfg_euler_delta(float* x, const float* v_c, const float* delta, int64_t n, float cfg_scale, float dsigma, void* stream);
 
 /*
+ * The fp32 pass of the solver plan (scail_dit.h "solver plan"): classifier-free guidance and ONE step of a linear multistep solver in the
+ * data prediction, x <- a x + b D + c D_prev.  v = [v_u; v_c] fp32 [2, n], only read; x and hist fp32 [n], updated in place.  Per
+ * element, in this order:
+ *   d = v_u + cfg_scale * (v_c - v_u)
+ *   D = x - sigma * d                      the data prediction of rectified flow at the step's STARTING sigma
+ *   y = a * x + b * D
+ *   y = y + c * hist                       only with use_prev != 0
+ *   x = y;  hist = D
+ * EVERY operation is rounded on its own (no fused multiply-add), as in scail_cfg_euler_delta: the call gives the bits of the torch fp32
+ * expression, one tensor operation per arithmetic operation.  With use_prev == 0 hist is never READ -- it may hold anything, NaN
+ * included -- and is written all the same.  Elementwise: one thread reads, then writes, its own elements; 16-byte accesses where x, v
+ * and hist are 16-byte aligned, with a scalar tail.  a, b, c are the caller's (scail_amd/sampler.py plan_solver).
+ * Errors (host side, naming the value): n < 0 or 2^31 workgroups or more; with n > 0 a null x, v or hist.  n == 0 launches nothing.
+ */
+int scail_cfg_multistep(float* x, const float* v, float* hist, int64_t n, float cfg_scale, float sigma, float a, float b, float c,
+                        int use_prev, void* stream);
+
+/*
  * Temporal tiling of RFSamplerLong (sampling.py:986-1085): the three elementwise fp32 passes of one sampler step around the network
  * evaluations of its tiles.  A latent frame is F = 16*H*W floats, x / den are [T, F], a tile has Tt <= min(T, 64) frames f_0 .. f_{Tt-1}
  * of [0, T) in any order.  `frames`, `wk` and `inv_wsum` are HOST arrays read during the call: their values travel in the kernel
@@ -403,6 +423,14 @@ int scail_tile_gather(const float* x, float* xin, const int32_t* frames, int64_t
 int scail_tile_blend_acc(float* den, const float* v, const int32_t* frames, const float* wk, int64_t Tt, int64_t T, int64_t F,
                          float cfg_scale, void* stream);
 int scail_tile_finish(float* x, float* den, const float* inv_wsum, int64_t T, int64_t F, float dsigma, void* stream);
+/*
+ * scail_tile_finish under a solver plan (scail_dit.h "solver plan"): scail_cfg_multistep's sequence from "D = x - sigma * d" on, with
+ * d = den[f, e] * inv_wsum[f], the product scail_tile_finish forms; then den[f, e] = 0.  x, den, hist fp32 [T, F]; inv_wsum a HOST array
+ * that travels in the kernel arguments; the same limits on T and F, the same errors, and a null hist.  Every operation is rounded on
+ * its own; with use_prev == 0 hist is never read.  16-byte accesses where F % 4 == 0 and x, den and hist are 16-byte aligned.
+ */
+int scail_tile_finish_multistep(float* x, float* den, const float* inv_wsum, float* hist, int64_t T, int64_t F, float sigma, float a, float b,
+                                float c, int use_prev, void* stream);
 
 
 /* ---- Wan2.1 causal 3D VAE (sgm/models/wan_vae.py), channels-last (T,H,W,C) bf16 activations ------------- */

@@ -322,6 +322,31 @@ def format_guidance_plan(plan):
             f"branch with the last stored delta, {n_cond} the cond branch without guidance")
 
 
+SOLVER_CHOICES = ("euler", "dpmpp2m")
+
+
+def solver_args(solver, step_cache=None, guidance=None):
+    """``--solver`` -> the ``solver`` option of RFSampler.sample_hip: None for "euler" (the route as it was), else the name.  A solver
+    goes with neither the step cache nor the guidance plan."""
+    if solver is None or solver == "euler":
+        return None
+    if solver not in SOLVER_CHOICES:
+        raise ValueError(f"--solver must be one of {SOLVER_CHOICES}, got {solver!r}")
+    if step_cache is not None:
+        raise ValueError(f"--solver {solver} does not go with --step-cache-threshold: the solver's pass takes the pair of a full step")
+    if guidance is not None:
+        raise ValueError(f"--solver {solver} does not go with --cfg-interval / --cfg-delta-every / --cfg-plan: the solver's pass takes the "
+                         "pair of a full step")
+    return solver
+
+
+def format_solver_plan(plan, solver="dpmpp2m"):
+    """The table as text: which steps are second order, and k of n"""
+    second = [i for i, row in enumerate(plan) if row[2] != 0.0]
+    return (f"solver plan ({solver}): {len(second)} of {len(plan)} steps are second order ({', '.join(map(str, second))}); the others are "
+            "first order (no usable history, or a step that starts at sigma = 1 or ends at sigma = 0)")
+
+
 def format_step_cache_plan(plan):
     """The plan as text: which steps compute, and k of n"""
     computed = [i for i, v in enumerate(plan) if not v]
@@ -353,8 +378,11 @@ def _calibrate(engine, c, uc, shape, steps, fp8_max_error):
 
 
 def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frames=None, engine=None, tile_frames=None, tile_overlap=None,
-        vae_chunk_frames=None, postprocess="torch", fp8_max_error=None, step_cache=None, guidance=None):
-    """``guidance``: None, or the guidance option (guidance_args; RFSampler.sample_hip): which steps run the CFG pair, the cond branch with
+        vae_chunk_frames=None, postprocess="torch", fp8_max_error=None, step_cache=None, guidance=None, solver=None):
+    """``solver``: None (the Euler loop as it was), or "dpmpp2m" (solver_args; RFSampler.sample_hip / RFSamplerLong.sample_hip): a second-order
+    multistep update in the data prediction, still one executor call: one window, several characters, temporal tiles.  One rank; not with
+    ``step_cache`` or ``guidance``.  The plan is printed.
+    ``guidance``: None, or the guidance option (guidance_args; RFSampler.sample_hip): which steps run the CFG pair, the cond branch with
     the stored delta, or the cond branch alone.  One rank, one window.  The plan is printed.
     ``fp8_max_error`` (fp8 networks only): probe the request's first evaluation and keep in bf16 every (layer, GEMM) whose fp8 result is
     further than this from bf16 (engine.calibrate_fp8).
@@ -387,7 +415,8 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
         if guidance is not None:
             raise NotImplementedError("guidance with temporal tiles is out of scope: this pose clip is longer than one window and the tiled loops "
                                       "keep no delta per temporal window")
-        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames, postprocess, fp8_max_error, step_cache)
+        return _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames, postprocess, fp8_max_error, step_cache,
+                          solver)
     pose_lat = engine.encode_first_stage(req["pose"].unsqueeze(0), None, force_encode=True)   # already half resolution (:350-351)
     ref_concat = ref_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)      # B C T H W -> B T C H W
     pose_latent = pose_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)
@@ -398,12 +427,14 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     uc = dict(crossattn=req["uncond_context"], **shared)
     _calibrate(engine, c, uc, (T, C, h, w), steps, fp8_max_error)
     torch.manual_seed(seed)
-    opts = {k: v for k, v in (("step_cache", step_cache), ("guidance", guidance)) if v is not None}
+    opts = {k: v for k, v in (("step_cache", step_cache), ("guidance", guidance), ("solver", solver)) if v is not None}
     z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, **opts)
     if step_cache is not None:
         print(format_step_cache_plan(engine.sampler.last_step_cache_plan))
     if guidance is not None:
         print(format_guidance_plan(engine.sampler.last_guidance_plan))
+    if solver is not None:
+        print(format_solver_plan(engine.sampler.last_solver_plan, solver))
     return _finish(engine, z, t0, vae_chunk_frames, postprocess)
 
 
@@ -425,11 +456,12 @@ def _finish(engine, z, t0, vae_chunk_frames=None, postprocess="torch"):
 
 
 def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_chunk_frames=None, postprocess="torch", fp8_max_error=None,
-               step_cache=None):
+               step_cache=None, solver=None):
     """A pose clip longer than one window (an extension, see the module docstring): RFSamplerLong with the configured sampler's
     parameters over ``tiles``; every window's pose frames [4 start, 4 (start + Tt - 1)] are VAE-encoded on their own (the causal VAE treats
     a window's first frame as a clip's first frame, which is how ``smpl_tiled[:, k]`` is used); noise and decode for the whole latent.
-    ``step_cache``: as for ``run`` -- one plan shared by the tiles, one residual per tile (RFSamplerLong.sample_hip); the plan is printed."""
+    ``step_cache``: as for ``run`` -- one plan shared by the tiles, one residual per tile (RFSamplerLong.sample_hip); the plan is printed.
+    ``solver``: as for ``run`` -- one update of the whole latent per step, one history for every tile; the plan is printed."""
     from . import sampler as S
     Tt = len(tiles[0])
     ref_concat = ref_lat.permute(0, 2, 1, 3, 4).contiguous().to(torch.bfloat16)
@@ -449,7 +481,11 @@ def _run_tiled(cfg, engine, req, ref_lat, tiles, steps, seed, device, t0, vae_ch
     try:
         _calibrate(engine, c, uc, (T, C, h, w), steps, fp8_max_error)       # the first window
         torch.manual_seed(seed)
-        if step_cache is None:
+        if solver is not None:
+            z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, tile_indices=tiles, solver=solver,
+                              **({} if step_cache is None else {"step_cache": step_cache}))
+            print(format_solver_plan(engine.sampler.last_solver_plan, solver))
+        elif step_cache is None:
             z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, tile_indices=tiles)
         else:
             z = engine.sample(c, uc=uc, batch_size=1, shape=(T, C, h, w), num_steps=steps, tile_indices=tiles, step_cache=step_cache)
@@ -521,6 +557,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cfg-plan", default=None,
                     help="opt-in guidance plan, spelled out: one entry per step, comma-separated: 0 = the pair, 1 = cond branch + stored delta, "
                          "2 = cond branch without guidance.  Stands alone; with --step-cache-threshold it must agree with that plan as it stands")
+    ap.add_argument("--solver", choices=SOLVER_CHOICES, default="euler",
+                    help="opt-in solver plan (an extension): dpmpp2m = DPM-Solver++(2M), a second-order multistep update in the data prediction "
+                         "that needs no further network evaluation per step (one fp32 pass and one fp32 latent of history); euler (default) "
+                         "is the route as it was.  The plan is printed.  No step count is recommended: nothing has been measured on real "
+                         "weights.  One GPU; one window, several characters and --tile-frames clips; not with --step-cache-threshold or the "
+                         "--cfg-* plans")
     ap.add_argument("--tile-frames", type=int, default=None,
                     help="pixel frames per temporal window, 4n + 1 (default: the network's num_frames); a pose clip with more frames is sampled "
                          "in overlapping windows (RFSamplerLong), an extension of the reference CLI; such a clip needs 4n + 1 frames")
@@ -577,6 +619,9 @@ def main(argv=None):
         gd = guidance_args(a.cfg_interval, a.cfg_delta_every, a.cfg_plan, a.tile_frames)
         if gd is not None:
             tk["guidance"] = gd
+        sv = solver_args(a.solver, sc, gd)
+        if sv is not None:
+            tk["solver"] = sv
     except ValueError as e:
         ap.error(str(e))
     lines = [(r, i) for i, r in enumerate(a.request)] + (list(read_from_file(a.input_file)) if a.input_file else [])

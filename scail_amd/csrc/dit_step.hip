@@ -1086,12 +1086,17 @@ extern "C" int scail_dit_sample(scail_dit* h, float* x, const float* timesteps, 
 // the Euler loop; reuse == nullptr: every step a plain evaluation (scail_dit_sample_chars), else step i in SCAIL_DIT_CACHE_REUSE mode
 // where reuse[i] != 0 and in SCAIL_DIT_CACHE_FILL mode otherwise (scail_dit_sample_cached, which has checked reuse and the cache).
 // guide == nullptr: every step the batch-2 pair, else step i as its SCAIL_DIT_GUIDE_* entry says (scail_dit_sample_guided, which has
-// checked the plan and the delta buffer)
+// checked the plan and the delta buffer).
+// solver == nullptr: scail_cfg_euler updates x, else scail_cfg_multistep under row i of the plan, with `hist` (scail_dit_sample_solver,
+// which has checked the plan and the history buffer); a solver plan goes with neither reuse nor guide
+struct SolverPlan {
+    const float *sigma, *coef;      // HOST fp32 [n_steps] and [n_steps][3]
+};
 static int sample_impl(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps,
                        float cfg_scale, const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose,
                        int64_t n_char, int64_t pose_frames, const float* rope_cos, const float* rope_sin,
                        int64_t T, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes, void* stream, const uint8_t* reuse, void* cache,
-                       const uint8_t* guide = nullptr, float* delta = nullptr) {
+                       const uint8_t* guide = nullptr, float* delta = nullptr, const SolverPlan* solver = nullptr, float* hist = nullptr) {
     DIT_TRY(chars_check("scail_dit_sample", n_char, pose_frames, T));
     SCAIL_REQUIRE(h != nullptr && x != nullptr && timesteps != nullptr && dsigma != nullptr && n_steps >= 0, "null argument");
     const int64_t step_bytes = scail_dit_chars_workspace_bytes(h, 2, T, H, W, n_char);
@@ -1126,6 +1131,11 @@ static int sample_impl(scail_dit* h, float* x, const float* timesteps, const flo
         DIT_TRY(dit_step_impl(h, xin, timesteps + 2 * i, cond, ref, 1, pose, 1, n_char, pose_frames, rope_cos, rope_sin, v, 2, T, H, W, nullptr,
                               SCAIL_DIT_CFG_PAIR, workspace, step_bytes, stream, mode, cp.r, cp.emb));
         if (guide != nullptr) DIT_TRY(scail_cfg_delta_store(v, delta, n, stream));
+        if (solver != nullptr) {
+            const float* co = solver->coef + 3 * i;
+            DIT_TRY(scail_cfg_multistep(x, v, hist, n, cfg_scale, solver->sigma[i], co[0], co[1], co[2], co[2] != 0.0f, stream));
+            continue;
+        }
         DIT_TRY(scail_cfg_euler(x, v, n, cfg_scale, dsigma[i], stream));
     }
     return 0;
@@ -1295,6 +1305,51 @@ extern "C" int scail_dit_sample_guided(scail_dit* h, float* x, const float* time
                        workspace_bytes, stream, reuse, cache, guide != nullptr ? guide : &none, static_cast<float*>(delta));
 }
 
+// ---- the solver plan (include/scail_dit.h "solver plan") ----
+extern "C" int64_t scail_dit_solver_bytes(int64_t T, int64_t H, int64_t W) {
+    // (not shape_fault: the history is the FULL latent of a tiled clip, whose token count no single evaluation has to hold)
+    if (T <= 0 || H <= 0 || W <= 0 || H % 4 != 0 || W % 4 != 0 || T >= (1 << 15) || H >= (1 << 15) || W >= (1 << 15)) return -1;
+    return align256(T * 16 * H * W * 4);
+}
+// the plan and the history buffer of a *_solver call, before anything is enqueued (host only; the message names index and value)
+static int solver_check(const char* who, int64_t n_steps, const float* sigma, const float* coef, const void* hist, int64_t hist_bytes,
+                        int64_t T, int64_t H, int64_t W) {
+    auto fail = [&](const std::string& msg) {
+        scail_set_error(std::string(who) + ": " + msg);
+        return 1;
+    };
+    if (n_steps < 0) return fail("n_steps must be >= 0, got " + std::to_string(n_steps));
+    if (n_steps > 0 && sigma == nullptr) return fail("null solver sigma with n_steps = " + std::to_string(n_steps));
+    if (n_steps > 0 && coef == nullptr) return fail("null solver coefficients with n_steps = " + std::to_string(n_steps));
+    for (int64_t i = 0; i < n_steps; ++i) {
+        if (!std::isfinite(sigma[i])) return fail("sigma[" + std::to_string(i) + "] = " + std::to_string(sigma[i]) + " is not finite");
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(coef[3 * i + k]))
+                return fail("coef[" + std::to_string(i) + "][" + std::to_string(k) + "] = " + std::to_string(coef[3 * i + k]) + " is not finite");
+    }
+    if (n_steps > 0 && coef[2] != 0.0f)
+        return fail("coef[0][2] = " + std::to_string(coef[2]) + " must be 0: step 0 has no history to use");
+    if (hist == nullptr) return fail("null history buffer (hist_bytes " + std::to_string(hist_bytes) + "; scail_dit_solver_bytes)");
+    if ((reinterpret_cast<uintptr_t>(hist) & 255) != 0)
+        return fail("the history buffer must be 256-byte aligned, got an address that is " + std::to_string(reinterpret_cast<uintptr_t>(hist) & 255) +
+                    " past a multiple of 256");
+    const int64_t need = scail_dit_solver_bytes(T, H, W);
+    if (need < 0) return fail("bad latent shape (T " + std::to_string(T) + ", H " + std::to_string(H) + ", W " + std::to_string(W) + ")");
+    if (hist_bytes < need)
+        return fail("history buffer too small: " + std::to_string(hist_bytes) + " bytes, needs " + std::to_string(need) + " (scail_dit_solver_bytes)");
+    return 0;
+}
+extern "C" int scail_dit_sample_solver(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                                       const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose, int64_t n_char, int64_t pose_frames,
+                                       const float* rope_cos, const float* rope_sin, int64_t T, int64_t H, int64_t W,
+                                       void* workspace, int64_t workspace_bytes, const float* sigma, const float* coef, void* hist,
+                                       int64_t hist_bytes, void* stream) {
+    DIT_TRY(solver_check("scail_dit_sample_solver", n_steps, sigma, coef, hist, hist_bytes, T, H, W));
+    const SolverPlan plan{sigma, coef};
+    return sample_impl(h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose, n_char, pose_frames, rope_cos, rope_sin, T, H, W, workspace,
+                       workspace_bytes, stream, nullptr, nullptr, nullptr, nullptr, &plan, static_cast<float*>(hist));
+}
+
 // ---- the decision signal of the step cache: distances of consecutive steps' time embeddings (include/scail_dit.h) ----
 constexpr int64_t TD_CHUNK = 8;     // scail_small_linear takes M <= 8
 // temb | e1 | emb | adaln: the signal's buffer holds TD_CHUNK + 1 rows -- row 0 is the last step of the chunk before
@@ -1370,12 +1425,14 @@ extern "C" int64_t scail_dit_sample_tiled_workspace_bytes(const scail_dit* h, in
 
 // the tiled loop; cached = false: every evaluation a plain one (scail_dit_sample_tiled), else tile k's evaluation of step i in
 // SCAIL_DIT_CACHE_REUSE mode where reuse[i] != 0 and in SCAIL_DIT_CACHE_FILL mode otherwise, on slab k of the cache
-// (scail_dit_sample_tiled_cached)
+// (scail_dit_sample_tiled_cached).  solver != nullptr: scail_tile_finish_multistep under row i of the plan finishes the step instead of
+// scail_tile_finish (scail_dit_sample_tiled_solver)
 static int sample_tiled_impl(const char* who, scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
                              const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose_tiles,
                              const int32_t* tile_frames, const float* tile_w, const float* inv_wsum, int64_t n_tiles, int64_t T, int64_t Tt,
                              const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace, int64_t workspace_bytes,
-                             void* stream, bool cached, const uint8_t* reuse, void* cache, int64_t cache_bytes) {
+                             void* stream, bool cached, const uint8_t* reuse, void* cache, int64_t cache_bytes,
+                             const SolverPlan* solver = nullptr, void* hist = nullptr, int64_t hist_bytes = 0) {
     auto fail = [&](const std::string& msg) {
         scail_set_error(std::string(who) + ": " + msg);
         return 1;
@@ -1410,6 +1467,7 @@ static int sample_tiled_impl(const char* who, scail_dit* h, float* x, const floa
         DIT_TRY(reuse_check(who, reuse, n_steps));
         DIT_TRY(cache_check(who, h, 0, false, cache, cache_bytes, 2, Tt, H, W, n_tiles));
     }
+    if (solver != nullptr) DIT_TRY(solver_check(who, n_steps, solver->sigma, solver->coef, hist, hist_bytes, T, H, W));
     const void* ptrs[] = {h, x, timesteps, dsigma, cond, ref, pose_tiles, rope_cos, rope_sin, workspace};
     const char* names[] = {"handle", "x", "timesteps", "dsigma", "cond", "ref", "pose_tiles", "rope_cos", "rope_sin", "workspace"};
     for (int i = 0; i < 10; ++i)
@@ -1442,6 +1500,13 @@ static int sample_tiled_impl(const char* who, scail_dit* h, float* x, const floa
                                   cached ? reinterpret_cast<scail_bf16*>(slabs + k * R) : nullptr, cache_emb));
             DIT_TRY(scail_tile_blend_acc(den, v, fr, tile_w + k * Tt, Tt, T, F, cfg_scale, stream));
         }
+        if (solver != nullptr) {
+            // one update of the whole latent after the blend: one history serves every tile
+            const float* co = solver->coef + 3 * i;
+            DIT_TRY(scail_tile_finish_multistep(x, den, inv_wsum, static_cast<float*>(hist), T, F, solver->sigma[i], co[0], co[1], co[2],
+                                                co[2] != 0.0f, stream));
+            continue;
+        }
         DIT_TRY(scail_tile_finish(x, den, inv_wsum, T, F, dsigma[i], stream));
     }
     return 0;
@@ -1461,4 +1526,15 @@ extern "C" int scail_dit_sample_tiled_cached(scail_dit* h, float* x, const float
                                              int64_t workspace_bytes, const uint8_t* reuse, void* cache, int64_t cache_bytes, void* stream) {
     return sample_tiled_impl("scail_dit_sample_tiled_cached", h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose_tiles, tile_frames, tile_w,
                              inv_wsum, n_tiles, T, Tt, rope_cos, rope_sin, H, W, workspace, workspace_bytes, stream, true, reuse, cache, cache_bytes);
+}
+extern "C" int scail_dit_sample_tiled_solver(scail_dit* h, float* x, const float* timesteps, const float* dsigma, int64_t n_steps, float cfg_scale,
+                                             const scail_dit_cond* cond, const scail_bf16* ref, const scail_bf16* pose_tiles,
+                                             const int32_t* tile_frames, const float* tile_w, const float* inv_wsum, int64_t n_tiles, int64_t T,
+                                             int64_t Tt, const float* rope_cos, const float* rope_sin, int64_t H, int64_t W, void* workspace,
+                                             int64_t workspace_bytes, const float* sigma, const float* coef, void* hist, int64_t hist_bytes,
+                                             void* stream) {
+    const SolverPlan plan{sigma, coef};
+    return sample_tiled_impl("scail_dit_sample_tiled_solver", h, x, timesteps, dsigma, n_steps, cfg_scale, cond, ref, pose_tiles, tile_frames, tile_w,
+                             inv_wsum, n_tiles, T, Tt, rope_cos, rope_sin, H, W, workspace, workspace_bytes, stream, false, nullptr, nullptr, 0, &plan,
+                             hist, hist_bytes);
 }

@@ -613,6 +613,100 @@ __global__ void cfg_euler_delta_kernel(float* __restrict__ x, const float* __res
     x[i] = x[i] + step;
 }
 
+// ---- solver plan (include/scail_dit.h "solver plan"; include/scail_hip.h scail_cfg_multistep / scail_tile_finish_multistep) ----
+// One element of a multistep update x <- a x + b D + c D_prev around the data prediction D = x - sigma d, every operation rounded on
+// its own.  use_prev == 0: `hist` is not read (the caller has not loaded it either); it leaves as D.
+__device__ __forceinline__ void multistep_elem(float& x, float& hist, float d, float sigma, float a, float b, float c, int use_prev) {
+#pragma clang fp contract(off)
+    const float sd = sigma * d;
+    const float D = x - sd;
+    const float ax = a * x;
+    const float bD = b * D;
+    float y = ax + bD;
+    if (use_prev) {
+        const float ch = c * hist;
+        y = y + ch;
+    }
+    x = y;
+    hist = D;
+}
+__device__ __forceinline__ float cfg_combine(float vu, float vc, float cfg) {
+#pragma clang fp contract(off)
+    const float diff = vc - vu;
+    const float g = cfg * diff;
+    return vu + g;
+}
+// v = [v_u; v_c] fp32 [2, n].  vec: x, v and hist are 16-byte aligned -- thread t takes elements 4t .. 4t + 3 of the first n & ~3 with
+// 16-byte accesses (v_c = v + n is 16-byte aligned only where n % 4 == 0; elsewhere its four values are loaded one by one), and the
+// first n & 3 threads take one element of the tail each.  Not vec: one element per thread.
+__global__ void cfg_multistep_kernel(float* __restrict__ x, const float* __restrict__ v, float* __restrict__ hist, int64_t n, float cfg,
+                                     float sigma, float a, float b, float c, int use_prev, int vec) {
+#pragma clang fp contract(off)
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n4 = vec ? n >> 2 : 0;
+    if (t < n4) {
+        const int64_t i = 4 * t;
+        float4 xv = *reinterpret_cast<const float4*>(x + i);
+        const float4 vu = *reinterpret_cast<const float4*>(v + i);
+        float4 vc;
+        if ((n & 3) == 0) {
+            vc = *reinterpret_cast<const float4*>(v + n + i);
+        } else {
+            vc = make_float4(v[n + i], v[n + i + 1], v[n + i + 2], v[n + i + 3]);
+        }
+        float4 hv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (use_prev) hv = *reinterpret_cast<const float4*>(hist + i);
+        multistep_elem(xv.x, hv.x, cfg_combine(vu.x, vc.x, cfg), sigma, a, b, c, use_prev);
+        multistep_elem(xv.y, hv.y, cfg_combine(vu.y, vc.y, cfg), sigma, a, b, c, use_prev);
+        multistep_elem(xv.z, hv.z, cfg_combine(vu.z, vc.z, cfg), sigma, a, b, c, use_prev);
+        multistep_elem(xv.w, hv.w, cfg_combine(vu.w, vc.w, cfg), sigma, a, b, c, use_prev);
+        *reinterpret_cast<float4*>(x + i) = xv;
+        *reinterpret_cast<float4*>(hist + i) = hv;
+    }
+    const int64_t i = 4 * n4 + t;      // the tail (vec), or every element
+    if (i < n) {
+        float xs = x[i], hs = 0.0f;
+        if (use_prev) hs = hist[i];
+        multistep_elem(xs, hs, cfg_combine(v[i], v[n + i], cfg), sigma, a, b, c, use_prev);
+        x[i] = xs;
+        hist[i] = hs;
+    }
+}
+// The tiled loop's finishing pass under a solver plan: tile_finish_kernel's d = den * inv_j, then the multistep update; den is left
+// zeroed.  vec: F % 4 == 0 and x, den and hist are 16-byte aligned, so every frame is -- thread e takes elements 4e .. 4e + 3 of frame
+// f0 + j; a frame size that is no multiple of 4 takes the scalar form throughout (its frames do not start on 16 bytes).
+__global__ void tile_finish_multistep_kernel(float* __restrict__ x, float* __restrict__ den, float* __restrict__ hist, TileArgs w, int64_t f0,
+                                             int64_t F, float sigma, float a, float b, float c, int use_prev, int vec) {
+#pragma clang fp contract(off)
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t j = blockIdx.y;
+    const float inv = w.w[j];
+    if (vec) {
+        if (4 * e >= F) return;
+        const int64_t o = (f0 + j) * F + 4 * e;
+        float4 xv = *reinterpret_cast<const float4*>(x + o);
+        const float4 dn = *reinterpret_cast<const float4*>(den + o);
+        float4 hv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (use_prev) hv = *reinterpret_cast<const float4*>(hist + o);
+        multistep_elem(xv.x, hv.x, dn.x * inv, sigma, a, b, c, use_prev);
+        multistep_elem(xv.y, hv.y, dn.y * inv, sigma, a, b, c, use_prev);
+        multistep_elem(xv.z, hv.z, dn.z * inv, sigma, a, b, c, use_prev);
+        multistep_elem(xv.w, hv.w, dn.w * inv, sigma, a, b, c, use_prev);
+        *reinterpret_cast<float4*>(x + o) = xv;
+        *reinterpret_cast<float4*>(hist + o) = hv;
+        *reinterpret_cast<float4*>(den + o) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    if (e >= F) return;
+    const int64_t o = (f0 + j) * F + e;
+    float xs = x[o], hs = 0.0f;
+    if (use_prev) hs = hist[o];
+    multistep_elem(xs, hs, den[o] * inv, sigma, a, b, c, use_prev);
+    x[o] = xs;
+    hist[o] = hs;
+    den[o] = 0.0f;
+}
+
 __global__ void zero_f32_kernel(float* __restrict__ y, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) y[i] = 0.0f;
@@ -985,6 +1079,23 @@ extern "C" int scail_cfg_euler_delta(float* x, const float* v_c, const float* de
     return scail_check_launch("cfg_euler_delta");
 }
 
+// ---- solver plan: host-side checks (the message names the value) + launches ----
+extern "C" int scail_cfg_multistep(float* x, const float* v, float* hist, int64_t n, float cfg_scale, float sigma, float a, float b, float c,
+                                   int use_prev, void* stream) {
+    if (int rc = cfg_delta_n_check("scail_cfg_multistep", n)) return rc;
+    if (n == 0) return 0;
+    if (x == nullptr || v == nullptr || hist == nullptr) {
+        scail_set_error(std::string("scail_cfg_multistep: null pointer: ") + (x == nullptr ? "x" : v == nullptr ? "v" : "hist") +
+                        " (n = " + std::to_string(n) + ")");
+        return 1;
+    }
+    const int vec = aligned16(x) && aligned16(v) && aligned16(hist);
+    const int64_t n4 = vec ? n >> 2 : 0, tail = n - 4 * n4, threads = n4 > tail ? n4 : tail;
+    hipLaunchKernelGGL(cfg_multistep_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, v, hist, n, cfg_scale,
+                       sigma, a, b, c, use_prev != 0, vec);
+    return scail_check_launch("cfg_multistep");
+}
+
 // ---- temporal tiling: host-side checks (the message names the value) + launches ----
 // Tt in 1..min(T, 64), every frame index in [0, T) and, `unique`, no index twice (two tile frames would accumulate into one latent frame
 // concurrently).  Shared with the sampler entry point (dit_step.hip), which checks every tile before anything is enqueued.
@@ -1073,6 +1184,26 @@ extern "C" int scail_tile_finish(float* x, float* den, const float* inv_wsum, in
         hipLaunchKernelGGL(tile_finish_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream, x, den, a, f0, F,
                            dsigma);
         if (int rc = scail_check_launch("tile_finish")) return rc;
+    }
+    return 0;
+}
+
+// scail_tile_finish under a solver plan: the same checks, launches and treatment of den / inv_wsum, the multistep update in its place
+extern "C" int scail_tile_finish_multistep(float* x, float* den, const float* inv_wsum, float* hist, int64_t T, int64_t F, float sigma, float a,
+                                           float b, float c, int use_prev, void* stream) {
+    if (int rc = tile_shape_check("scail_tile_finish_multistep", F)) return rc;
+    SCAIL_REQUIRE(T >= 0 && T < (1ll << 31), "bad frame count");
+    SCAIL_REQUIRE(x != nullptr && den != nullptr && inv_wsum != nullptr && hist != nullptr, "null pointer");
+    if (F == 0) return 0;
+    const int vec = (F & 3) == 0 && aligned16(x) && aligned16(den) && aligned16(hist);
+    const int64_t per_frame = vec ? F >> 2 : F;
+    for (int64_t f0 = 0; f0 < T; f0 += TILE_MAX) {      // 64 frames' factors per launch
+        const int64_t n = T - f0 < TILE_MAX ? T - f0 : TILE_MAX;
+        TileArgs w = {};
+        for (int64_t j = 0; j < n; ++j) w.w[j] = inv_wsum[f0 + j];
+        hipLaunchKernelGGL(tile_finish_multistep_kernel, dim3((unsigned)((per_frame + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream,
+                           x, den, hist, w, f0, F, sigma, a, b, c, use_prev != 0, vec);
+        if (int rc = scail_check_launch("tile_finish_multistep")) return rc;
     }
     return 0;
 }

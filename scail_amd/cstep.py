@@ -81,6 +81,7 @@ class CStep:
         self._cache = None                               # ((B, T, H, W, device), buffer) of the step cache, once a FILL has run
         self._tile_cache = None                          # ((n_tiles, Tt, H, W, device), buffer) of the tiled sampler's cache (sample_tiled_cached)
         self._delta = None                               # ((T, H, W, device), buffer) of the guidance plan's delta (sample_guided)
+        self._hist = None                                # ((T, H, W, device), buffer) of the solver plan's history (sample / sample_tiled)
         self._fp8_buf = None
         self._probe = None                               # (table, scratch) while the fp8 probe is on
         self.num_layers = net.num_layers
@@ -223,10 +224,60 @@ class CStep:
                self.CFG_PAIR if cfg_pair else 0, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
         return out
 
-    def sample(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose, cos, sin, n_char: int = 1) -> torch.Tensor:
+    # ---- solver plan (include/scail_dit.h "solver plan") ----
+    def solver_bytes(self, T, H, W) -> int:
+        n = L.load().scail_dit_solver_bytes(T, H, W)
+        if n < 0:
+            raise L.ScailHipError(f"scail_dit_solver_bytes: bad shape (T {T}, H {H}, W {W})")
+        return n
+
+    def _hist_for(self, T, H, W, device) -> torch.Tensor:
+        """The history buffer of a (T, H, W) latent, a new one when the shape or the device changed.  Handed out by ``_ws_for`` and kept
+        beside the workspace, as ``_cache_for`` does."""
+        key = (T, H, W, torch.device(device))
+        if self._hist is None or self._hist[0] != key:
+            ws, self._ws = self._ws, None
+            try:
+                buf = self._ws_for(self.solver_bytes(T, H, W), device, f"scail_dit_solver_bytes (T {T}, H {H}, W {W})")
+            finally:
+                self._ws = ws
+            self._hist = (key, buf)
+        return self._hist[1]
+
+    def solver_history(self, T, H, W) -> torch.Tensor:
+        """The data prediction D (1, T, 16, H, W) fp32 of the last step of a solver loop: a view of the history buffer"""
+        assert self._hist is not None and self._hist[0][:3] == (T, H, W), "no history buffer of this shape"
+        return self._hist[1][:4 * T * 16 * H * W].view(torch.float32).view(1, T, 16, H, W)
+
+    @staticmethod
+    def solver_tables(solver, n):
+        """The host arrays of a ``solver`` = (sigma, coef) option: (sigma fp32 [n], coef fp32 [n][3]); sigma = the steps' starting sigmas,
+        coef = one (a, b, c) per step (sampler.plan_solver)."""
+        sigma, coef = solver
+        sg = [float(v) for v in (sigma.tolist() if torch.is_tensor(sigma) else sigma)]
+        rows = [tuple(float(v) for v in r) for r in coef]
+        if len(sg) != n or len(rows) != n or any(len(r) != 3 for r in rows):
+            raise L.ScailHipError(f"solver: needs one starting sigma and one (a, b, c) per step ({n}), got {len(sg)} sigmas and {len(rows)} rows")
+        return (C.c_float * max(n, 1))(*sg), (C.c_float * max(3 * n, 1))(*[v for r in rows for v in r])
+
+    def sample(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose, cos, sin, n_char: int = 1, solver=None) -> torch.Tensor:
         """The whole Euler loop in one C call (scail_dit_sample_chars).  x32 (1,T,16,H,W) fp32 is updated in place and returned;
-        ``sigmas`` is the host schedule (n_steps + 1 values); ``cond`` the batch-2 conditioning (uncond, cond); ``n_char`` as for step."""
+        ``sigmas`` is the host schedule (n_steps + 1 values); ``cond`` the batch-2 conditioning (uncond, cond); ``n_char`` as for step.
+        ``solver``: None, or (sigma, coef) -- the steps' starting sigmas and one (a, b, c) per step (sampler.plan_solver): the loop under a
+        solver plan (scail_dit_sample_solver), still ONE call that only enqueues."""
         _, T, _, H, W = x32.shape
+        if solver is not None:
+            ts, dsa, n = self._schedule(sigmas, x32.device)
+            sg, co = self.solver_tables(solver, n)
+            hist = self._hist_for(T, H, W, x32.device)
+            ws = self._ws_for(L.load().scail_dit_sample_chars_workspace_bytes(self._h, T, H, W, n_char), x32.device,
+                              f"scail_dit_sample_chars_workspace_bytes (T {T}, H {H}, W {W}, n_char {n_char})")
+            cc = _cond_struct(cond)
+            assert x32.is_contiguous() and x32.dtype == torch.float32 and ref.shape[0] == 1 and pose.shape[0] == 1
+            L.call("scail_dit_sample_solver", self._h, x32.data_ptr(), ts.data_ptr(), C.cast(dsa, C.c_void_p), n, float(cfg_scale),
+                   C.byref(cc), ref.data_ptr(), pose.data_ptr(), n_char, pose.shape[1], cos.data_ptr(), sin.data_ptr(), T, H, W,
+                   ws.data_ptr(), ws.numel(), sg, co, hist.data_ptr(), hist.numel(), torch.cuda.current_stream().cuda_stream)
+            return x32
         ws = self._ws_for(L.load().scail_dit_sample_chars_workspace_bytes(self._h, T, H, W, n_char), x32.device,
                           f"scail_dit_sample_chars_workspace_bytes (T {T}, H {H}, W {W}, n_char {n_char})")
         ts, dsa, n = self._schedule(sigmas, x32.device)
@@ -416,19 +467,28 @@ class CStep:
         iw = inv_wsum.detach().cpu().float().reshape(-1).tolist()
         return (C.c_int32 * len(fr))(*fr), (C.c_float * len(tw))(*tw), (C.c_float * len(iw))(*iw)
 
-    def sample_tiled(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose_tiles, tile_indices, tile_w, inv_wsum, cos, sin) -> torch.Tensor:
+    def sample_tiled(self, x32, sigmas, cfg_scale, cond: Dict, ref, pose_tiles, tile_indices, tile_w, inv_wsum, cos, sin, solver=None) -> torch.Tensor:
         """The whole RFSamplerLong loop in one C call (scail_dit_sample_tiled).  x32 (1,T,16,H,W) fp32 is updated in place and returned;
         ``pose_tiles`` bf16 (1, n_tiles, Tt, 16, H/2, W/2); ``tile_indices`` n_tiles lists of Tt frame indices; ``tile_w`` host fp32
-        (n_tiles, Tt) = m_k * tile_weight; ``inv_wsum`` host fp32 (T); cos / sin: the tables of a Tt-frame clip."""
+        (n_tiles, Tt) = m_k * tile_weight; ``inv_wsum`` host fp32 (T); cos / sin: the tables of a Tt-frame clip.
+        ``solver``: None, or ``sample``'s (sigma, coef): the loop under a solver plan (scail_dit_sample_tiled_solver), with one history of
+        the full latent."""
         _, T, _, H, W = x32.shape
         n_tiles = len(tile_indices)
         Tt = len(tile_indices[0]) if n_tiles else 0
+        hist = self._hist_for(T, H, W, x32.device) if solver is not None else None
         ws = self._ws_for(self.sample_tiled_workspace_bytes(T, Tt, H, W), x32.device, "scail_dit_sample_tiled_workspace_bytes")
         ts, dsa, n = self._schedule(sigmas, x32.device)
         fr, tw, iw = self.tile_tables(tile_indices, tile_w, inv_wsum)
         cc = _cond_struct(cond)
         assert x32.is_contiguous() and x32.dtype == torch.float32 and ref.shape[0] == 1 and pose_tiles.is_contiguous()
         assert pose_tiles.shape == (1, n_tiles, Tt, 16, H // 2, W // 2) and pose_tiles.dtype == torch.bfloat16
+        if solver is not None:
+            sg, co = self.solver_tables(solver, n)
+            L.call("scail_dit_sample_tiled_solver", self._h, x32.data_ptr(), ts.data_ptr(), C.cast(dsa, C.c_void_p), n, float(cfg_scale), C.byref(cc),
+                   ref.data_ptr(), pose_tiles.data_ptr(), fr, tw, iw, n_tiles, T, Tt, cos.data_ptr(), sin.data_ptr(), H, W,
+                   ws.data_ptr(), ws.numel(), sg, co, hist.data_ptr(), hist.numel(), torch.cuda.current_stream().cuda_stream)
+            return x32
         L.call("scail_dit_sample_tiled", self._h, x32.data_ptr(), ts.data_ptr(), C.cast(dsa, C.c_void_p), n, float(cfg_scale), C.byref(cc),
                ref.data_ptr(), pose_tiles.data_ptr(), fr, tw, iw, n_tiles, T, Tt, cos.data_ptr(), sin.data_ptr(), H, W,
                ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)

@@ -614,32 +614,43 @@ class DiffusionTransformer(nn.Module):
         cos, sin = self._rope(T_rope, x32.shape[3] // 2, x32.shape[4] // 2, 0, 0, dev, n_char)
         return self._executor(), cond, cos, sin, x32.float().contiguous().clone()
 
-    def sample_c(self, x32, sigmas, cfg_scale, ctx, ref, pose, clip, cond_key=None, reuse=None, guide=None):
+    def sample_c(self, x32, sigmas, cfg_scale, ctx, ref, pose, clip, cond_key=None, reuse=None, guide=None, solver=None):
         """The whole RFSampler Euler loop as ONE C call (scail_dit_sample_chars, include/scail_dit.h): x32 (1,T,16,H,W) fp32,
         ctx (2, Lt, text_dim) = [uncond; cond], ref (1,C,16,H,W), pose (1,C*T,16,H/2,W/2) for C >= 1 characters (C = ref.shape[1]),
         clip (1,Lc,1280).  Single rank.  ``reuse``: None, or the step cache's plan -- one 0 / 1 per step, 1 = reuse the block residual
         of the last computed step (scail_dit_sample_cached).  ``guide``: None, or the guidance plan -- one lib.GUIDE_* entry per step
-        (sampler.plan_guidance; scail_dit_sample_guided), alone or together with ``reuse``."""
+        (sampler.plan_guidance; scail_dit_sample_guided), alone or together with ``reuse``.  ``solver``: None, or the solver plan
+        (sigma, coef) -- the steps' starting sigmas and one (a, b, c) per step (sampler.plan_solver; scail_dit_sample_solver) --, which
+        goes with neither ``reuse`` nor ``guide``."""
         T, n_char, dev = x32.shape[1], ref.shape[1], x32.device
         self._check_chars(n_char, T, pose.shape[1])
+        if solver is not None and (reuse is not None or guide is not None):
+            raise NotImplementedError("a solver plan together with the step cache or the guidance plan is out of scope (include/scail_dit.h "
+                                      "\"solver plan\")")
         if reuse is not None:
             self._step_cache_ok()
         if guide is not None:
             self._step_cache_ok("guidance")
         ex, cond, cos, sin, x = self._sample_prelude(x32, ctx, clip, cond_key, T, n_char)
+        if solver is not None:
+            return ex.sample(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, n_char=n_char, solver=solver)
         if guide is not None:
             return ex.sample_guided(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, guide, reuse=reuse, n_char=n_char)
         if reuse is not None:
             return ex.sample_cached(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, reuse, n_char=n_char)
         return ex.sample(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose, dev), cos, sin, n_char=n_char)
 
-    def sample_tiled_c(self, x32, sigmas, cfg_scale, ctx, ref, pose_tiles, clip, tile_indices, tile_w, inv_wsum, cond_key=None, reuse=None):
+    def sample_tiled_c(self, x32, sigmas, cfg_scale, ctx, ref, pose_tiles, clip, tile_indices, tile_w, inv_wsum, cond_key=None, reuse=None,
+                       solver=None):
         """The whole RFSamplerLong loop (temporal tiling) as ONE C call (scail_dit_sample_tiled, include/scail_dit.h): x32 (1,T,16,H,W) fp32,
         ctx (2, Lt, text_dim) = [uncond; cond], ref (1,1,16,H,W), pose_tiles (1, n_tiles, Tt, 16, H/2, W/2), clip (1,Lc,1280);
         tile_w (n_tiles, Tt) = m_k * tile_weight and inv_wsum (T) as RFSamplerLong.sample_hip forms them.  Single rank, one character.
         ``reuse``: None, or the step cache's plan -- one 0 / 1 per step, shared by every tile; 1 = every tile reuses its own block
-        residual of the last computed step (scail_dit_sample_tiled_cached)."""
+        residual of the last computed step (scail_dit_sample_tiled_cached).  ``solver``: None, or ``sample_c``'s solver plan
+        (scail_dit_sample_tiled_solver); not together with ``reuse``."""
         dev, Tt = x32.device, len(tile_indices[0])
+        if solver is not None and reuse is not None:
+            raise NotImplementedError("a solver plan together with the step cache is out of scope (include/scail_dit.h \"solver plan\")")
         if reuse is not None:
             self._step_cache_ok()
         if ref.shape[1] != 1:
@@ -648,6 +659,9 @@ class DiffusionTransformer(nn.Module):
             raise L.ScailHipError(f"smpl_tiled must be (1, n_tiles = {len(tile_indices)}, Tt = {Tt}, 16, H/2, W/2), got "
                                   f"{tuple(pose_tiles.shape)}")
         ex, cond, cos, sin, x = self._sample_prelude(x32, ctx, clip, cond_key, Tt, 1)
+        if solver is not None:
+            return ex.sample_tiled(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose_tiles, dev), tile_indices, tile_w, inv_wsum,
+                                   cos, sin, solver=solver)
         if reuse is not None:
             return ex.sample_tiled_cached(x, sigmas, cfg_scale, cond, _as_bf16(ref, dev), _as_bf16(pose_tiles, dev), tile_indices, tile_w, inv_wsum,
                                           cos, sin, reuse)

@@ -59,7 +59,7 @@ class SATVideoDiffusionEngine(nn.Module):
     def sample(self, cond: Dict, uc: Optional[Dict] = None, batch_size: int = 1, shape: Union[None, Tuple, List] = None,
                prefix=None, concat_images=None, ofs=None, fps=None, tile_indices=None,
                generator: Optional[torch.Generator] = None, num_steps: Optional[int] = None, fused: bool = True, step_cache=None, guidance=None,
-               **kwargs):
+               solver=None, **kwargs):
         """diffusion_video.py:456-587.  shape = (T, C, H, W).  Noise is drawn in fp32 on the host RNG
         stream of ``generator`` like ``torch.randn(batch, *shape)`` (:470), broadcast inside the
         sequence-parallel group (:486-493) and H/W-chunked (:495-552); result gathered to SP rank 0 (:571-585).
@@ -67,7 +67,18 @@ class SATVideoDiffusionEngine(nn.Module):
         ``tile_indices`` it reaches RFSamplerLong.sample_hip: one plan for every tile and one block residual per tile, for the requests
         that take the one-call tiled loop; the sampler refuses the others (a callback, several characters, tiles above 64 frames).
         ``guidance``: None, or the guidance option of RFSampler.sample_hip (an extension, opt-in; fused HIP network, one rank, no temporal
-        tiles): which steps run the CFG pair, the cond branch with the stored delta, or the cond branch alone."""
+        tiles): which steps run the CFG pair, the cond branch with the stored delta, or the cond branch alone.
+        ``solver``: None, or the solver option of RFSampler.sample_hip / RFSamplerLong.sample_hip (an extension, opt-in; fused HIP network,
+        one rank, with or without ``tile_indices``): "dpmpp2m" or "dpm1" in place of the Euler update.  Not with ``step_cache`` / ``guidance``."""
+        if solver is not None:
+            S.check_solver_name(solver, "solver")
+            if not (fused and isinstance(self.network, DiffusionTransformer)):
+                raise NotImplementedError("solver needs the fused path of the HIP network (RFSampler.sample_hip)")
+            if self.sp is not None and self.sp.size > 1:
+                raise NotImplementedError("solver runs on a single rank only: the sequence-parallel calls have no solver form")
+            if step_cache is not None or guidance is not None:
+                raise NotImplementedError("solver together with step_cache or guidance is out of scope: the solver's pass takes the pair "
+                                          "[v_u; v_c] of a full step (composition is the natural follow-up)")
         if guidance is not None:
             if not (fused and isinstance(self.network, DiffusionTransformer)):
                 raise NotImplementedError("guidance needs the fused path of the HIP network (RFSampler.sample_hip)")
@@ -106,6 +117,8 @@ class SATVideoDiffusionEngine(nn.Module):
             extra["step_cache"] = step_cache
         if guidance is not None:
             extra["guidance"] = guidance
+        if solver is not None:
+            extra["solver"] = solver
         if fused and isinstance(self.network, DiffusionTransformer):
             samples = self.sampler.sample_hip(self.network, randn, cond, uc, num_steps=num_steps, chunk_dim=chunk_dim, **extra)
         else:

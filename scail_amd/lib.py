@@ -55,9 +55,12 @@ SIGNATURES = {
     # the guidance plan's fp32 passes: v_c - v_u stored, and the Euler update around a stored delta (NULL: no guidance)
     "scail_cfg_delta_store": [_p, _p, _i64, _p],
     "scail_cfg_euler_delta": [_p, _p, _p, _i64, _f, _f, _p],
+    # the solver plan's fp32 pass: CFG + one multistep update (x, v, hist, n, cfg, sigma, a, b, c, use_prev)
+    "scail_cfg_multistep": [_p, _p, _p, _i64, _f, _f, _f, _f, _f, _i, _p],
     "scail_tile_gather": [_p, _p, _p, _i64, _i64, _i64, _p],
     "scail_tile_blend_acc": [_p, _p, _p, _p, _i64, _i64, _i64, _f, _p],
     "scail_tile_finish": [_p, _p, _p, _i64, _i64, _f, _p],
+    "scail_tile_finish_multistep": [_p, _p, _p, _p, _i64, _i64, _f, _f, _f, _f, _i, _p],
     "scail_conv3d_cl": [_p, _p, _p, _p, _i64, _p, _i64, _p, _p],
     "scail_conv3d_cl_norm": [_p, _p, _p, _p, _i64, _p, _p, _p],
     "scail_conv3d_cl_resid_norm": [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p],
@@ -143,6 +146,11 @@ SIGNATURES = {
     "scail_dit_guidance_bytes": [_i64, _i64, _i64],
     "scail_dit_sample_guided": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _i64,
                                 _p, _p, _i64, _p],
+    # the solver plan: the sampler loops with a coefficient table (host fp32 sigma, host fp32 coef [n][3], hist, hist bytes)
+    "scail_dit_solver_bytes": [_i64, _i64, _i64],
+    "scail_dit_sample_solver": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p],
+    "scail_dit_sample_tiled_solver": [_p, _p, _p, _p, _i64, _f, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, _p, _i64,
+                                      _p, _p, _p, _i64, _p],
     "scail_dit_time_distances_bytes": [_p, _i],
     "scail_dit_time_distances": [_p, _p, _i64, _i, _p, _p, _i64, _p],
     # include/scail_vae.h (scail_amd/cvae.py builds the structs)
@@ -201,7 +209,9 @@ ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- sc
                          # and the 6-bit GEMMs, scail_quant_mxfp6_rows / scail_gemm_mxfp6 / scail_dit_fp6_weight_bytes / scail_dit_enable_fp6,
                          # and the tiled step cache, scail_dit_sample_tiled_cache_bytes / scail_dit_sample_tiled_cached,
                          # and the guidance plan, scail_cfg_delta_store / scail_cfg_euler_delta / scail_dit_step_branch /
-                         # scail_dit_guidance_bytes / scail_dit_sample_guided)
+                         # scail_dit_guidance_bytes / scail_dit_sample_guided,
+                         # and the solver plan, scail_cfg_multistep / scail_tile_finish_multistep / scail_dit_solver_bytes /
+                         # scail_dit_sample_solver / scail_dit_sample_tiled_solver)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);

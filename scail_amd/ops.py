@@ -558,6 +558,17 @@ def cfg_euler_delta_(x, v_c, delta, cfg_scale, dsigma):
     return x
 
 
+def cfg_multistep_(x, v, hist, cfg_scale, sigma, a, b, c, use_prev):
+    """In place, one step of a solver plan (scail_cfg_multistep; include/scail_dit.h "solver plan"): d = v[0] + cfg * (v[1] - v[0]),
+    D = x - sigma * d, x = a * x + b * D (+ c * hist with ``use_prev``), hist = D, every operation rounded on its own.  x, hist fp32 of one
+    size, v fp32 (2, ...).  Without ``use_prev`` hist is only written."""
+    _chk(x, f32, "cfg_multistep.x"); _chk(v, f32, "cfg_multistep.v"); _chk(hist, f32, "cfg_multistep.hist")
+    assert x.is_contiguous() and v.is_contiguous() and hist.is_contiguous() and v.numel() == 2 * x.numel() and hist.numel() == x.numel()
+    L.call("scail_cfg_multistep", x.data_ptr(), v.data_ptr(), hist.data_ptr(), x.numel(), float(cfg_scale), float(sigma), float(a), float(b),
+           float(c), 1 if use_prev else 0, _stream())
+    return x
+
+
 # ---- temporal tiling (RFSamplerLong): the frame indices / weights are HOST values that travel in the kernel arguments ----
 def _tile_frames(frames):
     import ctypes as C
@@ -607,6 +618,19 @@ def tile_finish_(x, den, inv_wsum, dsigma):
     w, nw = _host_f32(inv_wsum)
     assert nw == x.shape[1]
     L.call("scail_tile_finish", x.data_ptr(), den.data_ptr(), w, x.shape[1], x[0, 0].numel(), float(dsigma), _stream())
+    return x
+
+
+def tile_finish_multistep_(x, den, inv_wsum, hist, sigma, a, b, c, use_prev):
+    """In place, ``tile_finish_`` under a solver plan (scail_tile_finish_multistep): d = den * inv_wsum[:, None], D = x - sigma * d,
+    x = a * x + b * D (+ c * hist with ``use_prev``), hist = D, every operation rounded on its own; ``den`` is left zeroed.  x, den, hist
+    fp32 (1, T, ...); ``inv_wsum``: T host values."""
+    _chk(x, f32, "tile_finish_multistep.x"); _chk(den, f32, "tile_finish_multistep.den"); _chk(hist, f32, "tile_finish_multistep.hist")
+    assert x.is_contiguous() and den.is_contiguous() and hist.is_contiguous() and x.shape == den.shape == hist.shape and x.shape[0] == 1
+    w, nw = _host_f32(inv_wsum)
+    assert nw == x.shape[1]
+    L.call("scail_tile_finish_multistep", x.data_ptr(), den.data_ptr(), w, hist.data_ptr(), x.shape[1], x[0, 0].numel(), float(sigma), float(a),
+           float(b), float(c), 1 if use_prev else 0, _stream())
     return x
 
 

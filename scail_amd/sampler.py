@@ -15,6 +15,7 @@ four elementwise torch ops; the arithmetic is the same fp32 expression.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict
 
 import numpy as np
@@ -282,6 +283,71 @@ def merge_guidance_with_step_cache(guide, reuse):
     return out
 
 
+SOLVERS = ("dpmpp2m", "dpm1")
+
+
+def check_solver_name(solver, what="plan_solver"):
+    if solver not in SOLVERS:
+        raise ValueError(f"{what}: unknown solver {solver!r} (one of {SOLVERS}; None is the Euler loop)")
+    return solver
+
+
+def plan_solver(sigmas, solver):
+    """The solver plan (include/scail_dit.h "solver plan"): one (a, b, c) per sampler step, x_{i+1} = a x_i + b D_i + c D_{i-1} with the
+    data prediction D_i = x_i - sigma_i d_i.  Pure host, fp64 (Python floats) from the host fp32 schedule; needs no device.
+
+    ``sigmas``: the whole schedule, n_steps + 1 values from the first step's starting sigma to the last step's end (``RFSampler.sigmas()``).
+    ``solver``: "dpmpp2m" = DPM-Solver++(2M), or "dpm1" = its first-order rows everywhere (for tests and A/B).  With rho =
+    sigma_{i+1} / sigma_i a first-order row is (rho, 1 - rho, 0) -- Euler mathematically, not in bits -- and a second-order row
+    (rho, (1 - rho)(1 + 1 / (2 r_i)), -(1 - rho) / (2 r_i)), r_i = h_{i-1} / h_i, h_i = lambda_{i+1} - lambda_i, lambda = log((1 - sigma) /
+    sigma).  A step is second order only where i >= 1 and lambda_{i-1}, lambda_i, lambda_{i+1} are finite, so a schedule from 1 to 0 has
+    steps 0, 1 and the last one first order, and its last row is (0, 1, 0).  a + b + c = 1.
+    Refused by name: an unknown solver, fewer than 2 sigmas, a sigma outside [0, 1], a sigma of 0 anywhere but last, a schedule that is
+    not strictly decreasing."""
+    check_solver_name(solver)
+    sig = [float(v) for v in (sigmas.tolist() if torch.is_tensor(sigmas) else sigmas)]
+    if len(sig) < 2:
+        raise ValueError(f"plan_solver: a schedule has at least 2 sigmas (one step), got {len(sig)}")
+    for i, v in enumerate(sig):
+        if not 0.0 <= v <= 1.0:
+            raise ValueError(f"plan_solver: sigma[{i}] = {v} lies outside [0, 1]")
+    for i, v in enumerate(sig[:-1]):
+        if v == 0.0:
+            raise ValueError(f"plan_solver: sigma[{i}] = 0 is not the last value: a step cannot start at sigma = 0")
+    for i in range(len(sig) - 1):
+        if not sig[i + 1] < sig[i]:
+            raise ValueError(f"plan_solver: the schedule must be strictly decreasing, got sigma[{i}] = {sig[i]} then sigma[{i + 1}] = {sig[i + 1]}")
+    lam = [math.log((1.0 - v) / v) if 0.0 < v < 1.0 else (-math.inf if v == 1.0 else math.inf) for v in sig]
+    rows = []
+    for i in range(len(sig) - 1):
+        rho = sig[i + 1] / sig[i]
+        if solver == "dpmpp2m" and i >= 1 and all(math.isfinite(lam[j]) for j in (i - 1, i, i + 1)):
+            r = (lam[i] - lam[i - 1]) / (lam[i + 1] - lam[i])
+            c = -(1.0 - rho) / (2.0 * r)
+            rows.append((rho, (1.0 - rho) - c, c))
+        else:
+            rows.append((rho, 1.0 - rho, 0.0))
+    return rows
+
+
+def solver_uses_prev(row) -> bool:
+    """Whether a row of a solver plan reads the history, as the library decides it: its c, rounded to fp32, is not zero"""
+    return float(np.float32(row[2])) != 0.0
+
+
+def _solver_alone(solver, step_cache, guidance, chunk_dim):
+    """The refusals of a ``solver`` option that RFSampler.sample_hip and RFSamplerLong.sample_hip share, before the network is touched"""
+    check_solver_name(solver, "solver")
+    if step_cache is not None:
+        raise NotImplementedError("solver together with step_cache is out of scope: the solver's pass takes the pair [v_u; v_c] of a full step "
+                                  "(composition is the natural follow-up); drop one of the two")
+    if guidance is not None:
+        raise NotImplementedError("solver together with guidance is out of scope: the solver's pass takes the pair [v_u; v_c], a cond-only step has "
+                                  "v_c and a stored delta (composition is the natural follow-up); drop one of the two")
+    if chunk_dim is not None:
+        raise NotImplementedError("solver runs on a single rank only: not on sequence-parallel ranks (chunk_dim)")
+
+
 STEP_CACHE_KEYS = ("threshold", "coefficients", "keep_first", "keep_last", "signal", "mask")
 
 
@@ -359,7 +425,7 @@ class RFSampler:
         return merge_guidance_with_step_cache(plan, reuse)
 
     def sample_hip(self, network, x, cond: Dict, uc: Dict, num_steps=None, scale=None, chunk_dim=None,
-                   step_callback=None, step_cache=None, guidance=None):
+                   step_callback=None, step_cache=None, guidance=None, solver=None):
         """x (1,T,16,H,W) fp32 on the GPU; cond/uc as the CLI builds them (sample_video.py:455-470).
         One step = one batch-2 DiT forward (uncond, cond) + scail_cfg_euler.
         ``step_cache`` (opt-in, an extension; None = this method as it was): a dict with ``threshold`` and optionally ``coefficients``,
@@ -371,7 +437,14 @@ class RFSampler:
         branch alone without guidance (include/scail_dit.h "guidance plan").  Combines with ``step_cache`` (merge_guidance_with_step_cache).
         Both routes take the plan and give the same bits, provided the conditioning GEMMs compute a row of the cond prompt alone as they
         compute it in the batch of two (they do wherever both sizes take one kernel: scail_gemm_kernel_name_for).
-        ``self.last_guidance_plan`` keeps it."""
+        ``self.last_guidance_plan`` keeps it.
+        ``solver`` (opt-in, an extension; None = this method as it was): "dpmpp2m" or "dpm1" (plan_solver): the Euler update is replaced by
+        x <- a x + b D + c D_prev in the data prediction D (include/scail_dit.h "solver plan"), with one fp32 latent of history and no
+        further network evaluation.  The one call (scail_dit_sample_solver) and the host loop below -- the instrumented route:
+        ``step_callback``, SCAIL_C_STEP=0 -- take the same table and give the same bits.  Not together with ``step_cache`` or ``guidance``, not
+        on sequence-parallel ranks.  ``self.last_solver_plan`` keeps the table."""
+        if solver is not None:
+            _solver_alone(solver, step_cache, guidance, chunk_dim)
         sig = self.sigmas(num_steps)                     # host fp32, like the reference
         cfg = float(self.guider.scale if scale is None else scale)
         ctx = torch.cat((uc["crossattn"], cond["crossattn"]), 0)
@@ -390,10 +463,18 @@ class RFSampler:
             if x.shape[0] != 1 or shared["ref_concat"].shape[0] != 1 or shared["concat_smpl_render"].shape[0] != 1:
                 raise NotImplementedError("guidance takes one latent with one shared ref / pose (the cond branch is a batch-1 evaluation)")
             gplan = self.last_guidance_plan = self.guidance_plan(sig, guidance, plan)
+        splan = None
+        if solver is not None:
+            if x.shape[0] != 1:
+                raise NotImplementedError(f"solver takes one latent (the update pass reads one CFG pair), got a batch of {x.shape[0]}")
+            splan = self.last_solver_plan = plan_solver(sig, solver)
         if (_executor_takes_loop(network) and step_callback is None and chunk_dim is None
                 and shared["ref_concat"].shape[0] == 1 and shared["concat_smpl_render"].shape[0] == 1):
             # the whole loop enqueued by ONE call into the library (scail_dit_sample_chars; any number of reference frames / pose
             # streams); same kernels, same order
+            if splan is not None:
+                return network.sample_c(x, sig, cfg, ctx, shared["ref_concat"], shared["concat_smpl_render"],
+                                        shared["image_clip_features"], cond_key=("sample_hip", id(cond)), solver=(sig[:-1], splan))
             if gplan is not None:
                 return network.sample_c(x, sig, cfg, ctx, shared["ref_concat"], shared["concat_smpl_render"],
                                         shared["image_clip_features"], cond_key=("sample_hip", id(cond)), reuse=plan, guide=gplan)
@@ -404,6 +485,7 @@ class RFSampler:
                                     shared["image_clip_features"], cond_key=("sample_hip", id(cond)))
         x = x.float().contiguous().clone()
         delta = torch.empty_like(x) if gplan is not None and any(g != GUIDE_COND for g in gplan) else None
+        hist = torch.empty_like(x) if splan is not None else None
         for i in range(len(sig) - 1):
             t = (sig[i] * 1000.0).repeat(2).to(x.device)                 # c_noise = 1000 sigma (RFScaling)
             if plan is not None:
@@ -420,6 +502,11 @@ class RFSampler:
             v = network.forward_f32(xin, t, ctx, None, cond_key=("sample_hip", id(cond)), chunk_dim=chunk_dim, **shared)
             if gplan is not None:
                 ops.cfg_delta_store(v, out=delta)
+            if splan is not None:
+                ops.cfg_multistep_(x, v, hist, cfg, float(sig[i]), *splan[i], use_prev=solver_uses_prev(splan[i]))
+                if step_callback is not None:
+                    step_callback(i, x)
+                continue
             ops.cfg_euler_(x, v, cfg, float(sig[i + 1] - sig[i]))
             if step_callback is not None:
                 step_callback(i, x)
@@ -511,14 +598,19 @@ class RFSamplerLong(RFSampler):
         return idxs, tile_w, 1.0 / wsum
 
     def sample_hip(self, network, x, cond: Dict, uc: Dict, num_steps=None, scale=None, chunk_dim=None,
-                   step_callback=None, tile_indices=None, step_cache=None, guidance=None):
+                   step_callback=None, tile_indices=None, step_cache=None, guidance=None, solver=None):
         """Fused path for the HIP network: per step and tile one batch-2 DiT forward (fp32 out); the text / CLIP
         conditioning (step- AND tile-invariant) is computed once per request.
         ``step_cache`` (opt-in; None = this method as it was): RFSampler.sample_hip's option.  One plan for every tile -- it depends on the
         schedule and the weights alone -- and one block residual per tile (scail_dit_sample_tiled_cached).  Only requests that take the
         one-call route below have a cached form (``_one_call_ok``); every other one is refused before the network is touched: there is no
-        cached host loop.  ``self.last_step_cache_plan`` keeps the plan."""
+        cached host loop.  ``self.last_step_cache_plan`` keeps the plan.
+        ``solver`` (opt-in; None = this method as it was): RFSampler.sample_hip's option.  The update happens once per step on the whole
+        latent, after the blend, so one history serves every tile (scail_dit_sample_tiled_solver; the host loop below takes the same table
+        through ops.tile_finish_multistep_ and gives the same bits).  ``self.last_solver_plan`` keeps the table."""
         self._check(tile_indices)
+        if solver is not None:
+            _solver_alone(solver, step_cache, guidance, chunk_dim)
         if guidance is not None:
             raise NotImplementedError("guidance with temporal tiles (RFSamplerLong) is out of scope: the tiled loops (scail_dit_sample_tiled*) keep "
                                       "no delta per tile; sample the clip in one window or drop the option")
@@ -540,11 +632,20 @@ class RFSamplerLong(RFSampler):
         plan = None
         if step_cache is not None:
             plan = self.last_step_cache_plan = self.step_cache_plan(network, sig, step_cache)
+        splan = None
+        if solver is not None:
+            if x.shape[0] != 1:
+                raise NotImplementedError(f"solver takes one latent, got a batch of {x.shape[0]}")
+            splan = self.last_solver_plan = plan_solver(sig, solver)
         idxs, tile_w, inv_wsum = self._tile_table(tile_indices, x.shape[1], x.device)
         if self._one_call_ok(network, x, shared["ref_concat"], smpl_tiled, tile_indices, step_callback, chunk_dim):
             # the whole loop enqueued by ONE call into the library (scail_dit_sample_tiled): same network kernels, the gather / blend /
             # Euler arithmetic below as HIP row kernels that round every operation on its own -- the same bits.  The weights are handed
             # over as host values once per request.
+            if splan is not None:
+                return network.sample_tiled_c(x, sig, cfg, ctx, shared["ref_concat"], smpl_tiled, shared["image_clip_features"],
+                                              [list(map(int, t)) for t in tile_indices], tile_w.cpu(), inv_wsum.cpu(),
+                                              cond_key=("sample_hip", id(cond)), solver=(sig[:-1], splan))
             if plan is not None:
                 return network.sample_tiled_c(x, sig, cfg, ctx, shared["ref_concat"], smpl_tiled, shared["image_clip_features"],
                                               [list(map(int, t)) for t in tile_indices], tile_w.cpu(), inv_wsum.cpu(),
@@ -554,6 +655,7 @@ class RFSamplerLong(RFSampler):
                                           cond_key=("sample_hip", id(cond)))
         x = x.float().contiguous().clone()
         dev = x.device
+        hist, inv_host = (torch.empty_like(x), inv_wsum.cpu()) if splan is not None else (None, None)
         tile_w, inv = tile_w[:, :, None, None, None], inv_wsum[:, None, None, None]
         for i in range(len(sig) - 1):
             t = (sig[i] * 1000.0).repeat(2).to(dev)
@@ -564,6 +666,11 @@ class RFSamplerLong(RFSampler):
                                         chunk_dim=chunk_dim, concat_smpl_render=smpl_tiled[:, k], **shared)
                 d = v[0:1] + cfg * (v[1:2] - v[0:1])                     # VanillaCFG, guiders.py:41-45
                 den[:, idxs[k]] += tile_w[k] * d
+            if splan is not None:
+                ops.tile_finish_multistep_(x, den, inv_host, hist, float(sig[i]), *splan[i], use_prev=solver_uses_prev(splan[i]))
+                if step_callback is not None:
+                    step_callback(i, x)
+                continue
             x = x + float(sig[i + 1] - sig[i]) * (den * inv)
             if step_callback is not None:
                 step_callback(i, x)
