@@ -50,7 +50,7 @@ const char* scail_last_error(void);
  * scail_dit.h's scail_dit_fp6_weight_bytes / scail_dit_enable_fp6, and for the guidance plan, scail_cfg_delta_store / scail_cfg_euler_delta
  * and scail_dit.h's scail_dit_step_branch / scail_dit_guidance_bytes / scail_dit_sample_guided, and for the solver plan,
  * scail_cfg_multistep / scail_tile_finish_multistep and scail_dit.h's scail_dit_solver_bytes / scail_dit_sample_solver /
- * scail_dit_sample_tiled_solver.) */
+ * scail_dit_sample_tiled_solver, and for the LoRA merge, scail_lora_merge_bf16 / scail_add_scaled_bf16.) */
 int scail_abi_version(void);
 
 /* ---- epilogues of scail_gemm_bf16 ---------------------------------------------------------- */
@@ -404,6 +404,29 @@ int scail_cfg_euler_delta(float* x, const float* v_c, const float* delta, int64_
  */
 int scail_cfg_multistep(float* x, const float* v, float* hist, int64_t n, float cfg_scale, float sigma, float a, float b, float c,
                         int use_prev, void* stream);
+
+/*
+ * LoRA adapters (scail_amd/lora.py): merge a low-rank weight update, or a full difference, into a bf16 weight, in place and once.
+ * w is an N x K window of a bf16 matrix with row stride ldw (elements); a row slice of a fused matrix is w + n0 * ldw.  up is fp32
+ * [N, r] (row stride ld_up), down fp32 [r, K] (ld_down), d fp32 [N, K] (ldd).  The factors are fp32 because adapter files come in fp16,
+ * bf16 or fp32 and all three widen exactly.  Per element (n, k), in this order:
+ *   acc = 0.0f
+ *   for j = 0 .. r-1 (ascending):   acc = acc + up[n, j] * down[j, k]
+ *   w[n, k] = bf16_rne( float(w[n, k]) + scale * acc )          scail_lora_merge_bf16
+ *   w[n, k] = bf16_rne( float(w[n, k]) + scale * d[n, k] )      scail_add_scaled_bf16
+ * EVERY operation is rounded on its own (no fused multiply-add), as in scail_cfg_euler_delta: the call gives the bits of the torch fp32
+ * expression, one tensor operation per arithmetic operation, and one rounding to bf16 (to nearest, ties to even).  The product runs on
+ * the VALU: an fp32 MFMA is an fmaf chain, which is not this arithmetic.
+ * In place and elementwise in (n, k): one thread reads, then writes, its own elements; nothing outside the N x K window is touched.
+ * 16-byte accesses to w where w is 16-byte aligned and ldw a multiple of 8, a scalar path for row tails and everything else.  There is
+ * no limit on r below 2^15: the r loop is chunked through LDS.  N == 0, K == 0 or (merge) r == 0 launches nothing and w keeps its bits,
+ * a -0 included.
+ * Errors (host side, before any launch, naming the value): negative N, K or r; r >= 2^15; ldw < K, ld_up < r, ld_down < K, ldd < K; a
+ * scale that is not finite; 2^31 workgroups or more; with a non-empty problem a null w, up, down or d.
+ */
+int scail_lora_merge_bf16(scail_bf16* w, int64_t ldw, int64_t N, int64_t K, const float* up, int64_t ld_up, const float* down,
+                          int64_t ld_down, int64_t r, float scale, void* stream);
+int scail_add_scaled_bf16(scail_bf16* w, int64_t ldw, int64_t N, int64_t K, const float* d, int64_t ldd, float scale, void* stream);
 
 /*
  * Temporal tiling of RFSamplerLong (sampling.py:986-1085): the three elementwise fp32 passes of one sampler step around the network

@@ -210,7 +210,29 @@ def request_from_files(ref_image: str, pose_video: str, cfg, conditioning: str =
     return req, (H, W)
 
 
-def build_engine(cfg, load=None, device="cuda"):
+def lora_arg(value):
+    """``--lora FILE[:STRENGTH]`` -> (path, strength): what follows the LAST colon is the strength when it reads as a number (so a path
+    with colons works as long as a strength is given), else the whole value is the path and the strength is 1"""
+    path, sep, tail = str(value).rpartition(":")
+    if sep and path:
+        try:
+            strength = float(tail)
+        except ValueError:
+            return str(value), 1.0
+        if not math.isfinite(strength):
+            raise ValueError(f"--lora {value}: the strength must be finite")
+        return path, strength
+    return str(value), 1.0
+
+
+def apply_loras(engine, loras):
+    """Merge the adapters [(path, strength), ...] into the engine's network, in order (engine.load_lora), and print one table each"""
+    from . import lora
+    for path, strength in loras or ():
+        print(lora.format_table(path, strength, engine.load_lora(path, strength)))
+
+
+def build_engine(cfg, load=None, device="cuda", loras=None):
     """Under ``python -m torch.distributed.run`` the whole world is one sequence-parallel group (the reference's CLI: dp = 1,
     sample_video.py:229): every rank builds the engine, encodes the request and joins ``engine.sample``; SP rank 0 decodes
     and saves (:484-507)."""
@@ -228,6 +250,7 @@ def build_engine(cfg, load=None, device="cuda"):
     if load:
         from .checkpoint import load_checkpoint
         load_checkpoint(engine, load, force_inference=cfg.get("args", {}).get("force_inference", True))
+    apply_loras(engine, loras)                                             # after --load: an adapter goes onto the checkpoint's weights
     return engine
 
 
@@ -378,8 +401,11 @@ def _calibrate(engine, c, uc, shape, steps, fp8_max_error):
 
 
 def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frames=None, engine=None, tile_frames=None, tile_overlap=None,
-        vae_chunk_frames=None, postprocess="torch", fp8_max_error=None, step_cache=None, guidance=None, solver=None):
-    """``solver``: None (the Euler loop as it was), or "dpmpp2m" (solver_args; RFSampler.sample_hip / RFSamplerLong.sample_hip): a second-order
+        vae_chunk_frames=None, postprocess="torch", fp8_max_error=None, step_cache=None, guidance=None, solver=None, loras=None):
+    """``loras``: None, or [(path, strength), ...] -- LoRA adapters merged into the network's weights in this order after ``load``
+    (scail_amd/lora.py; an extension), when this call builds the engine; an ``engine`` that is passed in is merged by its owner
+    (engine.load_lora), once.  One table per adapter is printed.
+    ``solver``: None (the Euler loop as it was), or "dpmpp2m" (solver_args; RFSampler.sample_hip / RFSamplerLong.sample_hip): a second-order
     multistep update in the data prediction, still one executor call: one window, several characters, temporal tiles.  One rank; not with
     ``step_cache`` or ``guidance``.  The plan is printed.
     ``guidance``: None, or the guidance option (guidance_args; RFSampler.sample_hip): which steps run the CFG pair, the cond branch with
@@ -396,7 +422,9 @@ def run(cfg, inputs=None, steps=None, load=None, seed=1234, device="cuda", frame
     if postprocess == "hip" and not torch.cuda.is_available():
         raise lib.ScailHipError("postprocess='hip' writes the uint8 frames with the library's kernels and needs a GPU; there is no host fallback")
     fp8_max_error = fp8_max_error_arg(fp8_max_error, cfg["model"]["network_config"].get("params", {}).get("gemm_precision", "bf16"))
-    engine = engine or build_engine(cfg, load, device)
+    if loras and engine is not None:
+        raise ValueError("loras go with the engine this call builds; merge them into a passed engine once, with engine.load_lora")
+    engine = engine or build_engine(cfg, load, device, loras=loras)
     H, W = cfg.get("args", {}).get("sampling_image_size", [512, 896])
     net = engine.network
     frames = frames or min(81, net.num_frames)
@@ -563,6 +591,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "is the route as it was.  The plan is printed.  No step count is recommended: nothing has been measured on real "
                          "weights.  One GPU; one window, several characters and --tile-frames clips; not with --step-cache-threshold or the "
                          "--cfg-* plans")
+    ap.add_argument("--lora", action="append", default=[], metavar="FILE[:STRENGTH]",
+                    help="merge a LoRA adapter into the DiT's weights on the GPU (an extension): .safetensors or a torch.load-able file with "
+                         "lora_A / lora_B or lora_down / lora_up pairs, alpha, diff and diff_b keys under the native or Wan2.1 module "
+                         "names; repeatable, applied in order after --load; STRENGTH defaults to 1.  One table per adapter is printed.  "
+                         "The Wan2.1 names could not be checked against a real adapter file")
     ap.add_argument("--tile-frames", type=int, default=None,
                     help="pixel frames per temporal window, 4n + 1 (default: the network's num_frames); a pose clip with more frames is sampled "
                          "in overlapping windows (RFSamplerLong), an extension of the reference CLI; such a clip needs 4n + 1 frames")
@@ -622,13 +655,14 @@ def main(argv=None):
         sv = solver_args(a.solver, sc, gd)
         if sv is not None:
             tk["solver"] = sv
+        loras = [lora_arg(v) for v in a.lora]
     except ValueError as e:
         ap.error(str(e))
     lines = [(r, i) for i, r in enumerate(a.request)] + (list(read_from_file(a.input_file)) if a.input_file else [])
     if lines:
         import os
         from . import video_io
-        engine = build_engine(cfg, a.load)
+        engine = build_engine(cfg, a.load, loras=loras)
         td = engine.network.text_dim
         for line, cnt in lines:
             text, input_dir, image_path, pose_path = parse_request(line)
@@ -660,7 +694,7 @@ def main(argv=None):
                 req.update(encode_conditioning(a.prompt, a.negative_prompt, req["ref"], text_dim, a.tokenizer, a.t5_ckpt, a.clip_ckpt,
                                                max_length=512 if text_dim == 4096 else 16))
             return req
-    video, z, dt = run(cfg, inputs, a.steps, a.load, a.seed, **tk)
+    video, z, dt = run(cfg, inputs, a.steps, a.load, a.seed, loras=loras, **tk)
     if video is None:
         return
     print(f"sampled latent {tuple(z.shape)} -> video {tuple(video.shape)} in {dt:.2f} s")

@@ -248,6 +248,7 @@ class DiffusionTransformer(nn.Module):
         # one C call per network evaluation (include/scail_dit.h) instead of ~25 ctypes calls per layer; env override
         self.use_c_step = os.environ.get("SCAIL_C_STEP", "1") != "0"
         self._cstep = None
+        self.loras = []                    # (adapter name or "<dict>", strength, entries) of every merge_lora, in order
         self._c_blocks = False             # test hook: drive the executor block by block (scail_dit_block per layer, the rest from the host): cross-check of the one-call step
 
     # ------------------------------------------------------------------------------------------
@@ -346,6 +347,34 @@ class DiffusionTransformer(nn.Module):
         self._prepared = None
         self._cond_cache = None
         return super().load_state_dict(*a, **k)
+
+    def weights_changed(self):
+        """Drop everything derived from the parameters' VALUES, after they were changed in place (merge_lora): the prepared arena (fp32
+        copies of the vectors and tables, the padded patch matrices), the conditioning cache (K / V projected through the old weights)
+        and the executor, and with it the fp8 / MX / fp6 weight buffers, the probe state and every cache the binding owns.  The next
+        call rebuilds them.  The per-layer fp8 selection (fp8_layer_masks) is the caller's choice and stays; the probe table it may
+        have come from measured the old weights and goes.  (scail_amd/sat_mixins.py HipBackend compares its executor's arena with
+        prepare() and follows.)"""
+        self._prepared = None
+        self._cond_cache = None
+        self._cstep = None
+        self.fp8_probe_table = None
+
+    @torch.no_grad()
+    def merge_lora(self, adapter, strength=1.0):
+        """Merge a LoRA adapter into the weights, on the GPU and in place (an extension, opt-in; scail_amd/lora.py has the arithmetic, the
+        key conventions and what is not known about them).  ``adapter``: a path (.safetensors or torch.load-able) or a dict of tensors.
+        The adapter is validated whole before any weight is touched (ValueError naming the key); parameters without storage (init_seed=None
+        before load_state_dict(assign=True)) or off the GPU are refused by name.  Returns the plan's summary rows (lora.summary) and
+        appends (name or "<dict>", strength, entries) to ``self.loras``.  Adapters stack; the result depends on their order in the last
+        bf16 bit.  There is no un-merge -- merge_lora(adapter, -strength) is not the inverse in bits (two bf16 roundings): load the
+        checkpoint again.  Sequence-parallel ranks hold replicated weights: every rank merges the same file."""
+        from . import lora
+        tensors = adapter if isinstance(adapter, dict) else lora.read_adapter(adapter)
+        plan = lora.plan_adapter(self, tensors, strength)
+        lora.apply_plan(self, plan)
+        self.loras.append(("<dict>" if isinstance(adapter, dict) else str(adapter), float(strength), len(plan)))
+        return lora.summary(plan)
 
     # ------------------------------------------------------------------------------------------
     # weight arena for the kernels

@@ -55,6 +55,10 @@ class SATVideoDiffusionEngine(nn.Module):
     def network(self) -> DiffusionTransformer:
         return self.model.diffusion_model
 
+    def load_lora(self, path, strength: float = 1.0):
+        """Merge a LoRA adapter into the network's weights (an extension, opt-in): DiffusionTransformer.merge_lora"""
+        return self.network.merge_lora(path, strength)
+
     @torch.no_grad()
     def sample(self, cond: Dict, uc: Optional[Dict] = None, batch_size: int = 1, shape: Union[None, Tuple, List] = None,
                prefix=None, concat_images=None, ofs=None, fps=None, tile_indices=None,

@@ -92,6 +92,9 @@ SIGNATURES = {
     # MXFP6: packed e2m3 codes [rows, 3 cols / 4 bytes] + E8M0 bytes; leading dimensions of packed matrices in bytes
     "scail_quant_mxfp6_rows": [_p, _i64, _p, _i64, _p, _i64, _i64, _i64, _p],
     "scail_gemm_mxfp6": [_p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _p, _i64, _p, _i64, _i64, _p],
+    # LoRA adapters: the in-place merge of up @ down, or of a full difference, into a bf16 weight window (scail_amd/lora.py)
+    "scail_lora_merge_bf16": [_p, _i64, _i64, _i64, _p, _i64, _p, _i64, _i64, _f, _p],
+    "scail_add_scaled_bf16": [_p, _i64, _i64, _i64, _p, _i64, _f, _p],
     "scail_resize_crop_aa": [_p, _i, _p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _p],
     "scail_pose_half": [_p, _p, _i64, _i64, _p, _i64, _i64, _i64, _i64, _p],
     # include/scail_dit.h (structs are passed by pointer; scail_amd/cstep.py builds them)
@@ -211,7 +214,8 @@ ABI_VERSION = 8          # (the streamed VAE decode only adds entry points -- sc
                          # and the guidance plan, scail_cfg_delta_store / scail_cfg_euler_delta / scail_dit_step_branch /
                          # scail_dit_guidance_bytes / scail_dit_sample_guided,
                          # and the solver plan, scail_cfg_multistep / scail_tile_finish_multistep / scail_dit_solver_bytes /
-                         # scail_dit_sample_solver / scail_dit_sample_tiled_solver)
+                         # scail_dit_sample_solver / scail_dit_sample_tiled_solver,
+                         # and the LoRA merge, scail_lora_merge_bf16 / scail_add_scaled_bf16)
                          # 8 = temporal tiling (scail_tile_gather / _blend_acc / _finish, scail_dit_sample_tiled);
                          # 7 = the character count in the network-level calls (scail_patchify_chars, scail_dit_*_chars);
                          # 6 = the fp8 GEMM path (scail_quant_fp8_rows, scail_gemm_fp8, scail_dit_fp8_weight_bytes, scail_dit_enable_fp8);

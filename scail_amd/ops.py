@@ -569,6 +569,38 @@ def cfg_multistep_(x, v, hist, cfg_scale, sigma, a, b, c, use_prev):
     return x
 
 
+# ---- LoRA adapters (scail_amd/lora.py): in place on a bf16 weight window, every operation rounded on its own ----
+def _window(t, dtype, name):
+    """(rows, cols, row stride) of a 2-D GPU tensor whose columns are contiguous: a matrix or a row / column slice of one"""
+    _chk(t, dtype, name)
+    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise L.ScailHipError(f"{name}: expected a 2-D tensor with contiguous columns, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t.shape[0], t.shape[1], (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def lora_merge_(w, up, down, scale):
+    """In place, w = bf16(float(w) + scale * (up @ down)) with the product accumulated over ascending j in fp32, every multiply and add
+    rounded on its own (scail_lora_merge_bf16).  w bf16 (N, K), a matrix or a row window of one; up fp32 (N, r); down fp32 (r, K)."""
+    N, K, ldw = _window(w, bf16, "lora_merge.w")
+    Nu, r, ld_up = _window(up, f32, "lora_merge.up")
+    rd, Kd, ld_down = _window(down, f32, "lora_merge.down")
+    if Nu != N or Kd != K or rd != r:
+        raise L.ScailHipError(f"lora_merge: up {tuple(up.shape)} @ down {tuple(down.shape)} does not give w {tuple(w.shape)}")
+    L.call("scail_lora_merge_bf16", w.data_ptr(), ldw, N, K, up.data_ptr(), ld_up, down.data_ptr(), ld_down, r, float(scale), _stream())
+    return w
+
+
+def add_scaled_(w, d, scale):
+    """In place, w = bf16(float(w) + scale * d), both operations rounded on their own (scail_add_scaled_bf16).  w bf16 (N, K), a matrix
+    or a row window of one; d fp32 (N, K)."""
+    N, K, ldw = _window(w, bf16, "add_scaled.w")
+    Nd, Kd, ldd = _window(d, f32, "add_scaled.d")
+    if (Nd, Kd) != (N, K):
+        raise L.ScailHipError(f"add_scaled: d {tuple(d.shape)} does not match w {tuple(w.shape)}")
+    L.call("scail_add_scaled_bf16", w.data_ptr(), ldw, N, K, d.data_ptr(), ldd, float(scale), _stream())
+    return w
+
+
 # ---- temporal tiling (RFSamplerLong): the frame indices / weights are HOST values that travel in the kernel arguments ----
 def _tile_frames(frames):
     import ctypes as C

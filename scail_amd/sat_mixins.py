@@ -107,6 +107,7 @@ class HipBackend:
     def __init__(self, engine=None):
         self.engine = engine
         self._cstep = None
+        self._arena = None             # the engine.prepare() dict self._cstep was built from
         self._cond_src = None          # the (text, clip) tensors the cached K / V were projected from (strong references)
         self._cond = None
 
@@ -139,8 +140,10 @@ class HipBackend:
         if layer_id == 0 or src is None or src[0] is not kt or src[1] is not kc or src[2] != (kt._version, kc._version):
             self._cond = eng.kv_conditioning(text, clip)
             self._cond_src = (kt, kc, (kt._version, kc._version))
-        if self._cstep is None:
-            self._cstep = CStep(eng, eng.prepare())
+        if self._cstep is None or (self._arena is not None and self._arena is not eng.prepare()):
+            # no executor yet, or the engine has a new arena: the weights were reloaded or changed in place (merge_lora)
+            self._arena = eng.prepare()
+            self._cstep = CStep(eng, self._arena)
         cos, sin = eng._rope(*rope, hidden.device)
         return self._cstep.block(layer_id, hidden, mod, self._cond, cos, sin)
 
