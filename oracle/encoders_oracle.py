@@ -73,9 +73,10 @@ def clip_visual_31(sd, imgs, num_heads, num_layers, patch, eps=1e-5):
     return x
 
 
-def clip_preprocess(frames):
-    """CLIPModel.visual preprocessing clip.py:511-522: frames (B,3,H,W) in [-1,1] -> bicubic 224 -> [0,1] -> normalise."""
-    x = F.interpolate(frames.float(), size=(224, 224), mode="bicubic", align_corners=False)
+def clip_preprocess(frames, size=224):
+    """CLIPModel.visual preprocessing clip.py:511-522: frames (B,3,H,W) in [-1,1] -> bicubic ``size`` (the tower's image_size) ->
+    [0,1] -> normalise."""
+    x = F.interpolate(frames.float(), size=(size, size), mode="bicubic", align_corners=False)
     x = x * 0.5 + 0.5
     mean = torch.tensor([0.48145466, 0.4578275, 0.40821073]).view(1, 3, 1, 1)
     std = torch.tensor([0.26862954, 0.26130258, 0.27577711]).view(1, 3, 1, 1)

@@ -52,6 +52,7 @@ class VisionTransformer(nn.Module):
                                                                       else torch.randn(shape, device=dev, generator=g) * std)
             _register(self, n, nn.Parameter(w.to(torch.bfloat16), requires_grad=False))
         self._prepared = None
+        self._tap = None                   # debug/test hook: called as _tap(layer_index, hidden_states); -1 = the pre_norm output
 
     def load_state_dict(self, *a, **k):
         self._prepared = None
@@ -97,7 +98,9 @@ class VisionTransformer(nn.Module):
         xs = ops.row_affine(tok, addrow=W["pos"])
         xs = ops.layernorm_affine(xs, *W["pre"], eps=self.norm_eps)
         scale = 1.0 / math.sqrt(D // H)
-        for lw in W["layers"]:
+        if self._tap is not None:
+            self._tap(-1, xs)
+        for i, lw in enumerate(W["layers"]):
             h = ops.layernorm_affine(xs, *lw["n1"], eps=self.norm_eps)
             qkv = ops.gemm(h, *lw["qkv"])
             a = ops.attn_small(qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:], H, scale=scale)
@@ -105,6 +108,8 @@ class VisionTransformer(nn.Module):
             h = ops.layernorm_affine(xs, *lw["n2"], eps=self.norm_eps, out=h)
             h1 = ops.gemm(h, *lw["fc1"], epilogue=L.EPI_GELU_ERF)
             ops.gemm(h1, *lw["fc2"], out=xs, epilogue=L.EPI_RESID, resid=xs)
+            if self._tap is not None:
+                self._tap(i, xs)
         return xs
 
 

@@ -65,6 +65,7 @@ class T5Encoder(nn.Module):
             _register(self, n, nn.Parameter(w.to(torch.bfloat16), requires_grad=False))
         self._prepared = None
         self._buckets: Dict = {}
+        self._tap = None                   # debug/test hook: called as _tap(layer_index, hidden_states); -1 = the embedding
 
     def load_state_dict(self, *a, **k):
         self._prepared = None
@@ -102,7 +103,9 @@ class T5Encoder(nn.Module):
         bucket = self._buckets[Ln]
         km = mask.to(dev).to(torch.int32).contiguous() if mask is not None else None
         A = self.dim_attn
-        for lw in W["layers"]:
+        if self._tap is not None:
+            self._tap(-1, x)
+        for i, lw in enumerate(W["layers"]):
             xn = ops.rmsnorm_rope(x, lw["n1"], out=torch.empty_like(x), eps=1e-6)
             qkv = ops.gemm(xn, lw["qkv"])
             a = ops.attn_small(qkv[..., :A], qkv[..., A:2 * A], qkv[..., 2 * A:], self.num_heads, scale=1.0, bucket=bucket,
@@ -113,6 +116,8 @@ class T5Encoder(nn.Module):
             h = ops.gemm(xn, lw["fc1"])
             ops.mul_(h, gate)
             ops.gemm(h, lw["fc2"], out=x, epilogue=L.EPI_RESID, resid=x)
+            if self._tap is not None:
+                self._tap(i, x)
         return ops.rmsnorm_rope(x, W["norm"], out=torch.empty_like(x), eps=1e-6)
 
 
